@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """Benchmark of the WOFT hot path on MI355X: tracked frames/sec at 1080p, 12 RAFT iterations.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N>1: one rank per GPU over RCCL; launched by torch.distributed.run -- by the caller, or by bench.py itself
    when it is started as a plain `python bench.py --gpus N` without the torchrun environment)
+
+A plain run does what the headline needs and nothing more: set-up, W warm-up steps, the K timed steps, the outputs of
+the last timed step (--dump-outputs) and the result line.  --full adds everything else: the per-launch HIP events of
+the roofline fields inside the timed region, the isolated lookup timings, the side runs (other precisions, correlation
+modes, weight head, graph replay, host frames, reference-form configs, ladder, lost frames, two sequences, steady
+state) and the CPU baseline with its EPE gate; the --no-* options switch parts of it off.
 
 One step = one tracker.track() call: pre-warp of the frame, weighted-RAFT flow (full model, 12
 iterations) template -> frame, masking + Sobol-500 subsampling, weighted least-squares homography,
@@ -110,6 +116,19 @@ def cpu_baseline(sd, template, mask, frames_np, iters):
     return times, keep["tc"]
 
 
+def dump_outputs(out_dir, result):
+    """What one track() call handed its caller, as <out_dir>/<name>.npy in float64: the pose (H_cur2init.npy) and every
+    numeric field of its meta (meta_<field>.npy: the global / local / last-good homographies, lost, N_lost, ...)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    H, meta = result
+    arrays = {"H_cur2init": H}
+    for key, v in sorted(vars(meta).items()):
+        if isinstance(v, (np.ndarray, bool, int, float, np.number, np.bool_)):
+            arrays[f"meta_{key}"] = v
+    for name, v in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.asarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -130,7 +149,7 @@ def main():
     ap.add_argument("--full-weight-head", action="store_true",
                     help="evaluate the weight head on every template pixel, as the reference's network does, instead of "
                          "only where the tracker reads the weights (its template mask: the tracker's default; identical "
-                         "tracks).  The default run times this variant too ('alt_weight_head').")
+                         "tracks).  A --full run times this variant too ('alt_weight_head').")
     ap.add_argument("--no-alt-corr", action="store_true",
                     help="skip the short extra run in the other correlation mode (reported under 'alt_corr'; in the "
                          "default mode it also measures the volume lookup for 'roofline_lookup')")
@@ -145,7 +164,15 @@ def main():
                          "'steady_state' passes")
     ap.add_argument("--no-template-cache", action="store_true",
                     help="recompute the template's features every frame, as the reference does")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (roofline events in the timed region, isolated "
+                         "lookup timings, side runs, CPU baseline + EPE gate); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed track() call returned (the pose and the numeric "
+                         "fields of its meta) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- N ranks of this same command line, one per GPU
@@ -230,14 +257,14 @@ def main():
     # instance of the register-streamed-weights conv kernel = the motion encoder's three 3x3 layers (update.py:83,85,86)
     ROOF_TAGS = ("convc2", "convf2", "convc2+convf2", "convm")
     # (HIP events are stream-ordered barriers: the volume-free lookup, not this mode's roofline kernel, is timed in isolation
-    #  below -- 'lookup_otf_by_flow_field' -- instead of inside the timed region)
-    plan.lookup_events = [] if corr_mode == "volume" else None
+    #  below -- 'lookup_otf_by_flow_field' -- instead of inside the timed region).  A plain run records no events.
+    plan.lookup_events = [] if args.full and corr_mode == "volume" else None
     wh_events, conv_events = [], {t: [] for t in ROOF_TAGS}
     wdist.barrier()
     torch.cuda.synchronize()
     wait0 = tracker.host_wait_s
     t0 = time.perf_counter()
-    results += track_all(tracker, Wm, K, timed=(plan, wh_events, conv_events))
+    results += track_all(tracker, Wm, K, timed=(plan, wh_events, conv_events) if args.full else None)
     t_track = time.perf_counter() - t0
     host_busy = t_track - (tracker.host_wait_s - wait0)   # the rank's Python launch loop: wall time not spent blocked on the GPU
     tracks = wdist.gather_tracks(results[Wm:])
@@ -252,6 +279,8 @@ def main():
 
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), results[-1])
     n_lost = int(tracks[:, :, 9].sum().item())
     peak_gb = torch.cuda.max_memory_allocated() / 2 ** 30        # every device buffer of the path is a torch tensor
 
@@ -387,7 +416,7 @@ def main():
     if len(same) > 1:                    # (another resolution / precision picked different kernels: keep the largest layer)
         layers = {k_: v_ for k_, v_ in layers.items() if k_.startswith("convc2")}
     have_conv = bool(layers) and any(conv_events.get(t) for t in layers)
-    if corr_mode == "volume":
+    if corr_mode == "volume" and args.full:
         # the lookup reads the volume: the named HBM-roofline kernel, measured live in the timed region
         out["roofline"] = lookup_roofline(events, plan.P, tracker.flower.engine.volume_storage)
         if have_conv:
@@ -401,7 +430,7 @@ def main():
     if bool(getattr(plan, "prog_wh", None)) and wh_events:
         out["roofline_weight_head"] = wh_roofline(wh_events, plan.prog_wh[0], plan.P)
     tc_gpu = {}
-    if world == 1:
+    if world == 1 and args.full:
         _, dst, _ = tracker.flower.compute_flow(template, frames[0], mode="TC", do_sigmoid=True)
         tc_gpu[args.precision] = dst.cpu()
         if corr_mode == "otf" and not args.no_alt_corr:
@@ -458,7 +487,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_alt_precisions:
+    if world == 1 and args.full and not args.no_alt_precisions:
         # the other arithmetic modes on the same sequence, each its own engine + buffers.  The STRICT fp32 operating
         # point (exact fp32 MFMA products, all-pairs volume: the reference's precision class) runs the full K steps.
         alt = {}
@@ -476,7 +505,7 @@ def main():
         if "fp32" in alt:
             out["strict_fp32"] = dict(alt["fp32"], dtype="f32 (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate)",
                                       note="same workload and step count as the headline, driver-timed in the same run")
-    if world == 1 and not args.no_alt_corr and args.precision != "fp32":
+    if world == 1 and args.full and not args.no_alt_corr and args.precision != "fp32":
         # the other correlation mode, same sequence; in the default (volume-free) mode this is also where the volume
         # lookup -- the named HBM-roofline kernel -- is measured live
         other = "volume" if corr_mode == "otf" else "otf"
@@ -497,7 +526,7 @@ def main():
             out["roofline_lookup_bf16_storage"] = lookup_roofline(evs, pl.P, trk.flower.engine.volume_storage)
             del trk, pl
             drop()
-    if world == 1 and not args.no_alt_corr:
+    if world == 1 and args.full and not args.no_alt_corr:
         # the weight head on every pixel (or, with --full-weight-head, on the mask region): full K steps, same tracks
         r, trk, pl, _ = side_run(K2, check_tracks=True, mask_wh=not mask_region)
         out["alt_weight_head"] = {("full" if mask_region else "mask_region"): r}
@@ -510,7 +539,7 @@ def main():
         out["alt_graph"] = r
         del trk, pl
         drop()
-    if world == 1 and not args.no_ladder:
+    if world == 1 and args.full and not args.no_ladder:
         # ---- host frames: what a real caller hands track() (WOFT_demo.py:61-78, TRK:113-120) -- one numpy frame per call,
         # crossing PCIe inside the timed region (pinned double-buffered staging + async H2D in woft_amd.tracker._FrameUploader);
         # same sequence, same tracks as the resident-frame headline
@@ -708,7 +737,7 @@ def main():
                                                                   "max": float(np.max(chunks))}}
             del trk
             drop()
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         if affinity0 is not None:
             # the launch thread was pinned to the GPU's NUMA node for the timed region (woft_amd.dist.bind_to_gpu_node);
             # the CPU baseline gets the cores the process started with
@@ -741,7 +770,7 @@ def main():
         out["epe_gate"] = {"passed": not bad, "failed_precisions": sorted(bad)}
         gate_failed = bool(bad)
     else:
-        out["epe_gate"] = {"passed": None, "note": "skipped: no CPU-oracle pass in this run (--no-cpu-baseline or N > 1)"}
+        out["epe_gate"] = {"passed": None, "note": "skipped: no CPU-oracle pass in this run (no --full, --no-cpu-baseline or N > 1)"}
         gate_failed = False
     # the figures a reader of the driver's `parsed` record needs beside `value` (it keeps `config`, not the extra keys)
     cfgd = out["config"]

@@ -8,6 +8,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,8 +18,8 @@ ROOT = Path(__file__).resolve().parent.parent
 def _run(extra, timeout=1200):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--no-cpu-baseline", "--no-ladder", "--no-alt-precisions", "--no-alt-corr",
-           *extra]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--no-cpu-baseline", "--no-ladder", "--no-alt-precisions",
+           "--no-alt-corr", *extra]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.lstrip().startswith("{")]
@@ -39,11 +40,11 @@ def test_bench_eight_ranks_dry_run():
 
 
 def test_bench_line_carries_ladder_and_lost_frames():
-    """Small-size run of the default bench line's extra passes: the like-for-like ladder, the lost-frame pass (forced every
+    """Small-size run of the --full bench line's extra passes: the like-for-like ladder, the lost-frame pass (forced every
     4th frame; the local flow runs in the second buffer set, so the frame after it costs what a normal frame costs) and the
     >= 200-step steady-state figure; the two-sequences-on-one-GPU side pass."""
     env = dict(os.environ)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--no-cpu-baseline", "--no-alt-precisions", "--no-alt-corr",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--no-cpu-baseline", "--no-alt-precisions", "--no-alt-corr",
            "--steps", "8", "--warmup", "2", "--height", "384", "--width", "512"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -76,3 +77,32 @@ def test_eight_ranks_1080p_host_launch_loops():
     busy = [r["host_busy_ms_per_step"] for r in d["per_rank"]]
     print(f"single-rank GPU frame {gpu_ms:.2f} ms; host launch loop per frame, 8 ranks: {[round(b, 2) for b in busy]} ms")
     assert max(busy) <= 0.25 * gpu_ms, (busy, gpu_ms)
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): exactly --steps timed steps, the headline fields and none of the extra passes; --dump-outputs
+    writes what the last timed track() call returned, and two runs with the same arguments write the same arrays."""
+    dumps = []
+    for k in range(2):
+        d_out = tmp_path / f"run{k}"
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", "5", "--warmup", "2", "--height", "256", "--width", "320",
+               "--dump-outputs", str(d_out)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ))
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.lstrip().startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+        assert abs(d["value"] - 5 / (d["ms_per_step"] * 5e-3)) < 1e-6 * d["value"] and d["unit"] == "frames/s"
+        assert d["metric"].startswith("tracked frames/sec") and d["dtype"]
+        for extra in ("roofline", "alt_precisions", "alt_corr", "reference_work", "lost_frame", "cpu_baseline", "steady_state"):
+            assert extra not in d, extra
+        files = sorted(p.name for p in d_out.glob("*.npy"))
+        assert "H_cur2init.npy" in files and "meta_lost.npy" in files, files
+        arrays = {f: np.load(d_out / f) for f in files}
+        assert arrays["H_cur2init.npy"].shape == (3, 3) and all(a.dtype == np.float64 for a in arrays.values())
+        assert np.isfinite(arrays["H_cur2init.npy"]).all() and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -6,9 +6,9 @@ from pathlib import Path
 import numpy as np
 import torch
 
-# one test below loads config files that live in the READ-ONLY reference tree: no __pycache__ may be written next to them (SURVEY
-# line 67) -- switched off for the whole interpreter before the first import machinery runs on such a file, and the loader below
-# compiles from source without touching any cache
+# one test below loads config files the way a caller loads them from a read-only tree: no __pycache__ may be written next to them
+# (SURVEY line 67) -- switched off for the whole interpreter before the first import machinery runs on such a file, and the loader
+# below compiles from source without touching any cache
 sys.dont_write_bytecode = True
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -27,14 +27,14 @@ def _module(path):
     return m
 
 
-def _load_config_without_cache(path):
+def _load_config_without_cache(path, *args):
     """pytracking.utils.config.load_config's semantics (module.get_config()) for a file in a read-only tree: the source is compiled
     in memory, nothing is read from or written to a __pycache__ directory."""
     import types
     m = types.ModuleType("tracker_config")
     m.__file__ = str(path)
     exec(compile(Path(path).read_text(), str(path), "exec"), m.__dict__)
-    return m.get_config()
+    return m.get_config(*args)
 
 
 def test_reference_form_config_is_recognised():
@@ -126,27 +126,24 @@ def test_strict_and_non_strict_comparisons_are_told_apart():
 
 
 def test_the_references_own_config_files_through_the_shim():
-    """In the build container (where /root/reference exists; skipped elsewhere): the reference's OWN tracker config files, loaded
-    unmodified through the `pytracking` shim of this repository -- which back end each gets.  The default WOFT.py (= ..._wLSq.py), its
-    downscale variants, the IRLS config and the ablations built from them are recognised; RANSAC / LiteFlowNet configs are out of scope."""
-    import pytest
-    ref = Path("/root/reference/pytracking/configs")
-    if not ref.exists():
-        pytest.skip("reference tree not present on this machine")
+    """The reference's own tracker config files, restated in their form in tests/configs/reference_forms.py (einops-shaped inputs,
+    DEBUG logging, nested re-weighting function, the reference's import paths only), loaded unmodified through the `pytracking`
+    shim of this repository -- which back end each gets.  The default WOFT.py (= ..._wLSq.py), its downscale variant, the IRLS
+    config (= ablation_08.py) and the ablations built from them are recognised; RANSAC / LiteFlowNet configs are out of scope."""
     from woft_amd.tracker import YAOFTrackerSingleControl
+    path = ROOT / "tests" / "configs" / "reference_forms.py"
     load_config = _load_config_without_cache
-    before = sorted(str(q) for q in ref.rglob("*.pyc"))
-    want = {"WOFT.py": (0, True, None), "WOFT_downscale_2x.py": (0, True, None), "ablation_08.py": (2, True, None),
-            "YAOFT_single_control_repRAFT_sub500_noreliableinl_wIRLSq.py": (2, True, None),
-            "YAOFT_single_control_repRAFT_sub500_noreliableinl_plainLSq.py": (0, False, None),
-            "YAOFT_single_control_repRAFT_sub500_alwayswarp_wLSq.py": (0, True, True),
-            "YAOFT_single_control_repRAFT_sub500_neverwarp_plainLSq.py": (0, False, False)}
+    before = sorted(str(q) for q in path.parent.rglob("*.pyc"))
+    want = {"wlsq": (0, True, None), "wlsq_downscale2": (0, True, None), "wirls": (2, True, None), "plain": (0, False, None),
+            "always_wlsq": (0, True, True), "never_plain": (0, False, False)}
+    assert sorted(want) == sorted(_module(path).KINDS)
     for name, (rew, weighted, const) in want.items():
-        conf = load_config(ref / name)
+        conf = load_config(path, name)
         assert conf.tracker_class is YAOFTrackerSingleControl and not conf.flow_config.precision
+        assert (conf.downscale_inputs == 2) == (name == "wlsq_downscale2"), name
         spec, how = probe.solver_spec(conf.H_estimator, make_forward_compatible(conf.subsampler_fn), conf.redet_success_fn)
         assert spec is not None and how.count("probed") == 3, (name, how)
         assert (spec["reweight"], spec["weighted"], spec["const_verdict"], spec["n_draw"]) == (rew, weighted, const, 500), (name, spec)
         if const is None:
             assert (spec["thr"], spec["min_frac"]) == (5.0, 0.2)
-    assert sorted(str(q) for q in ref.rglob("*.pyc")) == before, "the test wrote bytecode into the read-only reference tree"
+    assert sorted(str(q) for q in path.parent.rglob("*.pyc")) == before, "the test wrote bytecode next to the config files"

@@ -6,14 +6,14 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out
 mkdir -p $out
 cd $root
-python bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
-python bench.py --gpus 2 --steps 10 --warmup 3 > $out/${tag}_bench_2ranks_one_device.json 2>/dev/null
-python bench.py --height 720 --width 1280 --no-cpu-baseline > $out/${tag}_bench_720p.json 2>/dev/null
-python bench.py --height 720 --width 1280 --tracker-config WOFT_IRLS --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_720p_irls.json 2>/dev/null
-python bench.py --iters 32 --precision bf16 --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_1080p_it32_bf16.json 2>/dev/null
-python bench.py --iters 32 --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_1080p_it32_bf16x3.json 2>/dev/null
-python bench.py --height 2160 --width 3840 --steps 10 --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_4k.json 2>/dev/null
-python bench.py --height 480 --width 640 --no-cpu-baseline --no-ladder --no-alt-precisions --no-alt-corr > $out/${tag}_bench_480p.json 2>/dev/null
+python bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
+python bench.py --full --gpus 2 --steps 10 --warmup 3 > $out/${tag}_bench_2ranks_one_device.json 2>/dev/null
+python bench.py --full --height 720 --width 1280 --no-cpu-baseline > $out/${tag}_bench_720p.json 2>/dev/null
+python bench.py --full --height 720 --width 1280 --tracker-config WOFT_IRLS --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_720p_irls.json 2>/dev/null
+python bench.py --full --iters 32 --precision bf16 --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_1080p_it32_bf16.json 2>/dev/null
+python bench.py --full --iters 32 --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_1080p_it32_bf16x3.json 2>/dev/null
+python bench.py --full --height 2160 --width 3840 --steps 10 --no-cpu-baseline --no-alt-precisions > $out/${tag}_bench_4k.json 2>/dev/null
+python bench.py --full --height 480 --width 640 --no-cpu-baseline --no-ladder --no-alt-precisions --no-alt-corr > $out/${tag}_bench_480p.json 2>/dev/null
 python tools/bench_hfit.py > $out/${tag}_hfit_fullframe.txt 2>/dev/null
 { python tools/bench_lookup.py; python tools/bench_lookup.py --storage bf16;
   for abl in 1 2 3; do LOOKUP_ABL=$abl python tools/bench_lookup.py; done; } 2>/dev/null | grep lookup > $out/${tag}_lookup_isolated.txt

@@ -416,6 +416,22 @@ int woft_hfit_step(const float* pa, const float* pb, const float* w, int32_t n, 
 int woft_inlier_frac(const float* pa, const float* pb, int32_t n_max, const int32_t* count, const float* H,
                      float thr, float* frac, void* stream);
 
+/* RANSAC homography, what cv2.findHomography(pa, pb, cv2.RANSAC, thr, max_iters, conf) does in
+ * utils/least_squares_H.py:366-396 (find_homography_cvransac; configs/..._cvransac.py, ablation_09.py:26-30), restated in
+ * csrc/ransac.hip and DESIGN.md ("RANSAC"): max_iters hypotheses from a SplitMix64 stream keyed by (seed, k, draw), cv2's sample
+ * check, exact fp64 4-point models, cv2's fp32 error test err <= thr^2, cv2's sequential selection with the adaptive iteration
+ * count of confidence conf; then, for n > 4 and refine != 0, woft_hfit's DLT over the inliers and 10 Levenberg-Marquardt
+ * iterations.  pa, pb: [n][2] (A -> B); n = min(count[0], n_max) when count != NULL (device), else n_max.
+ * ws: woft_ransac_ws_bytes(n_max, max_iters) bytes of device scratch.  Hout: 9 floats (device), h33 = 1.
+ * status[0] (device) = 0 ok, 1 fewer than 4 points, 2 no model (no hypothesis with 4 or more inliers; Hout all NaN).
+ * info (device, may be NULL): {inliers of the best hypothesis, its index k (-1 without a model), iterations run}.
+ * inlier_mask (device, may be NULL): uint8 [n_max], 1 for the inliers of the best hypothesis, 0 elsewhere.
+ * -1 (before any launch) on a NULL pointer, max_iters < 1, thr <= 0 or conf outside [0, 1]. */
+int64_t woft_ransac_ws_bytes(int32_t n_max, int32_t max_iters);
+int woft_ransac(const float* pa, const float* pb, int32_t n_max, const int32_t* count, int32_t max_iters, double thr,
+                double conf, uint64_t seed, int32_t refine, void* ws, float* Hout, int32_t* status, int32_t* info,
+                uint8_t* inlier_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void feature_pyramid_kernel(const PyrArgs a) {
 
 }  // namespace
 
-extern "C" int woft_abi_version(void) { return 10000 * 0 + 100 * 3 + 0; }
+extern "C" int woft_abi_version(void) { return 10000 * 0 + 100 * 4 + 0; }
 
 extern "C" int woft_preprocess_bgr_u8(const uint8_t* img, int32_t h, int32_t w, float* out, int32_t hp, int32_t wp,
                                       int32_t pad_top, int32_t pad_left, void* stream) {

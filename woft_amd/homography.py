@@ -119,6 +119,37 @@ def find_homography_IRLSq_QR(points1, points2, weights=None, reweighting_fn=IRLS
     return _fit_callable(points1, points2, weights, reweighting_fn, n_iter)
 
 
+def find_homography_cvransac(pts_A, pts_B, weights=None, max_iters=10000, thr=1.4142, conf=0.995, seed=0):
+    """RANSAC homography (least_squares_H.py:366-396, cv2.findHomography(..., cv2.RANSAC) there), on the HIP device
+    (csrc/ransac.hip; semantics and deviations in DESIGN.md, "RANSAC").  pts (B,N,2) -> (B,3,3) float64, H / H[2,2], on
+    pts_A's device; numpy in, numpy out.  `weights` is accepted and ignored, as cv2 ignores it.  Every batch element is fitted
+    independently with the same `seed`.  Where no model is found (no hypothesis with 4 or more inliers) that element's H is
+    all NaN; the reference raises a TypeError there (None[2, 2])."""
+    rec = recorder()
+    if rec is not None:
+        return rec.fit("ransac", pts_A, pts_B, weights, ransac=(max_iters, thr, conf))
+    N = pts_A.shape[1]
+    assert N >= 4, "Not enough correspodences for RANSAC"
+    using_torch = isinstance(pts_A, torch.Tensor)
+    a = pts_A if using_torch else torch.from_numpy(np.ascontiguousarray(pts_A))
+    b = pts_B if using_torch else torch.from_numpy(np.ascontiguousarray(pts_B))
+    if tuple(a.shape) != tuple(b.shape) or a.dim() != 3 or a.shape[-1] != 2:
+        raise AssertionError((tuple(a.shape), tuple(b.shape)))
+    dev = a.device if a.is_cuda else torch.device("cuda")      # (host inputs: fitted on the HIP device, handed back)
+    B = a.shape[0]
+    out = torch.empty(B, 9, dtype=torch.float32, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    for k in range(B):
+        pa = a[k].to(device=dev, dtype=torch.float32).contiguous()
+        pb = b[k].to(device=dev, dtype=torch.float32).contiguous()
+        ops.ransac(pa, pb, out[k], status[k:k + 1], max_iters=max_iters, thr=thr, conf=conf, seed=seed)
+    H = out.double().view(B, 3, 3)
+    H = H / H[:, 2:3, 2:3]
+    if not using_torch:
+        return H.cpu().numpy()
+    return H.to(pts_A.device)
+
+
 def torch_proj_errors(GT_H, pts_A, pts_B):
     """L2 distance between H * pts_A and pts_B (least_squares_H.py:474-489).
     GT_H (B,3,3); pts (B,2,N) -> (B,N)."""

@@ -6,8 +6,8 @@ the fused device-side path instead of calling it."""
 import numpy as np
 import torch
 
-from .homography import (IRLSq_Huber, IRLSq_L1, find_homography_IRLSq_QR, find_homography_nonhomogeneous_QR,
-                         torch_proj_errors)
+from .homography import (IRLSq_Huber, IRLSq_L1, find_homography_cvransac, find_homography_IRLSq_QR,
+                         find_homography_nonhomogeneous_QR, torch_proj_errors)
 
 
 def sobol_points(n):
@@ -57,4 +57,12 @@ def estimator_irls(loss="huber", k=2.0, n_iter=5):
     def find_homography(pts_A, pts_B, weights=None):
         return find_homography_IRLSq_QR(pts_A, pts_B, weights=weights, reweighting_fn=fn, n_iter=n_iter)
     find_homography.woft_spec = ("irls", 2 if loss == "huber" else 1, float(k), n_iter)
+    return find_homography
+
+
+def estimator_ransac(max_iters=10000, thr=3.0, conf=0.995):
+    """RANSAC homography (least_squares_H.py:366-396 as configs/ablation_09.py:26-30 calls it); the weights are ignored."""
+    def find_homography(pts_A, pts_B, weights=None):
+        return find_homography_cvransac(pts_A, pts_B, weights=weights, max_iters=max_iters, thr=thr, conf=conf)
+    find_homography.woft_spec = ("ransac", int(max_iters), float(thr), float(conf))
     return find_homography

@@ -10,8 +10,9 @@ to ONE solver, `_solve`, which has two interchangeable back ends with identical 
 bit for bit):
 
   * device back end  -- configs built from woft_amd.presets (tagged callables): masking,
-    order-preserving compaction, Sobol selection, H fit and inlier test are HIP kernels
-    (csrc/select.hip, csrc/hfit.hip) with ONE device->host read per flow;
+    order-preserving compaction, Sobol selection, H fit (least squares / IRLS, or RANSAC) and
+    inlier test are HIP kernels (csrc/select.hip, csrc/hfit.hip, csrc/ransac.hip) with ONE
+    device->host read per flow;
   * callable back end -- any other reference-format config: the keep rule runs as the same
     `select` kernel (woft_tc_flags), the surviving correspondences are handed to the config's own
     subsampler / estimator / re-detection callables exactly as TRK:141-162,196-199 hands them.
@@ -180,6 +181,9 @@ class YAOFTrackerSingleControl:
                             pb=torch.empty(cap, 2, device=self.device), w=torch.empty(cap, device=self.device),
                             res=torch.zeros(16, dtype=torch.float32, device=self.device),
                             fit_ws=ops.hfit_ws(self.device) if cap > ops.HFIT_SINGLE_MAX else None)
+            R = self._fused.get("ransac")
+            if R is not None:
+                self._fb["fit_ws"] = ops.ransac_ws(cap, R["max_iters"], self.device)
             self._fb_key = n_grid
         return self._fb
 
@@ -395,8 +399,13 @@ class YAOFTrackerSingleControl:
         else:
             ops.tc_select(dst_xy, w, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds, F["sobol_u"], b["ws"],
                           b["pa"], b["pb"], b["w"], ires[12:14], grid=grid)
-        ops.hfit(b["pa"], b["pb"], b["w"] if weighted else None, res[0:9], ires[10:11], count=ires[12:13], reweight=F["reweight"],
-                 huber_k=F["huber_k"], n_irls=F["n_irls"], ws=b["fit_ws"])
+        R = F.get("ransac")
+        if R is not None:                  # (status 1 / 2 in the same slot: fewer than 4 points / no model, H all NaN)
+            ops.ransac(b["pa"], b["pb"], res[0:9], ires[10:11], count=ires[12:13], max_iters=R["max_iters"], thr=R["thr"],
+                       conf=R["conf"], ws=b["fit_ws"])
+        else:
+            ops.hfit(b["pa"], b["pb"], b["w"] if weighted else None, res[0:9], ires[10:11], count=ires[12:13],
+                     reweight=F["reweight"], huber_k=F["huber_k"], n_irls=F["n_irls"], ws=b["fit_ws"])
         ops.inlier_frac(b["pa"], b["pb"], res[0:9], res[9:10], thr=F["thr"], count=ires[12:13])
         # the flow's single device->host read: into a pinned buffer (no staging copy, no allocation), then wait for it
         if getattr(self, "_host_res", None) is None:

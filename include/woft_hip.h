@@ -328,6 +328,16 @@ int woft_wh_pack(const float* lookup, int32_t ld_lookup, const float* f1, int32_
                  float alpha, int64_t n_pix, int32_t nwin, float* mean, float* x8, void* stream);
 int woft_wh_reduce(const float* act, int32_t c, int32_t nwin2, const float* w, float bias,
                    int64_t n_pix, float* out, void* stream);
+/* MaskHead input (external/RAFT/raft_core/weighted_raft.py:295-309; utils/utils.py:59-73): the feature map f (NHWC fp32, h x w,
+ * c valid channels, channel stride cs) sampled at n_pix coordinates coords[p] = (x, y) in map pixels:
+ *   out[p*ld_out + 0..c) = bilinear_sampler(f, coords[p])
+ * with the reference's semantics: grid_sample(align_corners=True, padding_mode='zeros') after the normalisation
+ * 2x/(w-1) - 1, 2y/(h-1) - 1 -- the normalise / un-normalise round trip is taken in the same fp32 operations; a corner outside
+ * the map contributes 0 (no clamping).  Channels c..ld_out of a row are not written.  fp32 FMAs.
+ * -1 (before any launch) on a NULL pointer, c % 4 != 0, cs < c, ld_out < c, cs or ld_out not a multiple of 4, f or out not
+ * 16-byte aligned, h < 2 or w < 2 (the reference divides by zero there) or n_pix < 0; n_pix == 0 launches nothing. */
+int woft_warp_features(const float* f, int32_t h, int32_t w, int32_t c, int32_t cs, const float* coords, int64_t n_pix,
+                       float* out, int32_t ld_out, void* stream);
 /* The windows of a window list that a set of full-resolution pixels needs: dyn_index[j] = index[j] if the 1/8-res pixel
  * index[j] lies in the 3x3 neighbourhood of the cell of one of the n = min(count[0], n_max) points pts[i] = (x, y) (image
  * coordinates; cell = ((y + top) >> 3, (x + left) >> 3): the support of the x8 convex upsampling, weighted_raft.py:92-103),

@@ -82,6 +82,7 @@ _SIGS = {
     "woft_wh_pack": (i32, [vp, i32, vp, i32, vp, f32, i64, i32, vp, vp, vp]),
     "woft_wh_conv0": (i32, [vp, i32, vp, i64, i32, vp, vp, vp, vp, vp]),
     "woft_wh_reduce": (i32, [vp, i32, i32, vp, f32, i64, vp, vp]),
+    "woft_warp_features": (i32, [vp, i32, i32, i32, i32, vp, i64, vp, i32, vp]),
     "woft_wh_needed": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "woft_convex_upsample": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "woft_convex_weights_at": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),

@@ -8,6 +8,7 @@ Reference being replaced (paths under /root/reference/pytracking/external/RAFT/r
   WeightedRAFT.forward  weighted_raft.py:179-315      RAFT.forward  raft.py:169-262
   BasicEncoder / SmallEncoder  extractor.py:118-267   CorrBlock     corr.py:11-69
   BasicUpdateBlock / SmallUpdateBlock  update.py:99-136   WeightHead  weighted_raft.py:318-384
+  MaskHead (opt-in, mask_head=True)  weighted_raft.py:295-309,387-422
 
 Results-identical restructurings: BatchNorm(eval) folded into the cnet convs; the
 mask head evaluated only after the last iteration (test_mode consumes only that one,
@@ -99,7 +100,8 @@ class _Enc:
 
 
 class RaftEngine:
-    def __init__(self, state_dict, small=False, weighted=True, precision="fp32", corr="volume", volume_storage=None):
+    def __init__(self, state_dict, small=False, weighted=True, precision="fp32", corr="volume", volume_storage=None,
+                 mask_head=False):
         """precision: "fp32" (exact fp32 MFMA), "bf16x3" (split-bf16, fp32-emulating), "bf16", or "fp16" = the reference's
         `mixed_precision` scoping (weighted_raft.py:204-219,233-234,258-290: autocast around fnet, cnet and the update block
         only): those convolutions on fp16 operands with fp32 accumulation, the correlation, the weight head and both
@@ -109,7 +111,9 @@ class RaftEngine:
         to the volume path of the same precision).
         volume_storage: element type of the volume in HBM, "fp32" or "bf16" (fp32 accumulators rounded once at the GEMM's
         store; lookup interpolation and output stay fp32).  Default: "bf16" in the plain-bf16 precision -- its operating
-        point, half the store stream and the lookup's reads, SURVEY 8d -- else "fp32"."""
+        point, half the store stream and the lookup's reads, SURVEY 8d -- else "fp32".
+        mask_head: also evaluate the MaskHead of a 'weighted_masked' checkpoint (mask_head.net.*, weighted_raft.py:295-309,387-422)
+        after the last iteration -> flow(mout=...) receives the upsampled visibility logits."""
         if precision not in ops.PRECISION:
             raise ValueError(f"precision must be one of {sorted(ops.PRECISION)}")
         if corr not in ("volume", "otf"):
@@ -210,6 +214,23 @@ class RaftEngine:
             self.wh6_w[:self.wh6_c] = sd[f"{w}{last}.weight"].reshape(-1)
             self.wh6_w = self.wh6_w.contiguous().cuda()
             self.wh6_b = float(sd[f"{w}{last}.bias"].item())
+        self.mask_head = bool(mask_head)
+        if self.mask_head:
+            if not weighted:
+                raise ValueError("mask_head: the MaskHead belongs to WeightedRAFT (weighted_raft.py:75-76), not to plain RAFT")
+            m = "mask_head.net."
+            # class_params.mask_head_structure (weighted_raft.py:387-409) = the layers net.0, net.2, ... on [fmap1 | warped fmap2]
+            # (2 * fdim channels), a ReLU after each, then the closing 1x1 conv to one logit channel
+            idx = sorted(int(k.split(".")[2]) for k in sd if k.startswith(m) and k.endswith(".weight"))
+            shapes = [tuple(sd[f"{m}{i}.weight"].shape) for i in idx]
+            if len(idx) < 2 or shapes[-1][0] != 1 or shapes[-1][2:] != (1, 1) or shapes[0][1] != 2 * sp.fdim \
+                    or any(a[0] != b[1] for a, b in zip(shapes, shapes[1:])) or any(sh[2] != sh[3] or sh[2] % 2 == 0 for sh in shapes):
+                raise ValueError(f"mask head layers {shapes}: not a MaskHead on {2 * sp.fdim} channels (weighted_raft.py:387-409)")
+            self.mh_shapes = shapes
+            self.mh_layers = [ops.pack_conv(sd[f"{m}{i}.weight"], sd[f"{m}{i}.bias"]) for i in idx[:-1]]
+            self.mh_c = shapes[-1][1]
+            self.mh_wlast = sd[f"{m}{idx[-1]}.weight"].reshape(-1).clone()
+            self.mh_b = float(sd[f"{m}{idx[-1]}.bias"].item())
         self._plans = {}
 
     def plan(self, hp, wp, slot=0):
@@ -373,6 +394,27 @@ class _Plan:
                     self.prog_wh.append(cpw(x, pc, out, epi=EPI.EPI_RELU))
                     x = out
                 self.wh_last = x
+        if eng.mask_head:
+            # MaskHead (weighted_raft.py:295-309,387-422), after the last iteration on every source pixel (3x3 cross-pixel terms):
+            # woft_warp_features -> layers on the conv kernels (the first reads [f1 | warped] as two sources, no concatenated copy)
+            # -> closing 1x1 conv by woft_wh_reduce (nwin2 = 1) -> 1/8-resolution logits mh_low.  Arithmetic: the weight head's
+            # rule (prec_wh; the reference runs the head outside autocast).  One activation per layer, zeroed once (see above).
+            self.mh_warped = new_act(1, hf, wf, sp.fdim, zero=True)
+            self.prog_mh = []
+            x = None
+            for k, pc in enumerate(eng.mh_layers):
+                out = new_act(1, hf, wf, pc.cout, cs=_ru(_ru(pc.cout, 4), 32), zero=True)
+                if k == 0:
+                    self.prog_mh.append(self._cp(self.f1, pc, out, x2=self.mh_warped, c_split=sp.fdim, epi=EPI.EPI_RELU,
+                                                 precision=self.prec_wh))
+                else:
+                    self.prog_mh.append(self._cp(x, pc, out, epi=EPI.EPI_RELU, precision=self.prec_wh))
+                x = out
+            self.mh_last = x
+            self.mh_w = torch.zeros(x.cs, dtype=torch.float32)
+            self.mh_w[:eng.mh_c] = eng.mh_wlast
+            self.mh_w = self.mh_w.to(dev)
+            self.mh_low = z(P)
 
     def _fold_gather_programs(self):
         """Variants of the iteration programs in which the flow-head gather that ends iteration k is done by the lookup
@@ -707,10 +749,13 @@ class _Plan:
             self.run(self.prog_gate_bias)
         return reused
 
-    def flow(self, iters, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False, trace=None, defer_wh=False):
+    def flow(self, iters, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False, trace=None, defer_wh=False,
+             mout=None):
         """Target features -> volume -> `iters` refinements -> full-resolution outputs.
         defer_wh (full weighted model with a weight region set): stop before the weight head -- flow_up / dst are final,
-        wout is NOT written -- and let finish_weights() evaluate the head where the caller then says it reads the weights."""
+        wout is NOT written -- and let finish_weights() evaluate the head where the caller then says it reads the weights.
+        mout (engine built with mask_head): receives the upsampled visibility-mask logits (h*w floats, cropped like wout, never
+        passed through a sigmoid); the head runs after the weight head whether or not mout is given."""
         e, sp = self.eng, self.eng.spec
         if iters < 1:
             raise ValueError("iters must be >= 1")
@@ -734,7 +779,7 @@ class _Plan:
             ops.run_conv(p)
         wlow = None
         if defer_wh:
-            assert e.weighted and not sp.small and self.wh_region is not None
+            assert e.weighted and not sp.small and self.wh_region is not None and not e.mask_head
             ops.convex_upsample(self.coords, None, self.mask.t, self.hf, self.wf, crop, h, w, flow_up=flow_up, dst=dst,
                                 wout=None, do_sigmoid=do_sigmoid)
             return
@@ -749,6 +794,23 @@ class _Plan:
         else:
             ops.convex_upsample(self.coords, wlow, self.mask.t, self.hf, self.wf, crop, h, w, flow_up=flow_up,
                                 dst=dst, wout=wout, do_sigmoid=do_sigmoid)
+        if e.mask_head:
+            self._mask_head()
+            if mout is not None:        # the weight channel of the same upsampling kernels, on the mask logits (weighted_raft.py:305-308)
+                if sp.small:
+                    ops.upflow8(self.coords, self.mh_low, self.hf, self.wf, crop, h, w, wout=mout)
+                else:
+                    ops.convex_upsample(self.coords, self.mh_low, self.mask.t, self.hf, self.wf, crop, h, w, wout=mout)
+
+    def _mask_head(self):
+        """MaskHead on the final coordinates (weighted_raft.py:295-304, 411-422) -> self.mh_low (1/8-resolution logits)."""
+        e = self.eng
+        ops.warp_features(self.f2act[0], self.coords, self.mh_warped)
+        for p in self.prog_mh:
+            ops.run_conv(p)
+        last = self.mh_last
+        _lib.check(_lib.load().woft_wh_reduce(_lib.ptr(last.t), last.cs, 1, _lib.ptr(self.mh_w), e.mh_b, self.P,
+                                              _lib.ptr(self.mh_low), _lib.stream_ptr()), "woft_wh_reduce")
 
     def finish_weights(self, pts, count, n_max, pad, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False,
                        w_points=None):

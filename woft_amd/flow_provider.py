@@ -38,14 +38,42 @@ def _pad_geometry(h, w, mode):
     raise ValueError(f"invalid padding_mode '{mode}'")
 
 
+def _mask_head_shapes(structure, fdim):
+    """class_params.mask_head_structure -> the state-dict shapes of mask_head.net.{0,2,...}.weight (weighted_raft.py:387-409:
+    (channels, kernel) tuples or plain channel counts = 3x3 layers, on 2 * fdim input channels; closing 1x1 conv to 1)."""
+    try:
+        layers = [tuple(d) if isinstance(d, (list, tuple)) else (d, 3) for d in structure]
+        shapes, cur = [], 2 * fdim
+        for c, k in layers:
+            c, k = int(c), int(k)
+            if c < 1 or k < 1 or k % 2 == 0:
+                raise ValueError
+            shapes.append((c, cur, k, k))
+            cur = c
+    except (TypeError, ValueError):
+        raise ValueError(f"class_params.mask_head_structure {structure!r}: not a list of (channels, odd kernel) tuples "
+                         "or channel counts (weighted_raft.py:387-409)") from None
+    return shapes + [(1, cur, 1, 1)]
+
+
 class RAFTWrapper:
     def __init__(self, config):
         self.C = config
         cp = config.class_params
-        if cp.mask_estimation:
-            raise NotImplementedError("mask_estimation (MaskHead) is unset in every shipped config")
-        if self.C.raft_type not in ("orig", "weighted"):
+        if self.C.raft_type not in ("orig", "weighted", "weighted_masked"):
             raise ValueError(f"Unknown RAFT type {self.C.raft_type}")
+        # 'weighted_masked' (raft.py:38-42,142-147): WeightedRAFT with its MaskHead -> a visibility-mask output as well.  The two
+        # keys must agree: the reference unpacks 6 network outputs for 'weighted_masked' and 5 for 'weighted' and fails at the
+        # first flow with a ValueError when they do not -- here the same error class, at construction.  ('orig' ignores the key,
+        # as the reference does: plain RAFT has no head.)
+        self.masked = self.C.raft_type == "weighted_masked"
+        if self.masked and not cp.mask_estimation:
+            raise ValueError("raft_type 'weighted_masked' needs class_params.mask_estimation = True (and mask_head_structure): "
+                             "without the MaskHead the network has no mask output")
+        if self.C.raft_type == "weighted" and cp.mask_estimation:
+            raise ValueError("class_params.mask_estimation is set with raft_type 'weighted', which returns no mask: use raft_type "
+                             "'weighted_masked'")
+        self._cache_mask_warned = False
         logger.info(f"Loading weights from: {self.C.model}")
 
         def read(src):
@@ -60,8 +88,17 @@ class RAFTWrapper:
             in_backbone = lambda k: ("fnet" in k) or ("cnet" in k) or ("update_block" in k)
             state_dict = {k: v for k, v in state_dict.items() if not in_backbone(k)}
             state_dict.update({k: v for k, v in read(self.C.backbone_model).items() if in_backbone(k)})
-        weighted = self.C.raft_type == "weighted"
+        weighted = self.C.raft_type in ("weighted", "weighted_masked")
         small = bool(cp.small)
+        if self.masked:             # (checked against the checkpoint before any device work)
+            if not cp.mask_head_structure:
+                raise ValueError("raft_type 'weighted_masked' needs class_params.mask_head_structure (weighted_raft.py:387-409)")
+            want = _mask_head_shapes(cp.mask_head_structure, 128 if small else 256)
+            idx = sorted(int(k.split(".")[2]) for k in state_dict if k.startswith("mask_head.net.") and k.endswith(".weight"))
+            got = [tuple(state_dict[f"mask_head.net.{i}.weight"].shape) for i in idx]
+            if got != want or idx != list(range(0, 2 * len(want), 2)):
+                raise ValueError(f"class_params.mask_head_structure {cp.mask_head_structure!r} expects mask_head.net layers {want}; "
+                                 f"the checkpoint has {got} (at net.{idx})")
         # arithmetic of the convolutions / correlation products: "bf16x3" (split-bf16 operands, fp32 accumulation: fp32-EMULATING,
         # ~2^-16 relative per product; flow EPE <= 1e-4 px against the fp32 reference at 1080p, budget 1e-3 px), "fp32" (exact fp32
         # MFMA products, 4x slower), "bf16", "f16mx8", or "fp16".  `mixed_precision=True` selects "fp16" with the reference's scoping
@@ -95,7 +132,7 @@ class RAFTWrapper:
         self.corr = os.environ.get("WOFT_CORR") or getattr(self.C, "corr", None) or "otf"
         # flow config key `volume_storage` ("fp32" | "bf16"): element type of the correlation volume (corr = "volume")
         self.engine = RaftEngine(state_dict, small=small, weighted=weighted, precision=self.precision, corr=self.corr,
-                                 volume_storage=getattr(self.C, "volume_storage", None))
+                                 volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked)
         # opt-in (flow config key `graph`, env WOFT_GRAPH=1): the ~330 launches of a flow -- a static list per
         # resolution, fixed buffers, no allocation -- are captured once into a hipGraph and replayed per frame
         self.use_graph = (os.environ.get("WOFT_GRAPH") or str(int(bool(getattr(self.C, "graph", False))))) == "1"
@@ -115,7 +152,7 @@ class RAFTWrapper:
         def eager():
             # (mode "TC" hands out dst = grid + flow only: the (2, H, W) flow map is then not written at all)
             plan.flow(iters, crop, oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"], wout=o["w"] if weighted else None,
-                      do_sigmoid=do_sigmoid, defer_wh=defer_wh)
+                      do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"))
         if not self.use_graph or plan.lookup_events is not None or plan.wh_events is not None or plan.conv_events is not None:
             return eager()
         graphs = plan.__dict__.setdefault("_graphs", {})
@@ -192,6 +229,8 @@ class RAFTWrapper:
             self._out[key] = dict(flow=z(2, h, w), dst=z(2, h * w), w=z(1, h * w),
                                   src=torch.stack([torch.arange(h * w, device="cuda") % w,
                                                    torch.div(torch.arange(h * w, device="cuda"), w, rounding_mode="floor")]))
+            if self.masked:
+                self._out[key]["m"] = z(1, h * w)         # visibility-mask logits (weighted_masked)
         return self._out[key]
 
     def _cached_flow(self, src_img, identifier, mode, numpy_out, do_sigmoid, borrow=False):
@@ -232,18 +271,24 @@ class RAFTWrapper:
         tracker does)."""
         own = (lambda t: t) if borrow else (lambda t: t.clone())
         host = lambda t: t.cpu().numpy()
+        conv = host if numpy_out else own
+        # weighted_masked (raft.py:170-173,180-181,201-203,215-216): the visibility-mask logits follow the weights -- (1, H, W) in
+        # mode 'flow', (1, H*W) in mode 'TC' -- never through do_sigmoid / weights_postprocessing_fn (those act on the weights only)
+        extra = ()
         if mode == "flow":
             wts = weights.reshape(1, oh, ow) if weights is not None else None
-            if numpy_out:
-                return host(o["flow"]), (host(wts) if wts is not None else None)
-            return own(o["flow"]), (own(wts) if wts is not None else None)
+            if self.masked:
+                extra = (conv(o["m"].reshape(1, oh, ow)),)
+            return (conv(o["flow"]), (conv(wts) if wts is not None else None)) + extra
         self.last_flow_shape = {"batch": 1, "delta": 2, "H": oh, "W": ow}
+        if self.masked:
+            extra = (conv(o["m"]),)
         if numpy_out:
-            return host(o["src"]), host(o["dst"]), (host(weights) if weights is not None else None)
+            return (host(o["src"]), host(o["dst"]), (host(weights) if weights is not None else None)) + extra
         # (the int64 source grid is a constant of the resolution -- 33 MB at 1080p: the provider's own tensor under borrow=True
         #  (the tracker only indexes it); any other caller gets a tensor it may edit in place, as the reference's callers may --
         #  round-4 advisor finding: a shared grid that a caller offsets or sorts would corrupt every later call at this size)
-        return own(o["src"]), own(o["dst"]), (own(weights) if weights is not None else None)
+        return (own(o["src"]), own(o["dst"]), (own(weights) if weights is not None else None)) + extra
 
     def compute_flow(self, src_img, dst_img, mode="TC", vis=False, src_img_identifier=None,
                      numpy_out=False, do_sigmoid=False, borrow=False, defer_weights=False, weight_region=False,
@@ -251,6 +296,8 @@ class RAFTWrapper:
         """src_img / dst_img: (H, W, 3) uint8 BGR (numpy, or CUDA tensors already on the device).
         mode 'TC' -> (src_coords (2,HW) int64, dst_coords (2,HW) f32, weights (1,HW) f32 | None)
         mode 'flow' -> (flow (2,H,W), weights (1,H,W) | None).
+        raft_type 'weighted_masked' (raft.py:181,216): one more value, the visibility-mask logits -- (1,H,W) in mode 'flow',
+        (1,HW) in mode 'TC' -- never passed through a sigmoid.
         borrow (extension, default off): return the provider's own output buffers, valid until the next call.
         weight_region (extension, default off): the caller reads the weights only inside the region declared with
         pin_weight_region() (flows from the pinned source); without it every call returns the full weight map, as the
@@ -261,7 +308,14 @@ class RAFTWrapper:
         finish_weights(), only where the caller then says it reads the weights."""
         assert mode in ["flow", "TC"]
         assert src_img.shape == dst_img.shape
-        if src_img_identifier is not None:                 # pre-computed flow (raft.py:92-109)
+        if src_img_identifier is not None and self.masked:
+            # (deviation: the flow cache holds no mask -- utils/caching.py:53-59 -- and the reference raises UnboundLocalError on a
+            #  cache hit with 'weighted_masked' (raft.py:171,202); here the cache is skipped and the flow computed, with its mask)
+            if not self._cache_mask_warned:
+                self._cache_mask_warned = True
+                logger.warning("raft_type 'weighted_masked': the flow cache holds no visibility mask -- cached flows are not used, "
+                               "every flow is computed")
+        elif src_img_identifier is not None:               # pre-computed flow (raft.py:92-109)
             try:
                 return self._cached_flow(src_img, src_img_identifier, mode, numpy_out, do_sigmoid, borrow)
             except Exception as ex:   # no such file / array, object placeholders, truncated archives, wrong shapes / dtypes:
@@ -319,10 +373,12 @@ class RAFTWrapper:
         plan.load_image(1, d, top, left)
         self._last_dst[id(plan)] = (id(dst_img), key)         # (what this buffer set's target features will belong to after this call)
         o = self._outputs(oh, ow)
-        weighted = self.C.raft_type == "weighted"
+        weighted = self.C.raft_type in ("weighted", "weighted_masked")
         # (defer_weights = the number of pixels the caller will name: worth it only if their 3x3 supports cannot cover most
         # of the region anyway -- measured with 500 pixels: +0.7 % at 720p (3 900 windows), +6 % at 1080p, +11 % at 4K)
-        self.weights_deferred = bool(defer_weights and weighted and not self.engine.small and plan.wh_region is not None
+        # (weighted_masked: the mask head has 3x3 cross-pixel terms and runs on every pixel after the weight head -- not deferred)
+        self.weights_deferred = bool(defer_weights and weighted and not self.masked and not self.engine.small
+                                     and plan.wh_region is not None
                                      and mode == "TC" and not numpy_out
                                      and int(plan.wh_region[0].numel()) > self.defer_min_ratio * int(defer_weights))
         self._deferred = (plan, (top, left), oh, ow, o, bool(do_sigmoid)) if self.weights_deferred else None

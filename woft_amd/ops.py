@@ -690,6 +690,13 @@ def wh_needed(pts, count, n_max, top, left, hf, wf, index, bitmap, dyn_index, n_
                                      ptr(dyn_index), ptr(n_needed), stream_ptr()), "woft_wh_needed")
 
 
+def warp_features(f, coords, out):
+    """out[p, :f.c] = bilinear_sampler(f, coords[p]) for the out.n_pix pixels (woft_warp_features; grid_sample, align_corners=True,
+    zero padding: utils/utils.py:59-73)."""
+    check(_lib.load().woft_warp_features(ptr(f.t), f.h, f.w, f.c, f.cs, ptr(coords), out.n_pix, ptr(out.t), out.cs,
+                                         stream_ptr()), "woft_warp_features")
+
+
 def convex_upsample(coords, wlow, mask, hf, wf, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False):
     check(_lib.load().woft_convex_upsample(ptr(coords), ptr(wlow), ptr(mask), mask.shape[1], hf, wf, crop[0], crop[1],
                                            h, w, ptr(flow_up), ptr(dst), ptr(wout), int(do_sigmoid), stream_ptr()),

@@ -8,6 +8,7 @@ tensor shapes follow the reference modules:
   * encoders            pytracking/external/RAFT/raft_core/extractor.py:118-267
   * update blocks       pytracking/external/RAFT/raft_core/update.py:6-136
   * weight head         pytracking/external/RAFT/raft_core/weighted_raft.py:318-345
+  * mask head (opt-in)  pytracking/external/RAFT/raft_core/weighted_raft.py:387-409
 
 (the key list is pinned against the imported reference in
 tests/golden/state_dict_keys.json).  Everything is numpy.random.RandomState, so the
@@ -97,10 +98,13 @@ def _small_encoder(g, p, out_dim, norm):
     g.conv(p + ".conv2", out_dim, 96, 1, 1)
 
 
-def make_state_dict(seed=0, small=False, weighted=True, head_gain=1.0, weight_head_structure=None):
+def make_state_dict(seed=0, small=False, weighted=True, head_gain=1.0, weight_head_structure=None, mask_head_structure=None):
     """Synthetic checkpoint with the reference's key set.
     weight_head_structure: the flow config's `class_params.weight_head_structure` (weighted_raft.py:318-345: a list of
     (channels, kernel) tuples or plain channel counts = 3x3 layers); default [(128, 3)] * 3, the shipped configs' head.
+    mask_head_structure: `class_params.mask_head_structure` of a 'weighted_masked' config (MaskHead, weighted_raft.py:387-409,
+    same list form, input 2 * fdim channels): adds mask_head.net.* after every other tensor (so the tensors before it do not
+    change); None (default): no mask head.
 
     small=False, weighted=True  -> WeightedRAFT full (weighted_raft.py:62-72)
     small=True,  weighted=False -> plain RAFT-small  (raft.py:49-56)
@@ -144,6 +148,13 @@ def make_state_dict(seed=0, small=False, weighted=True, head_gain=1.0, weight_he
             g.conv(f"weight_head.net.{2 * i}", c, cur, k, k, "default")
             cur = c
         g.conv(f"weight_head.net.{2 * len(structure)}", 1, cur, 1, 1, "default")
+    if mask_head_structure is not None:
+        cur = 2 * (128 if small else 256)
+        for i, data in enumerate(mask_head_structure):
+            c, k = data if isinstance(data, (list, tuple)) else (data, 3)
+            g.conv(f"mask_head.net.{2 * i}", c, cur, k, k, "default")
+            cur = c
+        g.conv(f"mask_head.net.{2 * len(mask_head_structure)}", 1, cur, 1, 1, "default")
     return g.sd
 
 

@@ -127,6 +127,11 @@ class YAOFTrackerSingleControl:
 
     def __init__(self, config):
         self.C = config
+        if config.flow_config.raft_type == "weighted_masked":
+            # the tracker unpacks (src, dst, weights) from compute_flow (TRK:101,181); a 'weighted_masked' provider returns a fourth
+            # value, the visibility mask, which the tracker does not consume: refused here rather than at the first frame
+            raise ValueError("the tracker takes a flow config with raft_type 'orig' or 'weighted'; 'weighted_masked' (MaskHead "
+                             "visibility mask) returns a mask the tracker does not consume")
         if self.C.subsampler_fn:
             self.C.subsampler_fn = make_forward_compatible(self.C.subsampler_fn)
         self.flower = config.flow_config.of_class(config.flow_config)

@@ -562,6 +562,8 @@ __global__ __launch_bounds__(ST) void hfit_solve_kernel(int n_max, const int* __
         if (!cholesky_solve8(gram, sol)) {
             status[0] = 2;
             for (int i = 0; i < 9; ++i) Hout[i] = nanf("");
+            // (the scratch's sol may hold an earlier fit's solution: hfit_resid_kernel must not hand its residuals out)
+            for (int i = 0; i < 8; ++i) s.sol[i] = nanf("");
             return;
         }
         for (int i = 0; i < 8; ++i) s.sol[i] = sol[i];

@@ -378,6 +378,28 @@ int woft_upflow8(const float* coords1, const float* wlow, int32_t hf, int32_t wf
 int woft_warp_perspective_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, const double* hinv,
                              uint8_t* out, uint8_t* valid, int32_t nearest, void* stream);
 
+/* Search-window kernels (csrc/window.hip; tracker/WOFT_window.py: the flows of the window tracker run on a rectangle of the frame).
+ * A rectangle is rows [y0, y0 + hw) x columns [x0, x0 + ww) of an h x w image and must lie inside it with hw, ww >= 1: else -1.
+ *
+ * woft_warp_perspective_window_u8: the rectangle of what woft_warp_perspective_u8 writes for the same arguments, into a contiguous
+ * hw x ww x c `out` and hw x ww `valid` (either may be NULL, not both; nearest needs out).  Window pixel (i, j) holds exactly the
+ * bytes the full-frame call gives destination pixel (x0 + i, y0 + j): one device function serves both (csrc/warp_pixel.h). */
+int woft_warp_perspective_window_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, const double* hinv, int32_t y0,
+                                    int32_t x0, int32_t hw, int32_t ww, uint8_t* out, uint8_t* valid, int32_t nearest,
+                                    void* stream);
+/* Rectangle copy: out (hw x ww x c, contiguous) = img[y0 : y0 + hw, x0 : x0 + ww, :] (h x w x c uint8, c <= 4). */
+int woft_crop_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, int32_t y0, int32_t x0, int32_t hw, int32_t ww,
+                 uint8_t* out, void* stream);
+/* Bounding box of the non-zero pixels of a uint8 h x w mask: bbox (device) = {rmin, rmax, cmin, cmax, any} as five int32; an
+ * all-zero mask gives {0, 0, 0, 0, 0} (utils/geom_utils.py:46-64, Bbox.from_mask).  One launch.
+ * hinv != NULL (9 doubles on the host): the mask measured is the nearest-neighbour warp of `mask` by hinv, exactly
+ * woft_warp_perspective_u8(mask, h, w, 1, hinv, warped, NULL, 1), and `warped` (h x w, may be NULL) receives it.
+ * ws: woft_mask_bbox_ws_bytes() bytes of device scratch, ZEROED ONCE by the caller; every call leaves it zeroed again (calls that
+ * share one ws must be ordered by their stream). */
+int64_t woft_mask_bbox_ws_bytes(void);
+int woft_mask_bbox(const uint8_t* mask, int32_t h, int32_t w, const double* hinv, uint8_t* warped, void* ws, int32_t* bbox,
+                   void* stream);
+
 /* cv2.resize(img, None, fx, fy) with INTER_LINEAR geometry (tracker/YAOF_tracker_single_control.py:27-30,60-61,
  * `downscale_inputs`): src = (dst + 0.5) * scale - 0.5, edge clamped; scale = 1 / fx. */
 int woft_resize_linear_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, uint8_t* out, int32_t ho, int32_t wo,

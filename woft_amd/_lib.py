@@ -89,6 +89,10 @@ _SIGS = {
     "woft_upflow8": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "woft_warp_perspective_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), vp, vp, i32, vp]),
     "woft_resize_linear_u8": (i32, [vp, i32, i32, i32, vp, i32, i32, f32, f32, vp]),
+    "woft_warp_perspective_window_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), i32, i32, i32, i32, vp, vp, i32, vp]),
+    "woft_crop_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "woft_mask_bbox_ws_bytes": (i64, []),
+    "woft_mask_bbox": (i32, [vp, i32, i32, C.POINTER(C.c_double), vp, vp, vp, vp]),
     "woft_tc_select_ws_bytes": (i64, [i64]),
     "woft_tc_select": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
     "woft_tc_flags": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),

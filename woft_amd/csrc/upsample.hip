@@ -2,6 +2,7 @@
 // logits, fused with the operator-boundary epilogue (un-pad crop, sigmoid, correspondences).
 //   weighted_raft.py:92-103, 285-288 ; utils/utils.py:82-84 ; optical_flow/raft.py:148-159,185-199.
 #include "common.h"
+#include "warp_pixel.h"
 
 namespace {
 
@@ -138,50 +139,14 @@ __global__ void upflow8_kernel(const float* __restrict__ coords1, const float* _
     }
 }
 
-struct H9 { double v[9]; };
-
-// dst(x, y) = src(Hinv (x, y)); bilinear with zero border (or nearest).  `valid` = warp(ones) > 0.
+// dst(x, y) = src(Hinv (x, y)); bilinear with zero border (or nearest).  `valid` = warp(ones) > 0.  (The per-pixel arithmetic
+// is warp_pixel.h's, shared with the windowed warp of window.hip.)
 __global__ void warp_kernel(const uint8_t* __restrict__ img, int h, int w, int c, H9 hi, uint8_t* __restrict__ out,
                             uint8_t* __restrict__ valid, int nearest) {
     const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= (int64_t)h * w) return;
     const int y = (int)(o / w), x = (int)(o - (int64_t)y * w);
-    const double d = hi.v[6] * x + hi.v[7] * y + hi.v[8];
-    const double sx = (hi.v[0] * x + hi.v[1] * y + hi.v[2]) / d;
-    const double sy = (hi.v[3] * x + hi.v[4] * y + hi.v[5]) / d;
-    if (nearest) {
-        const double rx = rint(sx), ry = rint(sy);
-        const bool ok = rx >= 0 && rx < w && ry >= 0 && ry < h;
-        for (int k = 0; k < c; ++k) out[o * c + k] = ok ? img[((int64_t)ry * w + (int64_t)rx) * c + k] : 0;
-        if (valid) valid[o] = ok ? 1 : 0;
-        return;
-    }
-    double fx0 = floor(sx), fy0 = floor(sy);
-    const float fx = (float)(sx - fx0), fy = (float)(sy - fy0);
-    fx0 = fmin(fmax(fx0, -4.0), (double)w + 4.0);
-    fy0 = fmin(fmax(fy0, -4.0), (double)h + 4.0);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const bool okx0 = x0 >= 0 && x0 < w, okx1 = x0 + 1 >= 0 && x0 + 1 < w;
-    const bool oky0 = y0 >= 0 && y0 < h, oky1 = y0 + 1 >= 0 && y0 + 1 < h;
-    const float m00 = (okx0 && oky0) ? 1.f : 0.f, m01 = (okx1 && oky0) ? 1.f : 0.f;
-    const float m10 = (okx0 && oky1) ? 1.f : 0.f, m11 = (okx1 && oky1) ? 1.f : 0.f;
-    const int cx0 = min(max(x0, 0), w - 1), cx1 = min(max(x0 + 1, 0), w - 1);
-    const int cy0 = min(max(y0, 0), h - 1), cy1 = min(max(y0 + 1, 0), h - 1);
-    if (out != nullptr) {
-        for (int k = 0; k < c; ++k) {
-            const float t00 = m00 * (float)img[((int64_t)cy0 * w + cx0) * c + k];
-            const float t01 = m01 * (float)img[((int64_t)cy0 * w + cx1) * c + k];
-            const float t10 = m10 * (float)img[((int64_t)cy1 * w + cx0) * c + k];
-            const float t11 = m11 * (float)img[((int64_t)cy1 * w + cx1) * c + k];
-            const float top = t00 * (1.f - fx) + t01 * fx, bot = t10 * (1.f - fx) + t11 * fx;
-            const float v = top * (1.f - fy) + bot * fy;
-            out[o * c + k] = (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f);
-        }
-    }
-    if (valid != nullptr) {
-        const float top = m00 * (1.f - fx) + m01 * fx, bot = m10 * (1.f - fx) + m11 * fx;
-        valid[o] = (top * (1.f - fy) + bot * fy) > 0.f ? 1 : 0;
-    }
+    warp_pixel(img, h, w, c, hi, x, y, o, out, valid, nearest);
 }
 
 // cv2.resize(..., fx, fy, INTER_LINEAR) geometry: src = (dst + 0.5) * scale - 0.5, edge clamped;

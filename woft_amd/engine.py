@@ -242,6 +242,11 @@ class RaftEngine:
             self._plans[key] = _Plan(self, hp, wp)
         return self._plans[key]
 
+    def drop_plan(self, key):
+        """Forget the plan stored under `key` (the key `plan()` files it under) and with it its buffers; -> the plan or None.
+        Nobody calls this unless asked to bound the number of shapes (RAFTWrapper.bound_plans)."""
+        return self._plans.pop(key, None)
+
 
 class _Plan:
     """Buffers + launch programs for one padded input size (hp, wp), both multiples of 8."""

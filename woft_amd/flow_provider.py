@@ -5,6 +5,7 @@
 """
 import logging
 import os
+from collections import OrderedDict
 from pathlib import Path
 from timeit import default_timer as timer
 
@@ -54,6 +55,25 @@ def _mask_head_shapes(structure, fdim):
         raise ValueError(f"class_params.mask_head_structure {structure!r}: not a list of (channels, odd kernel) tuples "
                          "or channel counts (weighted_raft.py:387-409)") from None
     return shapes + [(1, cur, 1, 1)]
+
+
+class _Recent:
+    """Least-recently-used book-keeping of RAFTWrapper.bound_plans(): touch(key, keep) marks `key` as used now and returns the
+    keys that fall out -- all but the `keep` most recent ones, never the protected key (the one last touched with protect=True)."""
+
+    def __init__(self):
+        self.order, self.protected = OrderedDict(), None
+
+    def touch(self, key, keep, protect=False):
+        if protect:
+            self.protected = key
+        self.order[key] = None
+        self.order.move_to_end(key)
+        others = [k for k in self.order if k != self.protected]
+        dropped = others[:max(0, len(others) - keep)]
+        for k in dropped:
+            del self.order[k]
+        return dropped
 
 
 class RAFTWrapper:
@@ -145,6 +165,31 @@ class RAFTWrapper:
         self._cache_errors = set()
         self._last_dst = {}                # per buffer set: (id of the last dst_img object, padding geometry)
         self.source_features_reused = False
+        self._plan_bound = None
+        self._recent_plans, self._recent_outs, self._recent_pixels = _Recent(), _Recent(), _Recent()
+
+    def bound_plans(self, n_other):
+        """Opt-in bound on what the provider keeps per input shape (default: everything, for ever -- a tracker sees one or two
+        shapes).  After this call it keeps the shape of the flows from the pinned source, plus the `n_other` most recently used
+        other (shape, buffer set) pairs; older plans, their output buffers and window lists are dropped (least recently used
+        first) and rebuilt if the shape returns.  For callers whose input size changes from call to call: the window tracker's
+        frame t-1 -> t flows run on a box that follows the object."""
+        self._plan_bound = None if n_other is None else max(1, int(n_other))
+
+    def _touch_plan(self, plan_key, out_key, n_pix, pinned_here):
+        """Book-keeping of bound_plans(): plans are filed by PADDED size, output buffers by the un-padded size (several per plan),
+        the all-pixels window lists by 1/8-resolution pixel count -- of each, the pinned source's entry and the most recently
+        used others stay.  (What this call uses was just touched: it is never among the dropped.)"""
+        n = self._plan_bound
+        if n is None:
+            return
+        for key in self._recent_plans.touch(plan_key, n, protect=pinned_here):
+            plan = self.engine.drop_plan(key)
+            self._last_dst.pop(id(plan), None)
+        for key in self._recent_outs.touch(out_key, n, protect=pinned_here):
+            self._out.pop(key, None)
+        for key in self._recent_pixels.touch(n_pix, n, protect=pinned_here):
+            self._all_pixels.pop(key, None)
 
     def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True):
         """plan.flow() eagerly, or -- use_graph -- as ONE hipGraph launch (captured at the second call with the same
@@ -329,7 +374,9 @@ class RAFTWrapper:
         # a flow from another source leaves the pinned source's tensors (fmap1, net, inp, gate biases) where they are:
         # it runs in a second buffer set (the reference's lost branch, TRK:181-184, alternates template and frame t-1)
         pinned_here = src_img is self._pinned
-        plan = self.engine.plan(hp, wp, 0 if (pinned_here or self._pinned is None) else 1)
+        slot = 0 if (pinned_here or self._pinned is None) else 1
+        plan = self.engine.plan(hp, wp, slot)
+        self._touch_plan((hp, wp) if slot == 0 else (hp, wp, slot), (oh, ow), plan.P, pinned_here)
         start_time = timer()
 
         def up(a):

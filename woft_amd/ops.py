@@ -724,6 +724,59 @@ def warp_perspective_u8(img, Hmat, out=None, valid=None, nearest=False):
                                                stream_ptr()), "woft_warp_perspective_u8")
 
 
+def _hinv9(Hmat):
+    return (C.c_double * 9)(*np.linalg.inv(np.asarray(Hmat, dtype=np.float64)).ravel().tolist())
+
+
+def warp_perspective_window_u8(img, Hmat, rect, out=None, valid=None, nearest=False):
+    """The rectangle rect = (y0, x0, rows, cols) of warp_perspective_u8(img, Hmat, ...) into contiguous (rows, cols[, C]) `out`
+    and (rows, cols) `valid`: the same bytes as the full-frame call gives those destination pixels, for the window's work."""
+    h, w = img.shape[:2]
+    c = 1 if img.dim() == 2 else img.shape[2]
+    y0, x0, rows, cols = (int(v) for v in rect)
+    assert out is None or out.numel() == rows * cols * c
+    assert valid is None or valid.numel() == rows * cols
+    check(_lib.load().woft_warp_perspective_window_u8(ptr(img), h, w, c, _hinv9(Hmat), y0, x0, rows, cols, ptr(out), ptr(valid),
+                                                      int(nearest), stream_ptr()), "woft_warp_perspective_window_u8")
+
+
+def crop_u8(img, rect, out=None):
+    """img[y0:y0 + rows, x0:x0 + cols] of a packed (H, W[, C]) uint8 tensor as a contiguous tensor (woft_crop_u8)."""
+    h, w = img.shape[:2]
+    c = 1 if img.dim() == 2 else img.shape[2]
+    y0, x0, rows, cols = (int(v) for v in rect)
+    if out is None:
+        out = torch.empty((rows, cols) + tuple(img.shape[2:]), dtype=torch.uint8, device=img.device)
+    assert out.numel() == rows * cols * c and out.is_contiguous() and img.is_contiguous()
+    check(_lib.load().woft_crop_u8(ptr(img), h, w, c, y0, x0, rows, cols, ptr(out), stream_ptr()), "woft_crop_u8")
+    return out
+
+
+_BBOX_WS = {}
+
+
+def mask_bbox_ws(device=None):
+    """Scratch of woft_mask_bbox, zeroed once (every call leaves it zeroed); one per device and stream, like hfit_ws."""
+    dev = torch.device(device or DEV)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr())
+    if key not in _BBOX_WS:
+        _BBOX_WS[key] = torch.zeros(int(_lib.load().woft_mask_bbox_ws_bytes()), dtype=torch.uint8, device=dev)
+    return _BBOX_WS[key]
+
+
+def mask_bbox(mask, bbox=None, Hmat=None, warped=None, ws=None):
+    """{rmin, rmax, cmin, cmax, any} (5 int32 on the device) of the non-zero pixels of a (H, W) uint8 mask -- or, with Hmat, of
+    warp_perspective_u8(mask, Hmat, nearest=True), which `warped` (optional) receives in the same launch."""
+    h, w = mask.shape
+    if bbox is None:
+        bbox = torch.empty(5, dtype=torch.int32, device=mask.device)
+    assert mask.is_contiguous() and (warped is None or (warped.is_contiguous() and warped.numel() == h * w))
+    ws = ws if ws is not None else mask_bbox_ws(mask.device)
+    check(_lib.load().woft_mask_bbox(ptr(mask), h, w, None if Hmat is None else _hinv9(Hmat), ptr(warped), ptr(ws), ptr(bbox),
+                                     stream_ptr()), "woft_mask_bbox")
+    return bbox
+
+
 def resize_by_factor_u8(img, factor):
     """cv2.resize(img, None, fx=1/factor, fy=1/factor) (INTER_LINEAR geometry) on the device."""
     h, w = img.shape[:2]

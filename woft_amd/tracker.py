@@ -180,6 +180,7 @@ class YAOFTrackerSingleControl:
         return spec
 
     def _fused_buffers(self, n_grid):
+        # (WOFTWindow._fused_buffers swaps `_fb_key` / `_fb` from its own per-size cache: keep these two names)
         if getattr(self, "_fb_key", None) != n_grid:
             cap = 1024 if self._fused["n_draw"] else n_grid
             self._fb = dict(ws=ops.tc_select_ws(n_grid), pa=torch.empty(cap, 2, device=self.device),
@@ -455,3 +456,122 @@ class YAOFTrackerSingleControl:
         if judge:
             fit.success = bool(C.redet_success_fn(H, src_xy, dst_xy, post if post is not None else w))
         return fit
+
+
+class WOFTWindow(YAOFTrackerSingleControl):
+    """The reference's search-window tracker (pytracking/tracker/WOFT_window.py, WIN below): YAOFTrackerSingleControl with one
+    more config key, `search_window_margin`.  The template -> frame flow runs on the template mask's box plus that margin, fixed
+    at init() (WIN:37-44); the frame t-1 -> t flow of a lost frame on the box of the mask carried to frame t-1, plus the same
+    margin (WIN:212-221); a homography fitted between two crops goes back to frame coordinates through H_undo_crop (WIN:420-427).
+    State machine, solver back ends, weight-head shortcuts and the host-frame path are the parent's; only the two stages differ.
+
+    What differs from WIN, on purpose ("Search window"): a box that the minimum-size step pushes past the frame edge
+    is cut to the frame (WIN slices with a negative index there).  `search_bbox` / `local_search_bbox` hold the boxes in use
+    (woft_amd.window.Box; the local one is None on a frame that was not lost)."""
+    PLAN_BOUND = 4                    # local-window shapes the flow provider keeps besides the pinned global window
+    MIN_FLOW_SIDE = 16                # a local window cut smaller than this by the frame edge: no flow, previous pose kept
+
+    def __init__(self, config):
+        super().__init__(config)
+        from collections import OrderedDict
+        self._fb_cache = OrderedDict()
+        self.search_bbox = self.local_search_bbox = None
+        if hasattr(self.flower, "bound_plans"):
+            self.flower.bound_plans(self.PLAN_BOUND)
+
+    def init(self, img, mask, img_identifier=None):
+        from . import window
+        super().init(img, mask, img_identifier)                      # (downscaling, single-contour check, state: the parent's)
+        inside = self.np_template_mask > 0
+        Hh, Ww = inside.shape
+        self._margin = self.C.search_window_margin or None           # (absent key: an empty, falsy Config)
+        self._template_box = window.Box.from_mask(inside)
+        self.search_bbox = window.search_box(self._template_box, self._margin, Ww, Hh)
+        self.local_search_bbox = None
+        self._rect = rect = self.search_bbox.crop_rect()
+        y0, x0, rows, cols = rect
+        self._template_crop = ops.crop_u8(_device_u8(self.template_img), rect)
+        self._template_mask_crop = ops.crop_u8(self._template_mask_u8, rect)
+        self._gw_buf = None
+        if hasattr(self.flower, "pin_source"):                       # the parent pinned the whole template: re-pin the crop
+            self.flower.pin_source(self._template_crop)
+            if hasattr(self.flower, "pin_weight_region"):
+                self.flower.pin_weight_region(inside[y0:y0 + rows, x0:x0 + cols] if self._mask_weight_head() else None)
+
+    def track(self, input_img, debug=False, img_identifier=None):
+        self.local_search_bbox = None
+        return super().track(input_img, debug=debug, img_identifier=img_identifier)
+
+    def _fused_buffers(self, n_grid):
+        # (the parent keeps the buffers of ONE grid size; here the global and the local window alternate on lost frames)
+        c = self._fb_cache
+        if n_grid in c:
+            c.move_to_end(n_grid)
+            self._fb_key, self._fb = n_grid, c[n_grid]
+            return self._fb
+        self._fb_key = None
+        c[n_grid] = super()._fused_buffers(n_grid)
+        while len(c) > self.PLAN_BOUND + 1:
+            c.popitem(last=False)
+        return c[n_grid]
+
+    def _global_stage(self, frame, prewarp_H):
+        """Template crop -> the search window of the frame pre-warped by the last good homography (WIN:101-193): the window's
+        pixels of the pre-warp and of its validity map are all that is computed.  The keep rule runs in window coordinates with
+        the window's size as bounds (WIN:335-366), the re-detection test on the window-coordinate homography (WIN:191)."""
+        from . import window
+        rect = self._rect
+        rows, cols = rect[2], rect[3]
+        if self._gw_buf is None or self._gw_buf[0].shape[:2] != (rows, cols):
+            self._gw_buf = (torch.empty((rows, cols, frame.shape[2]), dtype=torch.uint8, device=self.device),
+                            torch.empty((rows, cols), dtype=torch.uint8, device=self.device))
+        prewarped, valid = self._gw_buf
+        if np.array_equal(prewarp_H, _EYE):
+            ops.crop_u8(frame, rect, prewarped)                      # identity warp: the frame's own pixels, all of them filled
+            valid = None
+        else:
+            ops.warp_perspective_window_u8(frame, prewarp_H, rect, prewarped, valid)
+        if self.C.do_not_mask_TCs_by_prewarped:
+            valid = None
+        src_xy, dst_xy, w, grid = self._flow(self._template_crop, prewarped)
+        fit = self._solve(src_xy, dst_xy, w, grid, (rows, cols), self._template_mask_crop, valid, bounds=True, judge=True)
+        fit.H = window.H_undo_crop(self.search_bbox, fit.H)
+        return fit
+
+    def _carried_mask_box(self):
+        """-> (template mask carried to frame t-1 (device uint8), its Box): nearest-neighbour warp by inv(prev_H2init) and the
+        bounding box of the result in one launch, one five-integer device -> host read (lost frames only)."""
+        from . import window
+        if np.array_equal(self.prev_H2init, _EYE):
+            return self._template_mask_u8, self._template_box
+        prev_mask = torch.empty_like(self._template_mask_u8)
+        if not self._margin:                                         # whole-frame window: nobody needs the box
+            ops.warp_perspective_u8(self._template_mask_u8, np.linalg.inv(self.prev_H2init), prev_mask, None, nearest=True)
+            return prev_mask, None
+        bbox = ops.mask_bbox(self._template_mask_u8, Hmat=np.linalg.inv(self.prev_H2init), warped=prev_mask)
+        rmin, rmax, cmin, cmax, any_set = bbox.cpu().tolist()
+        return prev_mask, window.Box.from_extent(rmin, rmax, cmin, cmax, bool(any_set))
+
+    def _local_stage(self, frame):
+        """Frame t-1 -> frame t on the box of the carried template mask plus the margin (WIN:208-255), chained onto the previous
+        pose.  A failed fit -- or a window the frame edge leaves no room for -- keeps the previous pose."""
+        from . import window
+        Hh, Ww = frame.shape[:2]
+        prev_mask, mask_box = self._carried_mask_box()
+        box = self.local_search_bbox = window.search_box(mask_box, self._margin, Ww, Hh)
+        rect = box.crop_rect()
+        if min(rect[2], rect[3]) < self.MIN_FLOW_SIDE:
+            logger.warning(f"local search window {box} leaves a {rect[2]} x {rect[3]} crop: no flow, pose of the previous frame kept")
+            return self.prev_H2init
+        prev_win = ops.crop_u8(_device_u8(self.prev_img), rect)
+        cur_win = ops.crop_u8(frame, rect)
+        mask_win = ops.crop_u8(prev_mask, rect)
+        src_xy, dst_xy, w, grid = self._flow(prev_win, cur_win)
+        try:                                                         # (the estimator only, as in the parent: anything else is an error)
+            fit = self._solve(src_xy, dst_xy, w, grid, (rect[2], rect[3]), mask_win, None, bounds=False, judge=False)
+            if not np.all(np.isfinite(fit.H)):
+                raise FloatingPointError("singular homography system")
+            return compose_H(window.H_undo_crop(box, fit.H), self.prev_H2init)
+        except Exception as ex:
+            logger.warning(f"frame-to-frame homography failed ({type(ex).__name__}): pose of the previous frame kept")
+            return self.prev_H2init

@@ -464,6 +464,20 @@ int woft_ransac(const float* pa, const float* pb, int32_t n_max, const int32_t* 
                 double conf, uint64_t seed, int32_t refine, void* ws, float* Hout, int32_t* status, int32_t* info,
                 uint8_t* inlier_mask, void* stream);
 
+/* RANSAC similarity (translation, rotation, scale; 4 degrees of freedom), what cv2.estimateAffinePartial2D(pa, pb,
+ * method=cv2.RANSAC, ransacReprojThreshold=thr, maxIters=max_iters, confidence=conf) does in utils/least_squares_H.py:349-363
+ * (find_homography_TRS), restated in csrc/trs.hip and DESIGN.md ("TRS"): max_iters two-point hypotheses from woft_ransac's
+ * SplitMix64 stream, closed-form fp64 models, cv2's fp32 error test err <= thr^2, cv2's sequential selection with the adaptive
+ * iteration count of confidence conf for two model points; then, for more than 2 inliers and refine != 0, the closed-form
+ * least-squares similarity over the inliers.  Arguments, count, info and inlier_mask as woft_ransac.
+ * ws: woft_trs_ws_bytes(n_max, max_iters) bytes of device scratch.  Hout: 9 floats (device), rows (a -b tx) (b a ty) (0 0 1).
+ * status[0] (device) = 0 ok, 1 fewer than 2 points, 2 no model (no hypothesis with 2 or more inliers; Hout all NaN).
+ * -1 (before any launch) on a NULL pointer, max_iters < 1, thr <= 0 or conf outside [0, 1]. */
+int64_t woft_trs_ws_bytes(int32_t n_max, int32_t max_iters);
+int woft_trs(const float* pa, const float* pb, int32_t n_max, const int32_t* count, int32_t max_iters, double thr,
+             double conf, uint64_t seed, int32_t refine, void* ws, float* Hout, int32_t* status, int32_t* info,
+             uint8_t* inlier_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,8 @@ _SIGS = {
     "woft_inlier_frac": (i32, [vp, vp, i32, vp, vp, f32, vp, vp]),
     "woft_ransac_ws_bytes": (i64, [i32, i32]),
     "woft_ransac": (i32, [vp, vp, i32, vp, i32, C.c_double, C.c_double, C.c_uint64, i32, vp, vp, vp, vp, vp, vp]),
+    "woft_trs_ws_bytes": (i64, [i32, i32]),
+    "woft_trs": (i32, [vp, vp, i32, vp, i32, C.c_double, C.c_double, C.c_uint64, i32, vp, vp, vp, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -25,8 +25,7 @@
 //   score  (hypothesis block x point chunk workgroups; partial counts by integer atomicAdd when there is more than one chunk:
 //           exact, so deterministic)  ->  select (one workgroup rebuilds the sequential loop from counts[]: prefix maxima,
 //           records, stop, best)  ->  mask (0/1 weights + optional uint8 mask)  ->  woft_hfit (DLT)  ->  final (LM + outputs).
-#include "common.h"
-#include <float.h>
+#include "ransac_common.h"
 #include <algorithm>
 
 namespace {
@@ -35,7 +34,6 @@ constexpr int RT = 256;             // threads of a scoring workgroup: 64 hypoth
 constexpr int RH = 64;              // hypotheses per scoring workgroup
 constexpr int RCHUNK = 2048;        // points per scoring workgroup (gridDim.y = ceil(n_max / RCHUNK))
 constexpr int MAX_ATTEMPTS = 1000;  // cv2's maxAttempts of getSubset
-constexpr int SELT = 1024;          // threads of the selection workgroup
 constexpr int LMT = 512;            // threads of the refinement workgroup (45 fp64 accumulators per lane)
 constexpr int LM_ITERS = 10;
 
@@ -53,7 +51,6 @@ struct RWs {
     void* hws;
 };
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 inline bool need_hws(int n_max) { return n_max > WOFT_HFIT_SINGLE_MAX; }
 
 inline RWs ws_layout(void* ws, int n_max, int max_iters) {
@@ -67,20 +64,6 @@ inline RWs ws_layout(void* ws, int n_max, int max_iters) {
     p += align256((int64_t)n_max * 4);
     o.hws = need_hws(n_max) ? (void*)p : nullptr;
     return o;
-}
-
-__device__ __forceinline__ int fit_n(const int* count, int n_max) { return count ? min(count[0], n_max) : n_max; }
-
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ int draw_index(uint64_t key, int k, uint32_t c, int n) {
-    const uint64_t u = splitmix64(key ^ (((uint64_t)(uint32_t)k << 32) | c));
-    return (int)(((u >> 32) * (uint64_t)n) >> 32);
 }
 
 // cv2 haveCollinearPoints for the triple (pivot i, j, k): differences of Point2f in fp32, the test in fp64
@@ -218,29 +201,10 @@ __global__ __launch_bounds__(RT) void ransac_score_kernel(const float2* __restri
     }
 }
 
-// RANSACUpdateNumIters(conf, (n - m) / n, 4, max_iters), the published formula; (1 - ep)^4 as two squarings
-__device__ int update_num_iters(double conf, int n, int m, int max_iters) {
-    const double p = fmin(fmax(conf, 0.0), 1.0);
-    const double ep = fmin(fmax((double)(n - m) / (double)n, 0.0), 1.0);
-    const double t = 1.0 - ep, t2 = t * t;
-    double num = fmax(1.0 - p, DBL_MIN);
-    double denom = 1.0 - t2 * t2;
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return (denom >= 0.0 || -num >= (double)max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
-
-__device__ __forceinline__ int niters_after(int m, double conf, int n, int max_iters) {
-    return m > 3 ? min(max_iters, update_num_iters(conf, n, m, max_iters)) : max_iters;
-}
-
 // one workgroup: the sequential loop's stop, best hypothesis and model, from counts[]
 __global__ __launch_bounds__(SELT) void ransac_select_kernel(const float2* __restrict__ pa, const float2* __restrict__ pb,
                                                              int n_max, const int* __restrict__ count, int max_iters, uint64_t key,
                                                              double conf, const int* __restrict__ counts, RState* __restrict__ st) {
-    __shared__ int scan[SELT];
-    __shared__ int stop_s, best_s;
     const int n = fit_n(count, n_max);
     const int tid = threadIdx.x;
     if (n < 4) {
@@ -258,43 +222,9 @@ __global__ __launch_bounds__(SELT) void ransac_select_kernel(const float2* __res
         }
         return;
     }
-    const int per = (max_iters + SELT - 1) / SELT;
-    const int b0 = min(max_iters, tid * per), b1 = min(max_iters, b0 + per);
-    int segmax = 0;
-    for (int k = b0; k < b1; ++k) segmax = max(segmax, counts[k]);
-    scan[tid] = segmax;
-    if (tid == 0) { stop_s = max_iters; best_s = -1; }
-    __syncthreads();
-    for (int o = 1; o < SELT; o <<= 1) {                    // inclusive prefix max
-        const int v = tid >= o ? scan[tid - o] : 0;
-        __syncthreads();
-        scan[tid] = max(scan[tid], v);
-        __syncthreads();
-    }
-    const int before = tid > 0 ? scan[tid - 1] : 0;          // max of the counts ahead of this thread's segment
-    // stop: the first k with k >= niters(after k-1) or no sample at k
-    int m = before;
-    for (int k = b0; k < b1; ++k) {
-        const int c = counts[k];
-        if (k >= niters_after(m, conf, n, max_iters) || c < 0) {
-            atomicMin(&stop_s, k);
-            break;
-        }
-        m = max(m, c);
-    }
-    __syncthreads();
-    const int S = stop_s;
-    // best: the last record (count > max(best, 3)) before the stop = the first index reaching the final maximum
-    m = before;
-    int last = -1;
-    for (int k = b0; k < min(b1, S); ++k) {
-        const int c = counts[k];
-        if (c > max(m, 3)) { m = c; last = k; }
-    }
-    if (last >= 0) atomicMax(&best_s, last);
-    __syncthreads();
+    int S, best;
+    sequential_select<4>(counts, max_iters, conf, n, S, best);
     if (tid == 0) {
-        const int best = best_s;
         st->iters = S;
         st->best_k = best;
         if (best < 0) {

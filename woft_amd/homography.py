@@ -150,6 +150,37 @@ def find_homography_cvransac(pts_A, pts_B, weights=None, max_iters=10000, thr=1.
     return H.to(pts_A.device)
 
 
+def find_homography_TRS(pts_A, pts_B, weights=None, max_iters=10000, thr=3.0, conf=0.999, seed=0):
+    """RANSAC similarity -- translation, rotation, scale -- as a homography (least_squares_H.py:349-363,
+    cv2.estimateAffinePartial2D(..., method=cv2.RANSAC, ransacReprojThreshold=3, maxIters=10000, confidence=0.999) there: its
+    fixed parameters are the defaults here), on the HIP device (csrc/trs.hip; semantics and deviations in DESIGN.md, "TRS").
+    pts (B,N,2) -> (B,3,3) float64 with last row (0, 0, 1), on pts_A's device; numpy in, numpy out.  `weights` is accepted and
+    ignored, as the reference ignores it.  Every batch element is fitted independently with the same `seed`.  Where no model
+    is found (no hypothesis with 2 or more inliers) that element's H is all NaN; the reference fails there on cv2's None."""
+    rec = recorder()
+    if rec is not None:
+        return rec.fit("trs", pts_A, pts_B, weights, ransac=(max_iters, thr, conf))
+    N = pts_A.shape[1]
+    assert N >= 2, "Not enough correspodences for a similarity"
+    using_torch = isinstance(pts_A, torch.Tensor)
+    a = pts_A if using_torch else torch.from_numpy(np.ascontiguousarray(pts_A))
+    b = pts_B if using_torch else torch.from_numpy(np.ascontiguousarray(pts_B))
+    if tuple(a.shape) != tuple(b.shape) or a.dim() != 3 or a.shape[-1] != 2:
+        raise AssertionError((tuple(a.shape), tuple(b.shape)))
+    dev = a.device if a.is_cuda else torch.device("cuda")      # (host inputs: fitted on the HIP device, handed back)
+    B = a.shape[0]
+    out = torch.empty(B, 9, dtype=torch.float32, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    for k in range(B):
+        pa = a[k].to(device=dev, dtype=torch.float32).contiguous()
+        pb = b[k].to(device=dev, dtype=torch.float32).contiguous()
+        ops.trs(pa, pb, out[k], status[k:k + 1], max_iters=max_iters, thr=thr, conf=conf, seed=seed)
+    H = out.double().view(B, 3, 3)
+    if not using_torch:
+        return H.cpu().numpy()
+    return H.to(pts_A.device)
+
+
 def torch_proj_errors(GT_H, pts_A, pts_B):
     """L2 distance between H * pts_A and pts_B (least_squares_H.py:474-489).
     GT_H (B,3,3); pts (B,2,N) -> (B,N)."""

@@ -871,6 +871,32 @@ def ransac(pa, pb, Hout, status, count=None, max_iters=10000, thr=1.4142, conf=0
                                   ptr(inlier_mask), stream_ptr()), "woft_ransac")
 
 
+_TRS_WS = {}
+
+
+def trs_ws(n_max, max_iters, device=None):
+    """Scratch of woft_trs (woft_trs_ws_bytes(n_max, max_iters)), one per device and stream like ransac_ws, grown on demand."""
+    dev = torch.device(device or DEV)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr())
+    need = int(_lib.load().woft_trs_ws_bytes(int(n_max), int(max_iters)))
+    if need < 0:
+        raise _lib.WoftHipError(f"woft_trs_ws_bytes({n_max}, {max_iters}) rejected its arguments")
+    if key not in _TRS_WS or _TRS_WS[key].numel() < need:
+        _TRS_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return _TRS_WS[key]
+
+
+def trs(pa, pb, Hout, status, count=None, max_iters=10000, thr=3.0, conf=0.999, seed=0, refine=True, info=None,
+        inlier_mask=None, ws=None):
+    """RANSAC similarity pa -> pb (csrc/trs.hip): Hout 9 floats, status 1 int32, info 3 int32 (inliers, best k, iterations) and
+    inlier_mask uint8 [n_max] optional; n = min(count[0], n_max) when count is given."""
+    n = pa.shape[0]
+    ws = ws if ws is not None else trs_ws(n, max_iters, pa.device)
+    check(_lib.load().woft_trs(ptr(pa), ptr(pb), n, ptr(count), int(max_iters), float(thr), float(conf),
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(refine)), ptr(ws), ptr(Hout), ptr(status), ptr(info),
+                               ptr(inlier_mask), stream_ptr()), "woft_trs")
+
+
 def inlier_frac(pa, pb, Hm, frac, thr=5.0, count=None):
     check(_lib.load().woft_inlier_frac(ptr(pa), ptr(pb), pa.shape[0], ptr(count), ptr(Hm), float(thr), ptr(frac),
                                        stream_ptr()), "woft_inlier_frac")

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .homography import (IRLSq_Huber, IRLSq_L1, find_homography_cvransac, find_homography_IRLSq_QR,
-                         find_homography_nonhomogeneous_QR, torch_proj_errors)
+                         find_homography_nonhomogeneous_QR, find_homography_TRS, torch_proj_errors)
 
 
 def sobol_points(n):
@@ -65,4 +65,13 @@ def estimator_ransac(max_iters=10000, thr=3.0, conf=0.995):
     def find_homography(pts_A, pts_B, weights=None):
         return find_homography_cvransac(pts_A, pts_B, weights=weights, max_iters=max_iters, thr=thr, conf=conf)
     find_homography.woft_spec = ("ransac", int(max_iters), float(thr), float(conf))
+    return find_homography
+
+
+def estimator_trs(max_iters=10000, thr=3.0, conf=0.999):
+    """RANSAC similarity -- translation, rotation, scale (least_squares_H.py:349-363, with its fixed parameters as defaults); the
+    weights are ignored."""
+    def find_homography(pts_A, pts_B, weights=None):
+        return find_homography_TRS(pts_A, pts_B, weights=weights, max_iters=max_iters, thr=thr, conf=conf)
+    find_homography.woft_spec = ("trs", int(max_iters), float(thr), float(conf))
     return find_homography

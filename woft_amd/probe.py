@@ -15,7 +15,8 @@ callables); an unmodified reference config fell back to calling its functions on
                         woft_amd.homography): accepted when it makes exactly one library call, hands its own arguments through
                         untouched and returns that call's result untouched; an IRLS re-weighting callable is matched against
                         IRLSq_L1 / IRLSq_Huber(k) on a residual sweep; a `find_homography_cvransac` call is accepted with constant
-                        max_iters / thr / conf and taken as unweighted (RANSAC ignores the weights);
+                        max_iters / thr / conf and taken as unweighted (RANSAC ignores the weights), and so is a
+                        `find_homography_TRS` call (the RANSAC similarity);
   * re-detection test -- the same recorder answers its `torch_proj_errors` call with crafted error vectors: accepted when the
                         verdict is `mean(errs <= thr) > frac` for a (thr, frac) pair identified by bisection and then checked
                         on a grid of (inlier count, N) cases, and when it projects the current-frame points onto the template.
@@ -163,20 +164,21 @@ def _probe_estimator_once(fn, n, device, with_weights=True):
     if len(rec.calls) != 1:
         return None
     c = rec.calls[0]
-    if c["kind"] not in ("lsq", "irls", "ransac") or out is not c["out"]:
+    if c["kind"] not in ("lsq", "irls", "ransac", "trs") or out is not c["out"]:
         return None
     same = lambda x, y: x is y or (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.shape == y.shape
                                    and x.dtype == y.dtype and torch.equal(x, y))
     if not (same(c["a"], a) and same(c["b"], b) and (c["w"] is None or same(c["w"], w))):
         return None
-    if c["kind"] == "ransac":
-        # RANSAC ignores the weights (cv2.findHomography has none): an unweighted fit whichever weights it was handed
+    if c["kind"] in ("ransac", "trs"):
+        # RANSAC ignores the weights (cv2.findHomography / estimateAffinePartial2D have none): an unweighted fit whichever weights
+        # it was handed
         max_iters, thr, conf = c["ransac"]
         num = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool) and np.isfinite(x)
         if not (isinstance(max_iters, (int, np.integer)) and not isinstance(max_iters, bool) and 1 <= max_iters < 2 ** 31
                 and num(thr) and thr > 0 and num(conf) and 0 <= conf <= 1):
             return None
-        return "ransac", int(max_iters), float(thr), float(conf), False
+        return c["kind"], int(max_iters), float(thr), float(conf), False
     weighted = c["w"] is not None          # (the reference's "plainLSq" configs hand the library weights=None: an unweighted fit)
     if c["kind"] == "lsq":
         return 0, 0.0, 0, weighted
@@ -194,7 +196,8 @@ def probe_estimator(fn, device="cpu"):
     """-> (reweight, huber_k, n_irls, weighted) when fn(pts_A (1,N,2), pts_B, weights (1,N)) is one pass-through call of the
     library's least-squares / IRLS estimator (reweight 0 / 1 L1 / 2 Huber; weighted = it hands the weights on);
     ("ransac", max_iters, thr, conf, False) when it is one pass-through call of find_homography_cvransac with constant
-    parameters (unweighted: RANSAC ignores the weights); else None.
+    parameters (unweighted: RANSAC ignores the weights), ("trs", max_iters, thr, conf, False) alike for find_homography_TRS;
+    else None.
     Asked at several N -- the minimal 4, 5, the subsampler's 500, beyond the one-workgroup solver's range -- and every answer must be
     the same (a callable that switches estimator on the number of correspondences keeps the callable back end); where it also accepts
     weights=None it must make the same call there, unweighted."""
@@ -337,8 +340,8 @@ def solver_spec(estimator, subsampler, redetection, device="cpu"):
     dict(reweight, huber_k, n_irls, thr, min_frac, n_draw) or None (callable back end), and how it was decided."""
     how = []
     spec = getattr(estimator, "woft_spec", None)
-    if spec is not None and spec[0] == "ransac":
-        est = ("ransac", int(spec[1]), float(spec[2]), float(spec[3]), False)
+    if spec is not None and spec[0] in ("ransac", "trs"):
+        est = (spec[0], int(spec[1]), float(spec[2]), float(spec[3]), False)
     else:
         est = (int(spec[1]), float(spec[2]), int(spec[3]), True) if spec is not None else probe_estimator(estimator, device)
     how.append("estimator: " + ("tagged" if spec is not None else ("probed" if est is not None else "callable")))
@@ -363,7 +366,7 @@ def solver_spec(estimator, subsampler, redetection, device="cpu"):
     const = red[1] if red[0] == "const" else None
     common = dict(thr=5.0 if const is not None else red[0], min_frac=0.0 if const is not None else red[1], const_verdict=const,
                   n_draw=n_draw)
-    if est[0] == "ransac":                 # (woft_ransac in place of woft_hfit; the same selection, result slots and host read)
-        return dict(reweight=0, huber_k=0.0, n_irls=0, weighted=False, ransac=dict(max_iters=est[1], thr=est[2], conf=est[3]),
+    if est[0] in ("ransac", "trs"):        # (woft_ransac / woft_trs in place of woft_hfit; the same selection, result slots and host read)
+        return dict(reweight=0, huber_k=0.0, n_irls=0, weighted=False, **{est[0]: dict(max_iters=est[1], thr=est[2], conf=est[3])},
                     **common), "; ".join(how)
     return dict(reweight=est[0], huber_k=est[1], n_irls=est[2], weighted=est[3], **common), "; ".join(how)

@@ -10,8 +10,8 @@ to ONE solver, `_solve`, which has two interchangeable back ends with identical 
 bit for bit):
 
   * device back end  -- configs built from woft_amd.presets (tagged callables): masking,
-    order-preserving compaction, Sobol selection, H fit (least squares / IRLS, or RANSAC) and
-    inlier test are HIP kernels (csrc/select.hip, csrc/hfit.hip, csrc/ransac.hip) with ONE
+    order-preserving compaction, Sobol selection, H fit (least squares / IRLS, RANSAC, or the RANSAC
+    similarity) and inlier test are HIP kernels (csrc/select.hip, csrc/hfit.hip, csrc/ransac.hip, csrc/trs.hip) with ONE
     device->host read per flow;
   * callable back end -- any other reference-format config: the keep rule runs as the same
     `select` kernel (woft_tc_flags), the surviving correspondences are handed to the config's own
@@ -190,6 +190,9 @@ class YAOFTrackerSingleControl:
             R = self._fused.get("ransac")
             if R is not None:
                 self._fb["fit_ws"] = ops.ransac_ws(cap, R["max_iters"], self.device)
+            T = self._fused.get("trs")
+            if T is not None:
+                self._fb["fit_ws"] = ops.trs_ws(cap, T["max_iters"], self.device)
             self._fb_key = n_grid
         return self._fb
 
@@ -405,10 +408,13 @@ class YAOFTrackerSingleControl:
         else:
             ops.tc_select(dst_xy, w, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds, F["sobol_u"], b["ws"],
                           b["pa"], b["pb"], b["w"], ires[12:14], grid=grid)
-        R = F.get("ransac")
+        R, T = F.get("ransac"), F.get("trs")
         if R is not None:                  # (status 1 / 2 in the same slot: fewer than 4 points / no model, H all NaN)
             ops.ransac(b["pa"], b["pb"], res[0:9], ires[10:11], count=ires[12:13], max_iters=R["max_iters"], thr=R["thr"],
                        conf=R["conf"], ws=b["fit_ws"])
+        elif T is not None:                # (the similarity estimator: status 1 is fewer than 2 points)
+            ops.trs(b["pa"], b["pb"], res[0:9], ires[10:11], count=ires[12:13], max_iters=T["max_iters"], thr=T["thr"],
+                    conf=T["conf"], ws=b["fit_ws"])
         else:
             ops.hfit(b["pa"], b["pb"], b["w"] if weighted else None, res[0:9], ires[10:11], count=ires[12:13],
                      reweight=F["reweight"], huber_k=F["huber_k"], n_irls=F["n_irls"], ws=b["fit_ws"])
@@ -425,7 +431,7 @@ class YAOFTrackerSingleControl:
         self.host_wait_s += time.perf_counter() - t0      # (bench: wall time minus this = the launch loop's host time per frame)
         ih = host.view(torch.int32)
         if int(ih[10]) == 1:
-            raise AssertionError(torch.Size([1, int(ih[12]), 2]))    # least_squares_H.py:162 (fewer than 4 points)
+            raise AssertionError(torch.Size([1, int(ih[12]), 2]))    # least_squares_H.py:162 (fewer than 4 points; TRS: than 2)
         verdict = F.get("const_verdict")       # (a re-detection test that is `return True` / `return False`: the reference's ablations)
         if verdict is None:
             verdict = bool(np.float32(host[9]) > np.float32(F["min_frac"]))

@@ -423,6 +423,19 @@ int woft_tc_select(const float* dst, const float* w, const uint8_t* tmask, const
  * tracker's generic path hands the compacted tensors to the config's subsampler / estimator callables). */
 int woft_tc_flags(const float* dst, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw, int32_t mh,
                   int32_t mw, int32_t check_dst, uint8_t* flags, void* stream);
+/* The same two with a per-source-pixel visibility probability vis: [gh*gw] float32 (this project's own rule, DESIGN.md
+ * "Visibility mask in the tracker"; the reference's tracker consumes no mask).  vis_mode 1 (gate): correspondence i survives iff it
+ * survives the keep rule above and vis[i] > vis_thr -- a strict fp32 compare, NaN is dropped; count[1], the Sobol draw and the
+ * compaction see the gated set; weights untouched.  vis_mode 2 (weight): keep rule unchanged, wout[k] = w[i] * vis[i] (one fp32
+ * multiply), vis[i] when w == NULL; woft_tc_flags_vis then equals woft_tc_flags.  vis == NULL or vis_mode 0: bit-identical to the
+ * entry points above.  vis[i] is read only where tmask passes.  Same workspace, same output format. */
+int woft_tc_select_vis(const float* dst, const float* w, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh,
+                       int32_t gw, int32_t mh, int32_t mw, int32_t check_dst, const float* sobol_u, int32_t n_draw,
+                       const float* vis, int32_t vis_mode, float vis_thr, void* ws, float* pa, float* pb, float* wout,
+                       int32_t cap, int32_t* count, void* stream);
+int woft_tc_flags_vis(const float* dst, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw, int32_t mh,
+                      int32_t mw, int32_t check_dst, const float* vis, int32_t vis_mode, float vis_thr, uint8_t* flags,
+                      void* stream);
 
 /* Weighted / iteratively re-weighted least-squares homography, utils/least_squares_H.py:142-210
  * (n_irls = 0) and :280-346 (n_irls = 5 -> 6 solves); reweight: 0 none, 1 L1 (:268-269),

@@ -96,6 +96,8 @@ _SIGS = {
     "woft_tc_select_ws_bytes": (i64, [i64]),
     "woft_tc_select": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
     "woft_tc_flags": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "woft_tc_select_vis": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, i32, vp, vp]),
+    "woft_tc_flags_vis": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, vp]),
     "woft_hfit_ws_bytes": (i64, []),
     "woft_hfit": (i32, [vp, vp, vp, i32, vp, i32, f32, i32, vp, vp, vp, vp]),
     "woft_hfit_step": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),

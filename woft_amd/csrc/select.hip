@@ -9,6 +9,10 @@
 //   N = number kept; if n_draw == 0 or n_draw >= N: every kept correspondence is selected, else the
 //   selected ranks are the DISTINCT values of (int32) rint(float32(N) * u_k), k < n_draw, in increasing
 //   order (the reference sets a boolean mask: original order, duplicates collapse).
+// Visibility (this project's own rule, not the reference's; DESIGN.md "Visibility mask in the tracker"): with a per-source-pixel
+// probability vis[i] the GATE adds `and vis[i] > thr` to keep[i] (strict fp32 compare: NaN is dropped), the WEIGHT rule leaves
+// keep[i] alone and writes w[k] * vis (vis alone without weights).  Both are template arguments of the kernels below: the
+// instantiations without them are the code of the entry points that take no visibility.
 // Three launches, no host round trip: (a) flags + per-1024 counts, (b) one workgroup: scan of the
 // counts, N, sorted unique rank list, (c) ranks -> output slots.  Outputs are in the H-fit kernel's
 // format: pa[k] = (dst_x, dst_y), pb[k] = (src_x, src_y), w[k].
@@ -61,11 +65,21 @@ struct Geo {
     int gh, gw, mh, mw;
 };
 
+// the visibility gate: vis[i] is read only where the template mask (a byte) has already passed
+struct Gate {
+    const float* vis;
+    float thr;
+};
+
+template <bool GATE>
 __device__ __forceinline__ bool keep_flag(const float* __restrict__ dst, const uint8_t* __restrict__ tmask,
                                           const uint8_t* __restrict__ pwmask, const Geo g, int check_dst, int64_t i,
-                                          int64_t n) {
+                                          int64_t n, const Gate v) {
     const int64_t mi = (g.gw == g.mw) ? i : (i / g.gw) * g.mw + (i % g.gw);
     bool keep = tmask[mi] != 0;
+    if (GATE) {
+        if (keep) keep = v.vis[i] > v.thr;           // (NaN compares false: dropped)
+    }
     if (keep && check_dst) {
         const float dx = dst[i], dy = dst[n + i];
         // NaN compares false below; treat it as out of bounds explicitly
@@ -77,17 +91,19 @@ __device__ __forceinline__ bool keep_flag(const float* __restrict__ dst, const u
 }
 
 // flags only (the tracker's generic path: the host compacts with the boolean mask, as the reference does)
+template <bool GATE>
 __global__ __launch_bounds__(256) void flags_kernel(const float* __restrict__ dst, const uint8_t* __restrict__ tmask,
                                                     const uint8_t* __restrict__ pwmask, Geo g, int check_dst,
-                                                    uint8_t* __restrict__ flags) {
+                                                    uint8_t* __restrict__ flags, Gate v) {
     const int64_t n = (int64_t)g.gh * g.gw;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) flags[i] = keep_flag(dst, tmask, pwmask, g, check_dst, i, n) ? 1 : 0;
+    if (i < n) flags[i] = keep_flag<GATE>(dst, tmask, pwmask, g, check_dst, i, n, v) ? 1 : 0;
 }
 
+template <bool GATE>
 __global__ __launch_bounds__(256) void select_flags_kernel(const float* __restrict__ dst, const uint8_t* __restrict__ tmask,
                                                            const uint8_t* __restrict__ pwmask, Geo g,
-                                                           int check_dst, int* ws, int nb) {
+                                                           int check_dst, int* ws, int nb, Gate v) {
     const Ws s = ws_layout(ws, nb);
     const int64_t n = (int64_t)g.gh * g.gw;
     const int64_t i0 = (int64_t)blockIdx.x * CHUNK + threadIdx.x * 4;
@@ -97,7 +113,7 @@ __global__ __launch_bounds__(256) void select_flags_kernel(const float* __restri
     for (int e = 0; e < 4; ++e) {
         const int64_t i = i0 + e;
         if (i >= n) continue;
-        f[e] = keep_flag(dst, tmask, pwmask, g, check_dst, i, n) ? 1 : 0;
+        f[e] = keep_flag<GATE>(dst, tmask, pwmask, g, check_dst, i, n, v) ? 1 : 0;
         cnt += f[e];
     }
     if (i0 < n) {
@@ -177,10 +193,11 @@ __global__ __launch_bounds__(1024) void select_plan_kernel(int* ws, int nb, cons
     }
 }
 
+template <bool VIS_WEIGHT>
 __global__ __launch_bounds__(256) void select_gather_kernel(const float* __restrict__ dst, const float* __restrict__ wgt,
                                                             int h, int w, const int* ws, int nb,
                                                             float* __restrict__ pa, float* __restrict__ pb,
-                                                            float* __restrict__ wo, int cap) {
+                                                            float* __restrict__ wo, int cap, const float* __restrict__ vis) {
     const Ws s = ws_layout(const_cast<int*>(ws), nb);
     const int64_t n = (int64_t)h * w;
     const int64_t i0 = (int64_t)blockIdx.x * CHUNK + threadIdx.x * 4;
@@ -214,8 +231,57 @@ __global__ __launch_bounds__(256) void select_gather_kernel(const float* __restr
         pa[2 * slot + 1] = dst[n + i];
         pb[2 * slot] = (float)(i % w);
         pb[2 * slot + 1] = (float)(i / w);
-        if (wo != nullptr) wo[slot] = (wgt != nullptr) ? wgt[i] : 1.f;
+        if (VIS_WEIGHT) {
+            if (wo != nullptr) wo[slot] = (wgt != nullptr) ? __fmul_rn(wgt[i], vis[i]) : vis[i];
+        } else {
+            if (wo != nullptr) wo[slot] = (wgt != nullptr) ? wgt[i] : 1.f;
+        }
     }
+}
+
+enum { VIS_NONE = 0, VIS_GATE = 1, VIS_WEIGHTED = 2 };
+
+int launch_flags(const float* dst, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw, int32_t mh, int32_t mw,
+                 int32_t check_dst, const float* vis, int32_t vis_mode, float vis_thr, uint8_t* flags, void* stream) {
+    if (!tmask || !flags || gh <= 0 || gw <= 0 || gh > mh || gw > mw || (check_dst && !dst)) return WOFT_EINVAL;
+    if (vis_mode < VIS_NONE || vis_mode > VIS_WEIGHTED || vis_thr != vis_thr) return WOFT_EINVAL;
+    const int64_t n = (int64_t)gh * gw;
+    const Geo g = {gh, gw, mh, mw};
+    const Gate v = {vis, vis_thr};
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (vis != nullptr && vis_mode == VIS_GATE)
+        hipLaunchKernelGGL(flags_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, dst, tmask, pwmask, g, check_dst, flags, v);
+    else
+        hipLaunchKernelGGL(flags_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, dst, tmask, pwmask, g, check_dst, flags, v);
+    return woft_launch_status();
+}
+
+int launch_select(const float* dst, const float* w, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw,
+                  int32_t mh, int32_t mw, int32_t check_dst, const float* sobol_u, int32_t n_draw, const float* vis,
+                  int32_t vis_mode, float vis_thr, void* ws, float* pa, float* pb, float* wout, int32_t cap, int32_t* count,
+                  void* stream) {
+    if (!dst || !tmask || !ws || !pa || !pb || !count || gh <= 0 || gw <= 0 || gh > mh || gw > mw || cap <= 0)
+        return WOFT_EINVAL;
+    if (n_draw < 0 || n_draw > MAX_DRAW || (n_draw > 0 && !sobol_u)) return WOFT_EINVAL;
+    if (vis_mode < VIS_NONE || vis_mode > VIS_WEIGHTED || vis_thr != vis_thr) return WOFT_EINVAL;
+    if (vis == nullptr) vis_mode = VIS_NONE;
+    const int64_t n = (int64_t)gh * gw;
+    const int nb = (int)((n + CHUNK - 1) / CHUNK);
+    const Geo g = {gh, gw, mh, mw};
+    const Gate v = {vis, vis_thr};
+    hipStream_t s = (hipStream_t)stream;
+    if (vis_mode == VIS_GATE)
+        hipLaunchKernelGGL(select_flags_kernel<true>, dim3(nb), dim3(256), 0, s, dst, tmask, pwmask, g, check_dst, (int*)ws, nb, v);
+    else
+        hipLaunchKernelGGL(select_flags_kernel<false>, dim3(nb), dim3(256), 0, s, dst, tmask, pwmask, g, check_dst, (int*)ws, nb, v);
+    hipLaunchKernelGGL(select_plan_kernel, dim3(1), dim3(1024), 0, s, (int*)ws, nb, sobol_u, n_draw, cap, count);
+    if (vis_mode == VIS_WEIGHTED)
+        hipLaunchKernelGGL(select_gather_kernel<true>, dim3(nb), dim3(256), 0, s, dst, w, gh, gw, (const int*)ws, nb, pa, pb,
+                           wout, cap, vis);
+    else
+        hipLaunchKernelGGL(select_gather_kernel<false>, dim3(nb), dim3(256), 0, s, dst, w, gh, gw, (const int*)ws, nb, pa, pb,
+                           wout, cap, vis);
+    return woft_launch_status();
 }
 
 }  // namespace
@@ -227,28 +293,27 @@ extern "C" int64_t woft_tc_select_ws_bytes(int64_t n) {
 
 extern "C" int woft_tc_flags(const float* dst, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw,
                              int32_t mh, int32_t mw, int32_t check_dst, uint8_t* flags, void* stream) {
-    if (!tmask || !flags || gh <= 0 || gw <= 0 || gh > mh || gw > mw || (check_dst && !dst)) return WOFT_EINVAL;
-    const int64_t n = (int64_t)gh * gw;
-    const Geo g = {gh, gw, mh, mw};
-    hipLaunchKernelGGL(flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dst, tmask,
-                       pwmask, g, check_dst, flags);
-    return woft_launch_status();
+    return launch_flags(dst, tmask, pwmask, gh, gw, mh, mw, check_dst, nullptr, VIS_NONE, 0.f, flags, stream);
+}
+
+extern "C" int woft_tc_flags_vis(const float* dst, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw,
+                                 int32_t mh, int32_t mw, int32_t check_dst, const float* vis, int32_t vis_mode, float vis_thr,
+                                 uint8_t* flags, void* stream) {
+    return launch_flags(dst, tmask, pwmask, gh, gw, mh, mw, check_dst, vis, vis_mode, vis_thr, flags, stream);
 }
 
 extern "C" int woft_tc_select(const float* dst, const float* w, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh,
                               int32_t gw, int32_t mh, int32_t mw, int32_t check_dst, const float* sobol_u,
                               int32_t n_draw, void* ws, float* pa, float* pb, float* wout, int32_t cap, int32_t* count,
                               void* stream) {
-    if (!dst || !tmask || !ws || !pa || !pb || !count || gh <= 0 || gw <= 0 || gh > mh || gw > mw || cap <= 0)
-        return WOFT_EINVAL;
-    if (n_draw < 0 || n_draw > MAX_DRAW || (n_draw > 0 && !sobol_u)) return WOFT_EINVAL;
-    const int64_t n = (int64_t)gh * gw;
-    const int nb = (int)((n + CHUNK - 1) / CHUNK);
-    const Geo g = {gh, gw, mh, mw};
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(select_flags_kernel, dim3(nb), dim3(256), 0, s, dst, tmask, pwmask, g, check_dst, (int*)ws, nb);
-    hipLaunchKernelGGL(select_plan_kernel, dim3(1), dim3(1024), 0, s, (int*)ws, nb, sobol_u, n_draw, cap, count);
-    hipLaunchKernelGGL(select_gather_kernel, dim3(nb), dim3(256), 0, s, dst, w, gh, gw, (const int*)ws, nb, pa, pb,
-                       wout, cap);
-    return woft_launch_status();
+    return launch_select(dst, w, tmask, pwmask, gh, gw, mh, mw, check_dst, sobol_u, n_draw, nullptr, VIS_NONE, 0.f, ws, pa, pb,
+                         wout, cap, count, stream);
+}
+
+extern "C" int woft_tc_select_vis(const float* dst, const float* w, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh,
+                                  int32_t gw, int32_t mh, int32_t mw, int32_t check_dst, const float* sobol_u,
+                                  int32_t n_draw, const float* vis, int32_t vis_mode, float vis_thr, void* ws, float* pa,
+                                  float* pb, float* wout, int32_t cap, int32_t* count, void* stream) {
+    return launch_select(dst, w, tmask, pwmask, gh, gw, mh, mw, check_dst, sobol_u, n_draw, vis, vis_mode, vis_thr, ws, pa, pb,
+                         wout, cap, count, stream);
 }

@@ -755,12 +755,14 @@ class _Plan:
         return reused
 
     def flow(self, iters, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False, trace=None, defer_wh=False,
-             mout=None):
+             mout=None, mask_sigmoid=False):
         """Target features -> volume -> `iters` refinements -> full-resolution outputs.
         defer_wh (full weighted model with a weight region set): stop before the weight head -- flow_up / dst are final,
         wout is NOT written -- and let finish_weights() evaluate the head where the caller then says it reads the weights.
         mout (engine built with mask_head): receives the upsampled visibility-mask logits (h*w floats, cropped like wout, never
-        passed through a sigmoid); the head runs after the weight head whether or not mout is given."""
+        passed through a sigmoid); the head runs after the weight head whether or not mout is given.
+        mask_sigmoid (the tracker's visibility request only): mout receives the sigmoid of those logits instead -- the do_sigmoid
+        flag the upsampling kernels already have for the weight channel."""
         e, sp = self.eng, self.eng.spec
         if iters < 1:
             raise ValueError("iters must be >= 1")
@@ -803,9 +805,10 @@ class _Plan:
             self._mask_head()
             if mout is not None:        # the weight channel of the same upsampling kernels, on the mask logits (weighted_raft.py:305-308)
                 if sp.small:
-                    ops.upflow8(self.coords, self.mh_low, self.hf, self.wf, crop, h, w, wout=mout)
+                    ops.upflow8(self.coords, self.mh_low, self.hf, self.wf, crop, h, w, wout=mout, do_sigmoid=mask_sigmoid)
                 else:
-                    ops.convex_upsample(self.coords, self.mh_low, self.mask.t, self.hf, self.wf, crop, h, w, wout=mout)
+                    ops.convex_upsample(self.coords, self.mh_low, self.mask.t, self.hf, self.wf, crop, h, w, wout=mout,
+                                        do_sigmoid=mask_sigmoid)
 
     def _mask_head(self):
         """MaskHead on the final coordinates (weighted_raft.py:295-304, 411-422) -> self.mh_low (1/8-resolution logits)."""

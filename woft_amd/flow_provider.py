@@ -191,19 +191,19 @@ class RAFTWrapper:
         for key in self._recent_pixels.touch(n_pix, n, protect=pinned_here):
             self._all_pixels.pop(key, None)
 
-    def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True):
+    def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True, mask_sigmoid=False):
         """plan.flow() eagerly, or -- use_graph -- as ONE hipGraph launch (captured at the second call with the same
         arguments; the per-launch event hooks of bench.py force the eager path)."""
         def eager():
             # (mode "TC" hands out dst = grid + flow only: the (2, H, W) flow map is then not written at all)
             plan.flow(iters, crop, oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"], wout=o["w"] if weighted else None,
-                      do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"))
+                      do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"), mask_sigmoid=mask_sigmoid)
         if not self.use_graph or plan.lookup_events is not None or plan.wh_events is not None or plan.conv_events is not None:
             return eager()
         graphs = plan.__dict__.setdefault("_graphs", {})
         region = plan.wh_region
         key = (iters, crop, oh, ow, weighted, do_sigmoid, want_flow, bool(defer_wh), o["flow"].data_ptr(),
-               region[0].data_ptr() if region is not None else 0)
+               region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid))
         g = graphs.get(key)
         if g is None:
             eager()                                        # this call's results; also the warm-up the capture needs
@@ -337,7 +337,7 @@ class RAFTWrapper:
 
     def compute_flow(self, src_img, dst_img, mode="TC", vis=False, src_img_identifier=None,
                      numpy_out=False, do_sigmoid=False, borrow=False, defer_weights=False, weight_region=False,
-                     src_is_previous_dst=False):
+                     src_is_previous_dst=False, visibility=False):
         """src_img / dst_img: (H, W, 3) uint8 BGR (numpy, or CUDA tensors already on the device).
         mode 'TC' -> (src_coords (2,HW) int64, dst_coords (2,HW) f32, weights (1,HW) f32 | None)
         mode 'flow' -> (flow (2,H,W), weights (1,H,W) | None).
@@ -350,7 +350,12 @@ class RAFTWrapper:
         defer_weights (extension, default off: 0; else the number of source pixels the caller will name; honoured for flows
         from the pinned source whose weight region is large against it, else ignored: check `weights_deferred` after the
         call): return the flow / correspondences with weights = None and evaluate the weight head later, in
-        finish_weights(), only where the caller then says it reads the weights."""
+        finish_weights(), only where the caller then says it reads the weights.
+        visibility (extension, default off; raft_type 'weighted_masked' only -- the tracker's visibility modes): the fourth value
+        is the visibility PROBABILITY, the sigmoid of the mask logits (taken in the mask's upsampling call, the do_sigmoid flag of
+        the weight channel), instead of the logits."""
+        if visibility and not self.masked:
+            raise ValueError("compute_flow(visibility=True) needs raft_type 'weighted_masked': no other type has a mask output")
         assert mode in ["flow", "TC"]
         assert src_img.shape == dst_img.shape
         if src_img_identifier is not None and self.masked:
@@ -430,7 +435,7 @@ class RAFTWrapper:
                                      and int(plan.wh_region[0].numel()) > self.defer_min_ratio * int(defer_weights))
         self._deferred = (plan, (top, left), oh, ow, o, bool(do_sigmoid)) if self.weights_deferred else None
         self._run_flow(plan, int(self.C.iters), (top, left), oh, ow, o, weighted, bool(do_sigmoid) and not post,
-                       defer_wh=self.weights_deferred, want_flow=(mode == "flow"))
+                       defer_wh=self.weights_deferred, want_flow=(mode == "flow"), mask_sigmoid=bool(visibility))
         if self.weights_deferred:
             return self._deliver(o, None, mode, oh, ow, numpy_out, borrow)
         logger.debug(f"flow enqueue time [s]: {float(timer() - start_time)}")

@@ -813,6 +813,35 @@ def tc_flags(dst, tmask_u8, pwmask_u8, h, wimg, check_dst, grid=None, out=None):
     return flags.view(torch.bool)
 
 
+VIS_MODES = {"gate": 1, "weight": 2}
+
+
+def tc_select_vis(dst, w, tmask_u8, pwmask_u8, h, wimg, check_dst, sobol_u, vis, vis_mode, vis_thr, ws, pa, pb, wout, count,
+                  grid=None):
+    """tc_select with the visibility probability vis (gh*gw floats; woft_tc_select_vis).  vis_mode 'gate': survivors also need
+    vis > vis_thr; 'weight': wout = w * vis (vis alone when w is None); None / 0: tc_select."""
+    n_draw = 0 if sobol_u is None else sobol_u.numel()
+    gh, gw = grid or (h, wimg)
+    assert dst.numel() == 2 * gh * gw and tmask_u8.numel() == h * wimg and (w is None or w.numel() == gh * gw)
+    assert vis is None or (vis.numel() == gh * gw and vis.dtype == torch.float32)
+    mode = VIS_MODES[vis_mode] if isinstance(vis_mode, str) else int(vis_mode or 0)
+    check(_lib.load().woft_tc_select_vis(ptr(dst), ptr(w), ptr(tmask_u8), ptr(pwmask_u8), gh, gw, h, wimg, int(check_dst),
+                                         ptr(sobol_u), n_draw, ptr(vis), mode, float(vis_thr), ptr(ws), ptr(pa), ptr(pb),
+                                         ptr(wout), pa.shape[0], ptr(count), stream_ptr()), "woft_tc_select_vis")
+
+
+def tc_flags_vis(dst, tmask_u8, pwmask_u8, h, wimg, check_dst, vis, vis_mode, vis_thr, grid=None, out=None):
+    """The keep rule of tc_select_vis alone -> bool tensor (gh*gw,) (woft_tc_flags_vis): gated in mode 'gate' only."""
+    gh, gw = grid or (h, wimg)
+    assert tmask_u8.numel() == h * wimg and (dst is None or dst.numel() == 2 * gh * gw)
+    assert vis is None or (vis.numel() == gh * gw and vis.dtype == torch.float32)
+    mode = VIS_MODES[vis_mode] if isinstance(vis_mode, str) else int(vis_mode or 0)
+    flags = out if out is not None else torch.empty(gh * gw, dtype=torch.uint8, device=tmask_u8.device)
+    check(_lib.load().woft_tc_flags_vis(ptr(dst), ptr(tmask_u8), ptr(pwmask_u8), gh, gw, h, wimg, int(check_dst), ptr(vis),
+                                        mode, float(vis_thr), ptr(flags), stream_ptr()), "woft_tc_flags_vis")
+    return flags.view(torch.bool)
+
+
 _HFIT_WS = {}
 
 

@@ -17,6 +17,11 @@ bit for bit):
     `select` kernel (woft_tc_flags), the surviving correspondences are handed to the config's own
     subsampler / estimator / re-detection callables exactly as TRK:141-162,196-199 hands them.
 
+Visibility (this project's own, no counterpart in TRK; DESIGN.md "Visibility mask in the tracker"): with the config key
+`visibility_mode` = 'gate' | 'weight' the flow config is a 'weighted_masked' one, and the MaskHead's per-pixel visibility probability
+prunes ('gate': p > `visibility_thr`) or scales ('weight': w * p) the correspondences inside the same select kernels, in both stages
+and both back ends.
+
 Frames live on the GPU (the two cv2.warpPerspective calls of TRK:89-95 are one HIP kernel) and the
 template's feature / context tensors are computed once (the flow provider pins the template).
 """
@@ -125,19 +130,46 @@ class _Fit(SimpleNamespace):
 class YAOFTrackerSingleControl:
     DEVICE = "cuda"                  # (a host-logic test may build the tracker around a stub flow provider on "cpu")
 
+    VISIBILITY_MODES = ("gate", "weight")
+
+    def _visibility_config(self):
+        """-> (mode | None, threshold as the fp32 value the kernels compare with).  Config keys `visibility_mode` (absent / falsy:
+        off) and `visibility_thr` (a float in (0, 1), default 0.5; read by 'gate' only)."""
+        C = self.C
+        mode = C.visibility_mode
+        if isinstance(mode, type(C)) or not mode:           # (key absent: an empty, falsy Config)
+            return None, 0.5
+        if mode not in self.VISIBILITY_MODES:
+            raise ValueError(f"visibility_mode {mode!r}: not one of {self.VISIBILITY_MODES} (or absent / None: the mask is not used)")
+        if C.flow_config.raft_type != "weighted_masked":
+            raise ValueError(f"visibility_mode {mode!r} needs a flow config with raft_type 'weighted_masked' (the MaskHead computes the "
+                             f"visibility); this one has {C.flow_config.raft_type!r}")
+        thr = C.visibility_thr
+        thr = 0.5 if (isinstance(thr, type(C)) or thr is None) else thr
+        try:
+            thr = float(thr)
+        except (TypeError, ValueError):
+            raise ValueError(f"visibility_thr {thr!r}: not a float in (0, 1)") from None
+        if not 0.0 < thr < 1.0:                              # (NaN fails both compares)
+            raise ValueError(f"visibility_thr {thr!r}: not a float in (0, 1)")
+        return mode, float(np.float32(thr))                  # rounded to fp32 once, here
+
     def __init__(self, config):
         self.C = config
-        if config.flow_config.raft_type == "weighted_masked":
+        self.visibility_mode, self.visibility_thr = self._visibility_config()
+        if config.flow_config.raft_type == "weighted_masked" and self.visibility_mode is None:
             # the tracker unpacks (src, dst, weights) from compute_flow (TRK:101,181); a 'weighted_masked' provider returns a fourth
-            # value, the visibility mask, which the tracker does not consume: refused here rather than at the first frame
+            # value, the visibility mask, which the tracker consumes only under a `visibility_mode`: refused here rather than at the first frame
             raise ValueError("the tracker takes a flow config with raft_type 'orig' or 'weighted'; 'weighted_masked' (MaskHead "
-                             "visibility mask) returns a mask the tracker does not consume")
+                             "visibility mask) returns a mask the tracker does not consume unless visibility_mode = 'gate' or "
+                             "'weight' is set")
         if self.C.subsampler_fn:
             self.C.subsampler_fn = make_forward_compatible(self.C.subsampler_fn)
         self.flower = config.flow_config.of_class(config.flow_config)
         self.device = self.DEVICE
         self._fused = self._fused_specs()
         self._sparse_weights = False
+        self.n_kept = None                # correspondences kept by the masks (and the gate) in the last solve
         self._replay = None
         self._announced = False
         self._local_chain = None          # (target frame object, frame number) of the last frame t-1 -> t flow
@@ -151,6 +183,14 @@ class YAOFTrackerSingleControl:
         config's estimator / subsampler / re-detection callables are the weighted LSq / IRLS estimators, the Sobol-n draw and
         the inlier-fraction test: tagged by woft_amd.presets, or found to BEHAVE as those (woft_amd.probe: reference-format
         configs define them inline, configs/..._wLSq.py:14-53); else None (callable back end: the config's own functions run)."""
+        self.solver_decision = None
+        spec = self._fused_specs_plain()
+        if self.visibility_mode is not None:
+            self.solver_decision += (f"; visibility {self.visibility_mode}"
+                                     + (f" (p > {self.visibility_thr:.9g})" if self.visibility_mode == "gate" else " (w * p)"))
+        return spec
+
+    def _fused_specs_plain(self):
         C = self.C
         self.solver_decision = "callable back end"
         v = C.device_solver
@@ -159,7 +199,9 @@ class YAOFTrackerSingleControl:
             return None
         if C.post_hoc_weights_postprocessing_fn or C.flow_numpy_out:
             return None
-        if not hasattr(self.flower, "pin_source") or self.flower.C.raft_type != "weighted":
+        if not hasattr(self.flower, "pin_source"):
+            return None
+        if self.flower.C.raft_type != ("weighted" if self.visibility_mode is None else "weighted_masked"):
             return None
         from .probe import solver_spec
         spec, how = solver_spec(C.H_estimator, C.subsampler_fn or None, C.redet_success_fn, device=self.device)
@@ -228,8 +270,10 @@ class YAOFTrackerSingleControl:
             # False / env WOFT_SPARSE_WH=0: on the whole mask region, as above).  Identical homographies (tested).
             v = self.C.sparse_weight_head
             on = (os.environ.get("WOFT_SPARSE_WH", "1") != "0") if (isinstance(v, type(self.C)) or v is None) else bool(v)
+            # (a visibility mode: the mask head runs on every pixel after the weight head and the provider defers nothing for a
+            #  'weighted_masked' network -- the non-deferred path)
             self._sparse_weights = bool(on and self._fused is not None and self._fused["n_draw"] and self._mask_weight_head()
-                                        and hasattr(self.flower, "finish_weights"))
+                                        and hasattr(self.flower, "finish_weights") and self.visibility_mode is None)
         self._set_pose(_EYE.copy(), good=True)
         self.prev_img, self.prev_img_identifier = img, img_identifier
         self.lost, self.N_lost = False, 0
@@ -276,6 +320,8 @@ class YAOFTrackerSingleControl:
 
         prewarp_H = self.last_good_H2init
         fit = self._global_stage(frame, prewarp_H)
+        if self.visibility_mode is not None:
+            meta.n_kept = self.n_kept                                # kept by the masks and the gate, template -> frame flow
         H_global = compose_H(prewarp_H, fit.H)
         meta.H_global_cur2init = H_global.copy()
         logger.debug(f"global_H_success: {fit.success}")
@@ -287,6 +333,8 @@ class YAOFTrackerSingleControl:
             H_cur2init = H_global
             if not self.C.no_local_H:
                 H_cur2init = meta.H_local_cur2init = self._local_stage(frame)
+                if self.visibility_mode is not None:
+                    meta.n_kept_local = self.n_kept                  # ... frame t-1 -> t flow (None: no flow ran)
         if debug:
             logger.debug("debug visualisation (TRK:210-264) needs the OpenCV GUI and is not part of the HIP path")
 
@@ -298,6 +346,8 @@ class YAOFTrackerSingleControl:
             meta.precision = getattr(self.flower, "precision", None)
             meta.precision_source = getattr(self.flower, "precision_source", None)
             meta.solver_decision = self.solver_decision
+            if self.visibility_mode is not None:      # (like n_kept: the field exists only with a mode)
+                meta.visibility_mode = self.visibility_mode
         k = self.C.downscale_inputs
         if k:                                                        # TRK:280-283
             H_cur2init = compose_H(np.diag([1.0 / k, 1.0 / k, 1.0]), H_cur2init, np.diag([float(k), float(k), 1.0]))
@@ -318,8 +368,8 @@ class YAOFTrackerSingleControl:
 
     # ---- the two flow stages ------------------------------------------------------------------------
     def _flow(self, src, dst, src_is_previous_dst=False):
-        """-> (grid coords (2, n) int64, target coords (2, n) f32, weights (1, n) f32 | None, (gh, gw)); borrowed
-        buffers of the provider: consumed before the next flow."""
+        """-> (grid coords (2, n) int64, target coords (2, n) f32, weights (1, n) f32 | None, visibility probabilities (1, n) f32 |
+        None (a visibility mode only), (gh, gw)); borrowed buffers of the provider: consumed before the next flow."""
         # (borrowed buffers, and -- only for THIS caller -- weights restricted to the region pinned in init(): a direct
         #  compute_flow() call by anybody else returns the full weight map, as the reference's does)
         kw = {"borrow": True, "weight_region": True} if hasattr(self.flower, "pin_source") else {}
@@ -329,10 +379,18 @@ class YAOFTrackerSingleControl:
             kw["defer_weights"] = int(self._fused["n_draw"])
         if src_is_previous_dst and "borrow" in kw:
             kw["src_is_previous_dst"] = True
-        src_xy, dst_xy, w = self.flower.compute_flow(src, dst, mode="TC", vis=False, src_img_identifier=None,
-                                                     do_sigmoid=True, **kw)
+        self.n_kept = None
+        p = None
+        if self.visibility_mode is not None:
+            # the tracker's own request: the fourth value is the visibility probability (the sigmoid of the mask logits, taken in the
+            # mask's upsampling call) -- compute_flow called by anybody else returns the logits, as the reference's does
+            src_xy, dst_xy, w, p = self.flower.compute_flow(src, dst, mode="TC", vis=False, src_img_identifier=None,
+                                                            do_sigmoid=True, visibility=True, **kw)
+        else:
+            src_xy, dst_xy, w = self.flower.compute_flow(src, dst, mode="TC", vis=False, src_img_identifier=None,
+                                                         do_sigmoid=True, **kw)
         s = getattr(self.flower, "last_flow_shape", None)
-        return src_xy, dst_xy, w, ((s["H"], s["W"]) if s else None)
+        return src_xy, dst_xy, w, p, ((s["H"], s["W"]) if s else None)
 
     def _global_stage(self, frame, prewarp_H):
         """Template -> frame pre-warped by the last good homography (TRK:85-162).  Kept: correspondences that start
@@ -352,9 +410,9 @@ class YAOFTrackerSingleControl:
             ops.warp_perspective_u8(frame, prewarp_H, prewarped, valid)
         if self.C.do_not_mask_TCs_by_prewarped:
             valid = None
-        src_xy, dst_xy, w, grid = self._flow(self.template_img, prewarped)
+        src_xy, dst_xy, w, p, grid = self._flow(self.template_img, prewarped)
         return self._solve(src_xy, dst_xy, w, grid, frame.shape[:2], self._template_mask_u8, valid, bounds=True,
-                           judge=True)
+                           judge=True, vis=p)
 
     def _local_stage(self, frame):
         """Frame t-1 -> frame t, chained onto the previous pose (TRK:171-207).  Kept: correspondences that start in
@@ -364,7 +422,7 @@ class YAOFTrackerSingleControl:
         # then takes its feature map from that flow instead of encoding the same image again (identical values)
         chained = (self._local_chain is not None and self._local_chain[0] is self.prev_img and self._local_chain[1] == self._n_tracked - 1
                    and os.environ.get("WOFT_LOCAL_REUSE", "1") != "0")
-        src_xy, dst_xy, w, grid = self._flow(self.prev_img, frame, src_is_previous_dst=chained)
+        src_xy, dst_xy, w, p, grid = self._flow(self.prev_img, frame, src_is_previous_dst=chained)
         self._local_chain = (frame, self._n_tracked)
         if np.array_equal(self.prev_H2init, _EYE):
             prev_mask = self._template_mask_u8
@@ -373,7 +431,7 @@ class YAOFTrackerSingleControl:
             ops.warp_perspective_u8(self._template_mask_u8, np.linalg.inv(self.prev_H2init), prev_mask, None,
                                     nearest=True)
         try:
-            fit = self._solve(src_xy, dst_xy, w, grid, frame.shape[:2], prev_mask, None, bounds=False, judge=False)
+            fit = self._solve(src_xy, dst_xy, w, grid, frame.shape[:2], prev_mask, None, bounds=False, judge=False, vis=p)
             if not np.all(np.isfinite(fit.H)):
                 raise FloatingPointError("singular homography system")
             return compose_H(fit.H, self.prev_H2init)
@@ -382,20 +440,37 @@ class YAOFTrackerSingleControl:
             return self.prev_H2init
 
     # ---- the solver ---------------------------------------------------------------------------------
-    def _solve(self, src_xy, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, judge):
-        """Prune the dense field and fit H (target -> source coordinates); judge: also run the re-detection test."""
+    def _solve(self, src_xy, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, judge, vis=None):
+        """Prune the dense field and fit H (target -> source coordinates); judge: also run the re-detection test.
+        vis (a visibility mode): the probabilities on the flow grid, applied inside the keep rule / the weights by either back end."""
         Hh, Ww = frame_hw
         grid = grid or (Hh, Ww)
-        if self._fused is not None:
-            return self._solve_device(dst_xy, w, grid, (Hh, Ww), src_mask_u8, dst_valid_u8, bounds)
-        return self._solve_callables(src_xy, dst_xy, w, grid, (Hh, Ww), src_mask_u8, dst_valid_u8, bounds, judge)
+        try:
+            if self._fused is not None:
+                return self._solve_device(dst_xy, w, grid, (Hh, Ww), src_mask_u8, dst_valid_u8, bounds, vis)
+            return self._solve_callables(src_xy, dst_xy, w, grid, (Hh, Ww), src_mask_u8, dst_valid_u8, bounds, judge, vis)
+        except AssertionError:
+            # Too few correspondences for a fit (least_squares_H.py:162).  Without a visibility mode this is the reference's
+            # behaviour: the global stage lets it out of track(), the local stage keeps the previous pose.  A gate is MEANT to empty
+            # the set under occlusion: the global stage then reports a failed re-detection (H = identity: the pre-warp's pose) and
+            # the frame is lost, as any other frame whose global fit is rejected.
+            if self.visibility_mode is None or not judge or self.n_kept is None or self.n_kept >= 4:
+                raise
+            logger.debug(f"global stage: {self.n_kept} correspondences after the visibility {self.visibility_mode}: no fit")
+            return _Fit(H=_EYE.copy(), success=False)
 
-    def _solve_device(self, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds):
+    def _solve_device(self, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, vis=None):
         F, b = self._fused, self._fused_buffers(grid[0] * grid[1])
         res = b["res"]
         ires = res.view(torch.int32)
         weighted = F.get("weighted", True)
-        if w is None and getattr(self.flower, "weights_deferred", False):
+        if vis is not None:
+            # (an unweighted estimator under 'weight': the output weight is p itself and the fit is called weighted)
+            ops.tc_select_vis(dst_xy, w if weighted else None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds,
+                              F["sobol_u"], vis, self.visibility_mode, self.visibility_thr, b["ws"], b["pa"], b["pb"], b["w"],
+                              ires[12:14], grid=grid)
+            weighted = weighted or self.visibility_mode == "weight"
+        elif w is None and getattr(self.flower, "weights_deferred", False):
             # The correspondences the fit will read are decided by the flow alone (masks, bounds, Sobol draw): select them
             # first, then let the provider evaluate the weight head on the windows under THEIR upsampling support only and
             # hand back the weights of exactly these pixels (exact: the head has no cross-pixel terms) -- identical fit.
@@ -430,6 +505,7 @@ class YAOFTrackerSingleControl:
         self._host_ev.synchronize()
         self.host_wait_s += time.perf_counter() - t0      # (bench: wall time minus this = the launch loop's host time per frame)
         ih = host.view(torch.int32)
+        self.n_kept = int(ih[13])                                    # (count[1] of the selection: part of the same read)
         if int(ih[10]) == 1:
             raise AssertionError(torch.Size([1, int(ih[12]), 2]))    # least_squares_H.py:162 (fewer than 4 points; TRS: than 2)
         verdict = F.get("const_verdict")       # (a re-detection test that is `return True` / `return False`: the reference's ablations)
@@ -437,15 +513,26 @@ class YAOFTrackerSingleControl:
             verdict = bool(np.float32(host[9]) > np.float32(F["min_frac"]))
         return _Fit(H=host[0:9].numpy().astype(np.float64).reshape(3, 3), success=bool(verdict))   # (astype: a copy; the verdict in float32, as torch compares a float32 mean with a Python float)
 
-    def _solve_callables(self, src_xy, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, judge):
+    def _solve_callables(self, src_xy, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, judge, vis=None):
         C = self.C
         post = None
         if C.post_hoc_weights_postprocessing_fn:
             post = self.flower.postprocess_weights(w.clone(), C.post_hoc_weights_postprocessing_fn)
-        keep = ops.tc_flags(dst_xy if bounds else None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds,
-                            grid=grid)
+        if vis is None:
+            keep = ops.tc_flags(dst_xy if bounds else None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds,
+                                grid=grid)
+        else:
+            keep = ops.tc_flags_vis(dst_xy if bounds else None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds,
+                                    vis, self.visibility_mode, self.visibility_thr, grid=grid)
         pick = lambda t: None if t is None else t[:, keep]
         src_xy, dst_xy, w, post = pick(src_xy), pick(dst_xy), pick(w), pick(post)
+        if vis is not None:
+            self.n_kept = int(src_xy.shape[1])
+            if self.n_kept == 0:                                     # (nothing to hand to the config's callables)
+                raise AssertionError(torch.Size([1, 0, 2]))
+            if self.visibility_mode == "weight":                     # w * p in fp32 on the compacted set; p alone without weights
+                pk = vis.reshape(1, -1)[:, keep]
+                w = pk if w is None else w * pk
         if judge:
             src_xy = src_xy.float()                                  # TRK:131 (global stage); the local stage hands the
                                                                      # subsampler the int64 grid coordinates (TRK:186-193)
@@ -539,8 +626,8 @@ class WOFTWindow(YAOFTrackerSingleControl):
             ops.warp_perspective_window_u8(frame, prewarp_H, rect, prewarped, valid)
         if self.C.do_not_mask_TCs_by_prewarped:
             valid = None
-        src_xy, dst_xy, w, grid = self._flow(self._template_crop, prewarped)
-        fit = self._solve(src_xy, dst_xy, w, grid, (rows, cols), self._template_mask_crop, valid, bounds=True, judge=True)
+        src_xy, dst_xy, w, p, grid = self._flow(self._template_crop, prewarped)
+        fit = self._solve(src_xy, dst_xy, w, grid, (rows, cols), self._template_mask_crop, valid, bounds=True, judge=True, vis=p)
         fit.H = window.H_undo_crop(self.search_bbox, fit.H)
         return fit
 
@@ -572,9 +659,9 @@ class WOFTWindow(YAOFTrackerSingleControl):
         prev_win = ops.crop_u8(_device_u8(self.prev_img), rect)
         cur_win = ops.crop_u8(frame, rect)
         mask_win = ops.crop_u8(prev_mask, rect)
-        src_xy, dst_xy, w, grid = self._flow(prev_win, cur_win)
+        src_xy, dst_xy, w, p, grid = self._flow(prev_win, cur_win)
         try:                                                         # (the estimator only, as in the parent: anything else is an error)
-            fit = self._solve(src_xy, dst_xy, w, grid, (rect[2], rect[3]), mask_win, None, bounds=False, judge=False)
+            fit = self._solve(src_xy, dst_xy, w, grid, (rect[2], rect[3]), mask_win, None, bounds=False, judge=False, vis=p)
             if not np.all(np.isfinite(fit.H)):
                 raise FloatingPointError("singular homography system")
             return compose_H(window.H_undo_crop(box, fit.H), self.prev_H2init)

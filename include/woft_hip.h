@@ -307,6 +307,22 @@ int woft_coords_update(float* coords1, const float* delta, int32_t ld_delta, int
                        float* flow4, float* flow_cat, int32_t ld_cat, void* stream);
 int woft_coords_init(float* coords1, int32_t hf, int32_t wf, float* flow4, float* flow_cat,
                      int32_t ld_cat, void* stream);
+/* Warm start (csrc/warm.hip; weighted_raft.py:184,223-224 and raft.py: coords1 = coords1 + flow_init).
+ * woft_coords_init_flow: woft_coords_init with coords1 = grid + flow_init.  flow_init: planar [2][hf][wf] fp32 (x plane, y
+ * plane) in 1/8-resolution pixels of the padded image, what the reference network's forward() receives.  flow4 / flow_cat
+ * (optional, woft_coords_update's layout) receive flow_init itself, bit for bit -- not (grid + flow_init) - grid.
+ * -1 (before any launch) on a NULL coords1 / flow_init or hf, wf <= 0. */
+int woft_coords_init_flow(float* coords1, const float* flow_init, int32_t hf, int32_t wf, float* flow4, float* flow_cat,
+                          int32_t ld_cat, void* stream);
+/* forward_interpolate (raft_core/utils/utils.py:28-56), the routine that carries a flow from one video frame pair to the
+ * next.  flow, out: planar [2][hf][wf] fp32, distinct buffers.  Point i (row-major, at (x0, y0)) lands at
+ * (x1, y1) = (x0 + dx, y0 + dy), computed in fp64, and is valid iff 0 < x1 < wf and 0 < y1 < hf (strictly).  Every grid
+ * cell receives (dx, dy) of the valid point whose landing position is nearest to it: squared Euclidean distance
+ * ddx*ddx + ddy*ddy in fp64 without contraction; of equally near points the one with the LOWEST index (the reference's
+ * scipy griddata leaves ties unspecified).  Deviation: without any valid point the reference raises; here out is all zeros.
+ * Exhaustive search (hf*wf candidates per cell), deterministic: no atomics, fixed order.
+ * -1 (before any launch) on a NULL pointer, flow == out, hf, wf <= 0 or hf*wf > 2^30. */
+int woft_forward_interpolate(const float* flow, int32_t hf, int32_t wf, float* out, void* stream);
 
 /* Weight-head glue (weighted_raft.py:258-279, 347-384).
  * woft_colsum: total[c] = sum_q f[q][c] in fp64 (ws: [n_part][c] doubles).

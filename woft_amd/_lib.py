@@ -78,6 +78,8 @@ _SIGS = {
     "woft_tile_rows": (i32, [vp, i32, i32, i32, vp, vp]),
     "woft_coords_update": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, vp]),
     "woft_coords_init": (i32, [vp, i32, i32, vp, vp, i32, vp]),
+    "woft_coords_init_flow": (i32, [vp, vp, i32, i32, vp, vp, i32, vp]),
+    "woft_forward_interpolate": (i32, [vp, i32, i32, vp, vp]),
     "woft_colsum": (i32, [vp, i64, i32, vp, i32, vp, vp]),
     "woft_wh_pack": (i32, [vp, i32, vp, i32, vp, f32, i64, i32, vp, vp, vp]),
     "woft_wh_conv0": (i32, [vp, i32, vp, i64, i32, vp, vp, vp, vp, vp]),

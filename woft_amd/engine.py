@@ -337,6 +337,8 @@ class _Plan:
         self.fh = new_act(1, hf, wf, 128 if sp.small else 256, zero=True)
         self.fh_part = None        # flow head folded into one conv launch: per-pixel partial products of its second conv
         self.delta = new_act(1, hf, wf, 2, cs=4, zero=True)
+        # warm start: the caller's flow_init is copied here, so that a captured graph reads it from a fixed address
+        self.flow_init = z(2, hf, wf)
         if self.otf:
             self.lookup = ops.make_lookup_otf_params(self.f1s, self.f2s, self.dims, hf, wf, sp.fdim, self.coords,
                                                      self.corr.t, sp.radius, 3 if x3 else (0 if self.prec == "fp32" else 1))
@@ -754,15 +756,32 @@ class _Plan:
             self.run(self.prog_gate_bias)
         return reused
 
+    def set_flow_init(self, flow_init):
+        """Copy the caller's initial flow -- (2, hf, wf), 1/8-resolution pixels of the padded image, any float dtype, either
+        device -- into the plan's own buffer; flow(..., flow_init=True) then starts from it."""
+        if tuple(flow_init.shape) != (2, self.hf, self.wf):
+            raise ValueError(f"flow_init must have shape (2, {self.hf}, {self.wf}) for a {self.hp} x {self.wp} padded input, "
+                             f"got {tuple(flow_init.shape)}")
+        self.flow_init.copy_(flow_init, non_blocking=True)
+
+    def flow_low(self):
+        """The final coords1 - coords0 of the last flow() as a new (2, hf, wf) tensor (the reference network's flow_low,
+        weighted_raft.py:240-255), read from flow4 -- what the last coordinate update wrote."""
+        return self.flow4.t[:, :2].t().reshape(2, self.hf, self.wf).contiguous()
+
     def flow(self, iters, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False, trace=None, defer_wh=False,
-             mout=None, mask_sigmoid=False):
+             mout=None, mask_sigmoid=False, flow_init=None):
         """Target features -> volume -> `iters` refinements -> full-resolution outputs.
         defer_wh (full weighted model with a weight region set): stop before the weight head -- flow_up / dst are final,
         wout is NOT written -- and let finish_weights() evaluate the head where the caller then says it reads the weights.
         mout (engine built with mask_head): receives the upsampled visibility-mask logits (h*w floats, cropped like wout, never
         passed through a sigmoid); the head runs after the weight head whether or not mout is given.
         mask_sigmoid (the tracker's visibility request only): mout receives the sigmoid of those logits instead -- the do_sigmoid
-        flag the upsampling kernels already have for the weight channel."""
+        flag the upsampling kernels already have for the weight channel.
+        flow_init (weighted_raft.py:184,223-224: coords1 = coords1 + flow_init): None = start from zero flow; a (2, hf, wf)
+        tensor = copied into the plan's buffer first (set_flow_init); True = the buffer as it stands.  The first iteration's
+        motion encoder reads it as the flow, the later coordinate updates write coords1 - coords0 as ever.  With a trace, the
+        trace is also called once as trace(plan, -1) after the initialisation, before the first iteration."""
         e, sp = self.eng, self.eng.spec
         if iters < 1:
             raise ValueError("iters must be >= 1")
@@ -770,7 +789,14 @@ class _Plan:
         self.run(self.prog_volume)
         self.target_valid = True                             # (level-0 target map + operand now belong to the image in img[1])
         off = sp.flow_off
-        ops.coords_init(self.coords, self.hf, self.wf, self.flow4.t, self.xbuf.t[:, off:], self.xbuf.cs)
+        if flow_init is None:
+            ops.coords_init(self.coords, self.hf, self.wf, self.flow4.t, self.xbuf.t[:, off:], self.xbuf.cs)
+        else:
+            if flow_init is not True:
+                self.set_flow_init(flow_init)
+            ops.coords_init_flow(self.coords, self.flow_init, self.hf, self.wf, self.flow4.t, self.xbuf.t[:, off:], self.xbuf.cs)
+            if trace is not None:
+                trace(self, -1)
         last = getattr(self, "prog_iter_last", None) if iters > 1 else None
         fold = self._fold if trace is None else None        # (a trace reads the coordinates after every iteration)
         for it in range(iters):

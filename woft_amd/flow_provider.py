@@ -191,19 +191,23 @@ class RAFTWrapper:
         for key in self._recent_pixels.touch(n_pix, n, protect=pinned_here):
             self._all_pixels.pop(key, None)
 
-    def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True, mask_sigmoid=False):
+    def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True, mask_sigmoid=False,
+                  has_init=False):
         """plan.flow() eagerly, or -- use_graph -- as ONE hipGraph launch (captured at the second call with the same
-        arguments; the per-launch event hooks of bench.py force the eager path)."""
+        arguments; the per-launch event hooks of bench.py force the eager path).
+        has_init: start from the plan's flow_init buffer (filled by the caller BEFORE this call: a replayed graph reads the
+        buffer's fixed address, the copy into it is not part of the graph)."""
         def eager():
             # (mode "TC" hands out dst = grid + flow only: the (2, H, W) flow map is then not written at all)
             plan.flow(iters, crop, oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"], wout=o["w"] if weighted else None,
-                      do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"), mask_sigmoid=mask_sigmoid)
+                      do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"), mask_sigmoid=mask_sigmoid,
+                      flow_init=True if has_init else None)
         if not self.use_graph or plan.lookup_events is not None or plan.wh_events is not None or plan.conv_events is not None:
             return eager()
         graphs = plan.__dict__.setdefault("_graphs", {})
         region = plan.wh_region
         key = (iters, crop, oh, ow, weighted, do_sigmoid, want_flow, bool(defer_wh), o["flow"].data_ptr(),
-               region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid))
+               region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid), bool(has_init))
         g = graphs.get(key)
         if g is None:
             eager()                                        # this call's results; also the warm-up the capture needs
@@ -335,9 +339,36 @@ class RAFTWrapper:
         #  round-4 advisor finding: a shared grid that a caller offsets or sorts would corrupt every later call at this size)
         return (own(o["src"]), own(o["dst"]), (own(weights) if weights is not None else None)) + extra
 
+    @staticmethod
+    def _as_flow_init(flow_init, hp, wp):
+        """The caller's flow_init -> a float32 (2, hp/8, wp/8) torch tensor (its own device), or ValueError."""
+        want = (2, hp // 8, wp // 8)
+        t = flow_init if isinstance(flow_init, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow_init))
+        if t.dim() == 4 and t.shape[0] == 1:
+            t = t[0]
+        if tuple(t.shape) != want or not t.is_floating_point():
+            raise ValueError(f"flow_init must be a float array of shape {want} or {(1,) + want} (1/8-resolution pixels of the "
+                             f"{hp} x {wp} padded image), got {tuple(flow_init.shape)} {flow_init.dtype}")
+        return t.detach().to(torch.float32)
+
+    def flow_key(self, src_img):
+        """(buffer set, hp, wp, pad_top, pad_left) a compute_flow(src_img, ...) call would run in -- `last_flow_key` of a call
+        that did: two flows with equal keys have 1/8-resolution grids of the same geometry (the tracker's warm start)."""
+        hp, wp, top, left = _pad_geometry(src_img.shape[0], src_img.shape[1], self.C.padding_mode)[:4]
+        return (0 if (src_img is self._pinned or self._pinned is None) else 1, hp, wp, top, left)
+
+    def flow_low(self, copy=True):
+        """After any COMPUTED flow (not a cache hit): its final 1/8-resolution flow coords1 - coords0, (2, hp/8, wp/8) fp32 on
+        the device, in 1/8-resolution pixels of the padded image -- the reference network's flow_low (weighted_raft.py:240-255),
+        which its wrapper drops.  copy=False: a view of the engine's buffer, valid until the next flow in the same buffer set."""
+        plan = getattr(self, "_low_plan", None)
+        if plan is None:
+            raise RuntimeError("flow_low(): no flow has been computed yet")
+        return plan.flow_low() if copy else plan.flow4.t[:, :2].t().reshape(2, plan.hf, plan.wf)
+
     def compute_flow(self, src_img, dst_img, mode="TC", vis=False, src_img_identifier=None,
                      numpy_out=False, do_sigmoid=False, borrow=False, defer_weights=False, weight_region=False,
-                     src_is_previous_dst=False, visibility=False):
+                     src_is_previous_dst=False, visibility=False, flow_init=None, iters=None):
         """src_img / dst_img: (H, W, 3) uint8 BGR (numpy, or CUDA tensors already on the device).
         mode 'TC' -> (src_coords (2,HW) int64, dst_coords (2,HW) f32, weights (1,HW) f32 | None)
         mode 'flow' -> (flow (2,H,W), weights (1,H,W) | None).
@@ -353,7 +384,14 @@ class RAFTWrapper:
         finish_weights(), only where the caller then says it reads the weights.
         visibility (extension, default off; raft_type 'weighted_masked' only -- the tracker's visibility modes): the fourth value
         is the visibility PROBABILITY, the sigmoid of the mask logits (taken in the mask's upsampling call, the do_sigmoid flag of
-        the weight channel), instead of the logits."""
+        the weight channel), instead of the logits.
+        flow_init (extension, default off: None; the reference NETWORK's argument, weighted_raft.py:184,223-224, which the reference's
+        wrapper never passes): the refinement starts from coords1 = grid + flow_init instead of the identity grid.  (2, hp/8, wp/8)
+        or (1, 2, hp/8, wp/8) -- 1/8-resolution pixels of the PADDED image (hp, wp), what the network receives -- as a torch
+        tensor (either device) or a numpy float array; any other shape raises a ValueError that names the expected one.  Ignored
+        on a flow-cache hit (the cache bypasses the network).  flow_low() after a call returns what the next call of a video
+        would pass through woft_amd.warm.forward_interpolate.
+        iters (extension, default None = the flow config's `iters`): the number of refinement iterations of THIS call."""
         if visibility and not self.masked:
             raise ValueError("compute_flow(visibility=True) needs raft_type 'weighted_masked': no other type has a mask output")
         assert mode in ["flow", "TC"]
@@ -381,6 +419,11 @@ class RAFTWrapper:
         pinned_here = src_img is self._pinned
         slot = 0 if (pinned_here or self._pinned is None) else 1
         plan = self.engine.plan(hp, wp, slot)
+        if flow_init is not None:
+            flow_init = self._as_flow_init(flow_init, hp, wp)
+        n_iters = int(self.C.iters) if iters is None else int(iters)
+        if n_iters < 1:
+            raise ValueError("iters must be >= 1")
         self._touch_plan((hp, wp) if slot == 0 else (hp, wp, slot), (oh, ow), plan.P, pinned_here)
         start_time = timer()
 
@@ -434,8 +477,12 @@ class RAFTWrapper:
                                      and mode == "TC" and not numpy_out
                                      and int(plan.wh_region[0].numel()) > self.defer_min_ratio * int(defer_weights))
         self._deferred = (plan, (top, left), oh, ow, o, bool(do_sigmoid)) if self.weights_deferred else None
-        self._run_flow(plan, int(self.C.iters), (top, left), oh, ow, o, weighted, bool(do_sigmoid) and not post,
-                       defer_wh=self.weights_deferred, want_flow=(mode == "flow"), mask_sigmoid=bool(visibility))
+        if flow_init is not None:
+            plan.set_flow_init(flow_init)                   # (outside any graph: see _run_flow)
+        self._run_flow(plan, n_iters, (top, left), oh, ow, o, weighted, bool(do_sigmoid) and not post,
+                       defer_wh=self.weights_deferred, want_flow=(mode == "flow"), mask_sigmoid=bool(visibility),
+                       has_init=flow_init is not None)
+        self._low_plan, self.last_flow_key = plan, (slot,) + key
         if self.weights_deferred:
             return self._deliver(o, None, mode, oh, ow, numpy_out, borrow)
         logger.debug(f"flow enqueue time [s]: {float(timer() - start_time)}")

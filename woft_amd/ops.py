@@ -678,6 +678,27 @@ def coords_init(coords, hf, wf, flow4=None, flow_cat=None, ld_cat=0):
           "woft_coords_init")
 
 
+def coords_init_flow(coords, flow_init, hf, wf, flow4=None, flow_cat=None, ld_cat=0):
+    """coords = grid + flow_init, flow4 / flow_cat = flow_init itself (woft_coords_init_flow).  flow_init: contiguous (2, hf, wf)
+    fp32 device tensor, 1/8-resolution pixels of the padded image."""
+    assert flow_init.dtype == torch.float32 and flow_init.is_contiguous() and tuple(flow_init.shape) == (2, hf, wf)
+    check(_lib.load().woft_coords_init_flow(ptr(coords), ptr(flow_init), hf, wf, ptr(flow4), ptr(flow_cat), ld_cat,
+                                            stream_ptr()), "woft_coords_init_flow")
+
+
+def forward_interpolate(flow, out=None):
+    """forward_interpolate (raft_core/utils/utils.py:28-56) of a contiguous (2, hf, wf) fp32 device tensor -> `out` (a new
+    tensor by default; never `flow` itself): woft_forward_interpolate -- exact nearest valid landing point per cell, lowest
+    point index on a tie, zeros without any valid point."""
+    assert flow.dtype == torch.float32 and flow.is_contiguous() and flow.dim() == 3 and flow.shape[0] == 2
+    if out is None:
+        out = torch.empty_like(flow)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == flow.shape
+    check(_lib.load().woft_forward_interpolate(ptr(flow), flow.shape[1], flow.shape[2], ptr(out), stream_ptr()),
+          "woft_forward_interpolate")
+    return out
+
+
 def coords_update(coords, delta, ld_delta, wf, flow4=None, flow_cat=None, ld_cat=0):
     check(_lib.load().woft_coords_update(ptr(coords), ptr(delta), ld_delta, wf, coords.shape[0], ptr(flow4),
                                          ptr(flow_cat), ld_cat, stream_ptr()), "woft_coords_update")

@@ -22,6 +22,11 @@ Visibility (this project's own, no counterpart in TRK; DESIGN.md "Visibility mas
 prunes ('gate': p > `visibility_thr`) or scales ('weight': w * p) the correspondences inside the same select kernels, in both stages
 and both back ends.
 
+Warm start (this project's own, no counterpart in TRK; DESIGN.md "Warm start"): with the config key `warm_start_local` the
+frame t-1 -> t flow of the second and later frames of a run of lost frames starts from the forward-interpolated 1/8-resolution
+flow of the previous one (RAFT's video warm start, raft_core/utils/utils.py:28-56) instead of from zero; `warm_start_iters`
+sets the iteration count of those flows.  `meta.local_warm_started` says which kind a lost frame's flow was.
+
 Frames live on the GPU (the two cv2.warpPerspective calls of TRK:89-95 are one HIP kernel) and the
 template's feature / context tensors are computed once (the flow provider pins the template).
 """
@@ -154,8 +159,24 @@ class YAOFTrackerSingleControl:
             raise ValueError(f"visibility_thr {thr!r}: not a float in (0, 1)")
         return mode, float(np.float32(thr))                  # rounded to fp32 once, here
 
+    def _warm_start_config(self):
+        """-> (on, iterations of a warm-started flow | None = the flow config's).  Config keys `warm_start_local` (absent / falsy:
+        off) and `warm_start_iters` (an integer >= 1; absent / None: the flow config's `iters`)."""
+        C = self.C
+        on = C.warm_start_local
+        on = False if isinstance(on, type(C)) else bool(on)
+        n = C.warm_start_iters
+        if isinstance(n, type(C)) or n is None:
+            return on, None
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"warm_start_iters {n!r}: not an integer >= 1")
+        return on, int(n)
+
     def __init__(self, config):
         self.C = config
+        self.warm_start_local, self.warm_start_iters = self._warm_start_config()
+        self.local_warm_started = False   # whether the last frame t-1 -> t flow started from a carried flow
+        self._warm = None                 # (flow_low of the last frame t-1 -> t flow, its provider flow key): the carried flow
         self.visibility_mode, self.visibility_thr = self._visibility_config()
         if config.flow_config.raft_type == "weighted_masked" and self.visibility_mode is None:
             # the tracker unpacks (src, dst, weights) from compute_flow (TRK:101,181); a 'weighted_masked' provider returns a fourth
@@ -251,6 +272,7 @@ class YAOFTrackerSingleControl:
         self.template_img = img
         self.np_template_mask = mask_np
         self._local_chain = None
+        self._warm = None
         self.template_mask = torch.from_numpy(inside).to(self.device)
         self._template_mask_u8 = torch.from_numpy(inside.astype(np.uint8) * 255).to(self.device)
         if hasattr(self.flower, "pin_source"):
@@ -303,6 +325,7 @@ class YAOFTrackerSingleControl:
             input_img = ops.resize_by_factor_u8(_device_u8(input_img), self.C.downscale_inputs)
         if self._replay is not None:                                 # TRK:63-76
             meta, self._replay = self._replay, None
+            self._warm = None
             H_cur2init = meta.estim_H_current2template
             self.lost, self.N_lost = False, 0
             self.prev_H2init = self.last_good_H2init = H_cur2init
@@ -327,12 +350,14 @@ class YAOFTrackerSingleControl:
         logger.debug(f"global_H_success: {fit.success}")
         if fit.success:
             self.lost, self.N_lost = False, 0
+            self._warm = None                                        # (a re-detected frame ends the run: nothing to carry)
             H_cur2init = H_global
         else:
             self.lost, self.N_lost = True, self.N_lost + 1
             H_cur2init = H_global
             if not self.C.no_local_H:
                 H_cur2init = meta.H_local_cur2init = self._local_stage(frame)
+                meta.local_warm_started = self.local_warm_started    # (False without `warm_start_local`)
                 if self.visibility_mode is not None:
                     meta.n_kept_local = self.n_kept                  # ... frame t-1 -> t flow (None: no flow ran)
         if debug:
@@ -367,7 +392,7 @@ class YAOFTrackerSingleControl:
             self.last_good_H2init = H.copy()
 
     # ---- the two flow stages ------------------------------------------------------------------------
-    def _flow(self, src, dst, src_is_previous_dst=False):
+    def _flow(self, src, dst, src_is_previous_dst=False, flow_init=None, iters=None):
         """-> (grid coords (2, n) int64, target coords (2, n) f32, weights (1, n) f32 | None, visibility probabilities (1, n) f32 |
         None (a visibility mode only), (gh, gw)); borrowed buffers of the provider: consumed before the next flow."""
         # (borrowed buffers, and -- only for THIS caller -- weights restricted to the region pinned in init(): a direct
@@ -379,6 +404,10 @@ class YAOFTrackerSingleControl:
             kw["defer_weights"] = int(self._fused["n_draw"])
         if src_is_previous_dst and "borrow" in kw:
             kw["src_is_previous_dst"] = True
+        if flow_init is not None:                                    # (warm start: the local stage only)
+            kw["flow_init"] = flow_init
+            if iters is not None:
+                kw["iters"] = iters
         self.n_kept = None
         p = None
         if self.visibility_mode is not None:
@@ -422,8 +451,21 @@ class YAOFTrackerSingleControl:
         # then takes its feature map from that flow instead of encoding the same image again (identical values)
         chained = (self._local_chain is not None and self._local_chain[0] is self.prev_img and self._local_chain[1] == self._n_tracked - 1
                    and os.environ.get("WOFT_LOCAL_REUSE", "1") != "0")
-        src_xy, dst_xy, w, p, grid = self._flow(self.prev_img, frame, src_is_previous_dst=chained)
+        init, self.local_warm_started = None, False
+        if self.warm_start_local:
+            # warm start: the previous track() ran this stage too, its flow belonged to frames (t-2, t-1) -- `chained`, whatever
+            # WOFT_LOCAL_REUSE says -- and ran in the buffer set and padding geometry this one will (equal flow keys)
+            ran = (self._local_chain is not None and self._local_chain[0] is self.prev_img
+                   and self._local_chain[1] == self._n_tracked - 1)
+            if ran and self._warm is not None and self._warm[1] == self.flower.flow_key(self.prev_img):
+                from .warm import forward_interpolate
+                init = forward_interpolate(self._warm[0])
+            self.local_warm_started = init is not None
+        src_xy, dst_xy, w, p, grid = self._flow(self.prev_img, frame, src_is_previous_dst=chained, flow_init=init,
+                                                iters=self.warm_start_iters)
         self._local_chain = (frame, self._n_tracked)
+        if self.warm_start_local:
+            self._warm = (self.flower.flow_low(), self.flower.last_flow_key)
         if np.array_equal(self.prev_H2init, _EYE):
             prev_mask = self._template_mask_u8
         else:
@@ -565,6 +607,11 @@ class WOFTWindow(YAOFTrackerSingleControl):
     MIN_FLOW_SIDE = 16                # a local window cut smaller than this by the frame edge: no flow, previous pose kept
 
     def __init__(self, config):
+        v = config.warm_start_local
+        if not isinstance(v, type(config)) and v:
+            # (the local windows move with the object: the flow of one window is not on the grid of the next)
+            raise NotImplementedError("warm_start_local is not provided by the search-window tracker: its frame t-1 -> t flows run "
+                                      "on a window that follows the object, so consecutive flows do not share a grid")
         super().__init__(config)
         from collections import OrderedDict
         self._fb_cache = OrderedDict()

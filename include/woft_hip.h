@@ -465,6 +465,19 @@ int woft_tc_flags_vis(const float* dst, const uint8_t* tmask, const uint8_t* pwm
 int64_t woft_hfit_ws_bytes(void);
 int woft_hfit(const float* pa, const float* pb, const float* w, int32_t n_max, const int32_t* count,
               int32_t reweight, float huber_k, int32_t n_irls, void* ws, float* Hout, int32_t* status, void* stream);
+/* `batch` independent fits of at most WOFT_HFIT_SINGLE_MAX correspondences each in ONE launch: workgroup b fits element b
+ * with the one-workgroup code of woft_hfit (ws == NULL) -- same arithmetic, same summation order, same status codes, so
+ * Hout[b] / status[b] are bit-identical to woft_hfit on element b alone.  pa, pb: [batch][n_max][2], w: [batch][n_max] or
+ * NULL (all ones), counts: [batch] device int32 or NULL; element b uses n = min(counts[b], n_max) (n_max without counts) and
+ * reads only the first n rows of its slice.  Hout: [batch][9], status: [batch].  reweight, huber_k and n_irls are shared by
+ * the batch.  An element that fails (fewer than 4 points, singular or non-finite system) writes its own NaN Hout and status
+ * and nothing else.  WOFT_EINVAL before any launch on a NULL pa / pb / Hout / status, batch < 1, batch >
+ * WOFT_HFIT_BATCH_MAX (one workgroup per element in grid dimension x: larger batches are split by the caller), n_max < 1
+ * and n_max > WOFT_HFIT_SINGLE_MAX (larger problems stay with woft_hfit's streaming path, one element at a time). */
+#define WOFT_HFIT_BATCH_MAX 65535
+int woft_hfit_batched(const float* pa, const float* pb, const float* w, int32_t batch, int32_t n_max,
+                      const int32_t* counts, int32_t reweight, float huber_k, int32_t n_irls, float* Hout,
+                      int32_t* status, void* stream);
 /* ONE re-weighted solve of the same system, for arbitrary `reweighting_fn` callables (least_squares_H.py:280,323-337):
  * rew: [2n] per-row re-weights sqrt(reweighting_fn(residual)) of the previous step or NULL (= ones, first step);
  * first != 0 (re)computes the normalisation into ws; res (may be NULL): [2n] residuals A x - b of THIS step's solution

@@ -57,9 +57,17 @@ def _fit(points1, points2, weights, reweight, huber_k, n_irls):
         dev = torch.device("cuda")
         out = _fit(points1.to(dev), points2.to(dev), None if weights is None else weights.to(dev), reweight, huber_k, n_irls)
         return out.to(points1.device)
-    B = points1.shape[0]
+    B, N = points1.shape[0], points1.shape[1]
     out = torch.empty(B, 3, 3, dtype=torch.float32, device=points1.device)
     status = torch.zeros(B, dtype=torch.int32, device=points1.device)
+    if B > 1 and N <= ops.HFIT_SINGLE_MAX:
+        # one launch, one workgroup per element (woft_hfit_batched): the bits of the per-element loop below
+        pa, pb = points1.float().contiguous(), points2.float().contiguous()
+        w = weights.float().reshape(B, -1).contiguous() if weights is not None else None
+        if w is not None and w.shape[1] != N:
+            raise AssertionError(weights.shape)
+        ops.hfit_batched(pa, pb, w, out, status, reweight=reweight, huber_k=huber_k, n_irls=n_irls)
+        return out
     for b in range(B):
         pa, pb, w = _operands(points1, points2, weights, b)
         ops.hfit(pa, pb, w, out[b].view(9), status[b:b + 1], reweight=reweight, huber_k=huber_k, n_irls=n_irls)
@@ -192,6 +200,53 @@ def torch_proj_errors(GT_H, pts_A, pts_B):
     z = proj[:, 2:3]
     scale = torch.where(z.abs() > 1e-8, 1.0 / (z + 1e-8), torch.ones_like(z))
     return torch.sqrt(torch.square(scale * proj[:, :2] - pts_B).sum(dim=1))
+
+
+# ---- projection-error helpers (least_squares_H.py:400-505) -----------------------------------------------------------------
+# Plain torch ops on the caller's device, batched; not a hot path, no kernel.  The homogeneous conversions follow the rule
+# torch_proj_errors uses above (kornia's convert_points_from_homogeneous: scale = 1 / (z + 1e-8) where |z| > 1e-8, else 1).
+# They are differentiable as torch ops are, but the HIP estimators above are FORWARD ONLY: an H that came out of
+# find_homography_* carries no autograd graph, so a training loss built from these helpers does not reach the
+# correspondences through the fit.
+def torch_e2p(pts):
+    """Euclidean -> homogeneous: (B, 2, N) -> (B, 3, N), a row of ones appended (least_squares_H.py:440-449)."""
+    return torch.cat([pts, torch.ones_like(pts[:, :1])], dim=1)
+
+
+def torch_p2e(homo):
+    """Homogeneous -> Euclidean: (B, 3, N) -> (B, 2, N) (least_squares_H.py:452-461)."""
+    z = homo[:, -1:]
+    scale = torch.where(z.abs() > 1e-8, 1.0 / (z + 1e-8), torch.ones_like(z))
+    return scale * homo[:, :-1]
+
+
+def torch_H_proj(H, pts):
+    """Points warped by homographies: H (B, 3, 3), pts (B, 2, N) -> (B, 2, N) (least_squares_H.py:464-471)."""
+    return torch_p2e(torch.matmul(H, torch_e2p(pts)))
+
+
+def torch_reproj_errors(GT_H, est_H, pts_A):
+    """L2 distance between pts_A and inv(est_H) * GT_H * pts_A: forward by the ground truth, back by the estimate
+    (least_squares_H.py:400-419; the training configs' loss_fn).  GT_H, est_H (B, 3, 3); pts_A (B, 2, N) -> (B, N).
+    Forward only with respect to the HIP estimators (see above)."""
+    reproj = torch_p2e(torch.linalg.inv(est_H) @ torch.matmul(GT_H, torch_e2p(pts_A)))
+    return torch.sqrt(torch.square(reproj - pts_A).sum(dim=1))
+
+
+def torch_proj_diff_errors(GT_H, est_H, pts_A):
+    """L2 distance between GT_H * pts_A and est_H * pts_A (least_squares_H.py:422-437).
+    GT_H, est_H (B, 3, 3); pts_A (B, 2, N) -> (B, N)."""
+    return torch.sqrt(torch.square(torch_H_proj(GT_H, pts_A) - torch_H_proj(est_H, pts_A)).sum(dim=1))
+
+
+def reproj_errors(GT_H, est_H, pts_A, mean=True):
+    """The numpy form of torch_reproj_errors for one homography pair (least_squares_H.py:492-502): GT_H, est_H (3, 3),
+    pts_A (2, N); the composed homography is normalised to h33 = 1 and the division by z is plain.  -> the mean error as a
+    float, or the (N,) errors when mean is False."""
+    Hfb = compose_H(GT_H, np.linalg.inv(est_H))
+    p = np.matmul(Hfb, np.vstack((pts_A, np.ones(pts_A.shape[1]))))
+    err = np.sqrt(np.square(p[:-1] / p[-1:] - pts_A).sum(axis=0))
+    return float(err.mean()) if mean else err
 
 
 def compose_H(*Hs):

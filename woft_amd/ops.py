@@ -888,6 +888,23 @@ def hfit(pa, pb, w, Hout, status, count=None, reweight=0, huber_k=1.0, n_irls=0,
                                 ptr(ws), ptr(Hout), ptr(status), stream_ptr()), "woft_hfit")
 
 
+HFIT_BATCH_MAX = 65535
+
+
+def hfit_batched(pa, pb, w, Hout, status, counts=None, reweight=0, huber_k=1.0, n_irls=0):
+    """B independent fits of N <= HFIT_SINGLE_MAX correspondences each in one launch (woft_hfit_batched): pa, pb (B, N, 2),
+    w (B, N) or None, Hout (B, 9) or (B, 3, 3), status (B,) int32, counts (B,) int32 or None -- all contiguous, fp32, on one
+    device.  Element b gets the bits of hfit() on element b alone.  More than HFIT_BATCH_MAX elements: one launch per
+    HFIT_BATCH_MAX of them."""
+    B, n = pa.shape[0], pa.shape[1]
+    fn = _lib.load().woft_hfit_batched
+    for lo in range(0, B, HFIT_BATCH_MAX):
+        hi = min(B, lo + HFIT_BATCH_MAX)
+        check(fn(ptr(pa[lo:hi]), ptr(pb[lo:hi]), ptr(w[lo:hi]) if w is not None else None, hi - lo, n,
+                 ptr(counts[lo:hi]) if counts is not None else None, reweight, float(huber_k), n_irls, ptr(Hout[lo:hi]),
+                 ptr(status[lo:hi]), stream_ptr()), "woft_hfit_batched")
+
+
 def hfit_step(pa, pb, w, rew, first, res, Hout, status, ws=None):
     """One re-weighted solve with externally supplied row re-weights; residuals of its solution -> res."""
     ws = ws if ws is not None else hfit_ws(pa.device)

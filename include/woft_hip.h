@@ -478,6 +478,24 @@ int woft_hfit(const float* pa, const float* pb, const float* w, int32_t n_max, c
 int woft_hfit_batched(const float* pa, const float* pb, const float* w, int32_t batch, int32_t n_max,
                       const int32_t* counts, int32_t reweight, float huber_k, int32_t n_irls, float* Hout,
                       int32_t* status, void* stream);
+/* Backward of the plain weighted fit (reweight = 0, n_irls = 0; utils/least_squares_H.py:142-210, which the reference's
+ * training configs differentiate with torch autograd through torch.linalg.qr): given gH: [batch][9], the gradient of a
+ * scalar with respect to the Hout of woft_hfit_batched / woft_hfit on the same pa, pb, w, counts, writes the gradients with
+ * respect to the points, gpa, gpb: [batch][n_max][2], and the weights, gw: [batch][n_max].  ONE launch, workgroup b handles
+ * element b alone; nothing is saved by the forward: the workgroup recomputes the Hartley statistics, the fp32 rows, the fp64
+ * Gram matrix and its Cholesky factor exactly as the forward does and carries the adjoint in fp64 (one adjoint solve with
+ * the same factor, then one pass over the correspondences).  No global scratch, no atomics, every sum
+ * in a fixed order: deterministic, and element b gets the bits of a batch = 1 call on element b alone.  Any of gpa, gpb, gw
+ * may be NULL: that gradient is neither computed nor stored and the others keep their bits; w == NULL means unit weights
+ * and gw must then be NULL.  Rows at and beyond n = min(counts[b], n_max) are never read and their gradient slots are
+ * written as exact zeros.  status (may be NULL): [batch], the forward's codes.  An element whose forward fails (status 1 or
+ * 2) gets ZERO gradients in all of its slots -- not the NaN torch autograd would return: the forward's NaN Hout already
+ * reports the failure, and one degenerate sample must not poison an optimiser step whose loss masks it out.  WOFT_EINVAL
+ * before any launch on a NULL pa / pb / gH, all three outputs NULL, gw with a NULL w, batch < 1, batch >
+ * WOFT_HFIT_BATCH_MAX, n_max < 1 and n_max > WOFT_HFIT_SINGLE_MAX (the streaming fit has no backward). */
+int woft_hfit_batched_bwd(const float* pa, const float* pb, const float* w, int32_t batch, int32_t n_max,
+                          const int32_t* counts, const float* gH, float* gpa, float* gpb, float* gw, int32_t* status,
+                          void* stream);
 /* ONE re-weighted solve of the same system, for arbitrary `reweighting_fn` callables (least_squares_H.py:280,323-337):
  * rew: [2n] per-row re-weights sqrt(reweighting_fn(residual)) of the previous step or NULL (= ones, first step);
  * first != 0 (re)computes the normalisation into ws; res (may be NULL): [2n] residuals A x - b of THIS step's solution

@@ -103,6 +103,7 @@ _SIGS = {
     "woft_hfit_ws_bytes": (i64, []),
     "woft_hfit": (i32, [vp, vp, vp, i32, vp, i32, f32, i32, vp, vp, vp, vp]),
     "woft_hfit_batched": (i32, [vp, vp, vp, i32, i32, vp, i32, f32, i32, vp, vp, vp]),
+    "woft_hfit_batched_bwd": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "woft_hfit_step": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "woft_inlier_frac": (i32, [vp, vp, i32, vp, vp, f32, vp, vp]),
     "woft_ransac_ws_bytes": (i64, [i32, i32]),

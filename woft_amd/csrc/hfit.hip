@@ -256,6 +256,337 @@ __global__ __launch_bounds__(HT) void hfit_batched_kernel(const float* __restric
              status + b);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Backward of the plain weighted fit (reweight = 0, one solve): gradients of a scalar with respect to pa, pb and w, given its
+// gradient with respect to the Hout of hfit_one.  Nothing is saved by the forward; one workgroup recomputes the statistics, the
+// rows and the Gram matrix with the forward's own instruction sequence (same s1, s2, means and Gram bits, hence the same
+// status), keeps the solution in fp64 and carries the adjoint in fp64 (stages a - e).
+// ------------------------------------------------------------------------------------------------------------------
+
+// Cholesky factor of G[0:8,0:8] (gram: [9][9]) as a packed lower triangle, L[i (i + 1) / 2 + j].  The operations and their order
+// are those of the one-lane solve in hfit_one; every index is a constant after unrolling, so L lives in registers (no scratch).
+// A non-positive or NaN pivot makes the result false (the forward's status 2); the factor is then not to be used.
+__device__ __forceinline__ bool chol8_factor(const double* gram, double (&L)[36]) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = gram[i * 9 + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+            if (i == j) {
+                ok = ok && (s > 0.0);
+                L[i * (i + 1) / 2 + i] = sqrt(s);
+            } else {
+                L[i * (i + 1) / 2 + j] = s / L[j * (j + 1) / 2 + j];
+            }
+        }
+    }
+    return ok;
+}
+
+// rhs <- (L L^T)^-1 rhs, fp64 in and out (the forward rounds its solution to fp32; the backward keeps all 53 bits)
+__device__ __forceinline__ void chol8_solve_f64(const double (&L)[36], double (&rhs)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        double s = rhs[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= L[i * (i + 1) / 2 + k] * rhs[k];
+        rhs[i] = s / L[i * (i + 1) / 2 + i];
+    }
+#pragma unroll
+    for (int i = 7; i >= 0; --i) {
+        double s = rhs[i];
+#pragma unroll
+        for (int k = i + 1; k < 8; ++k) s -= L[k * (k + 1) / 2 + i] * rhs[k];
+        rhs[i] = s / L[i * (i + 1) / 2 + i];
+    }
+}
+
+// exact zeros into rows [from, n_max) of the gradient slices that exist
+__device__ __forceinline__ void bwd_zero_rows(float* __restrict__ gpa, float* __restrict__ gpb, float* __restrict__ gw, int from,
+                                              int n_max) {
+    for (int i = from + (int)threadIdx.x; i < n_max; i += HT) {
+        if (gpa != nullptr) ((float2*)gpa)[i] = make_float2(0.f, 0.f);
+        if (gpb != nullptr) ((float2*)gpb)[i] = make_float2(0.f, 0.f);
+        if (gw != nullptr) gw[i] = 0.f;
+    }
+}
+
+// One element, one workgroup of HT threads, n <= n_max <= 2 HT (a thread owns the correspondences threadIdx.x and
+// threadIdx.x + HT and keeps their normalised-coordinate gradients in registers across the reductions of stage e).
+// Static LDS: red 10 368 B + tot 360 B + gram 648 B + bw 192 B + 4 B.
+__device__ __forceinline__ void hfit_bwd_one(const float* __restrict__ pa, const float* __restrict__ pb,
+                                             const float* __restrict__ w, int n, int n_max, const float* __restrict__ gout,
+                                             float* __restrict__ gpa, float* __restrict__ gpb, float* __restrict__ gw,
+                                             int* __restrict__ status) {
+    __shared__ double red[(HT / 64) * 81];
+    __shared__ double tot[NG];
+    __shared__ double gram[81];
+    __shared__ double bw[24];          // x[8] | u[8] | gT1 (00, 11, 02, 12) | gT2 (00, 11, 02, 12)
+    __shared__ int fail_s;
+    if (n < 4) {
+        bwd_zero_rows(gpa, gpb, gw, 0, n_max);
+        if (threadIdx.x == 0 && status != nullptr) status[0] = 1;
+        return;
+    }
+
+    // ---- Hartley statistics: the forward's code, the forward's bits ------------------------------
+    double s4[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += HT) {
+        s4[0] += (double)pa[2 * i];
+        s4[1] += (double)pa[2 * i + 1];
+        s4[2] += (double)pb[2 * i];
+        s4[3] += (double)pb[2 * i + 1];
+    }
+    block_sum<4>(s4, red, tot);
+    const float m1x = (float)(tot[0] / n), m1y = (float)(tot[1] / n);
+    const float m2x = (float)(tot[2] / n), m2y = (float)(tot[3] / n);
+    __syncthreads();
+    double d2[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += HT) {
+        const float ax = pa[2 * i] - m1x, ay = pa[2 * i + 1] - m1y;
+        const float bx = pb[2 * i] - m2x, by = pb[2 * i + 1] - m2y;
+        d2[0] += (double)sqrtf(ax * ax + ay * ay);
+        d2[1] += (double)sqrtf(bx * bx + by * by);
+    }
+    block_sum<2>(d2, red, tot);
+    const float den1 = (float)(tot[0] / n) + 1e-8f, den2 = (float)(tot[1] / n) + 1e-8f;      // mean distance + eps
+    const float s1 = sqrtf(2.0f) / den1;
+    const float s2 = sqrtf(2.0f) / den2;
+    const float t1x = -s1 * m1x, t1y = -s1 * m1y, t2x = -s2 * m2x, t2y = -s2 * m2y;
+    __syncthreads();
+
+    // ---- Gram matrix on the fp64 matrix cores, as the forward's first (only) solve ----------------
+    typedef double f64x4 __attribute__((ext_vector_type(4)));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ec = lane & 15, ek = lane >> 4;
+    {
+        f64x4 g4 = {0.0, 0.0, 0.0, 0.0};
+        for (int base = wave * 2; base < n; base += (HT / 64) * 2) {
+            const int i = base + (ek >> 1);
+            double val = 0.0;
+            if (i < n && ec < 9) {
+                const float x1 = s1 * pa[2 * i] + t1x, y1 = s1 * pa[2 * i + 1] + t1y;
+                const float x2 = s2 * pb[2 * i] + t2x, y2 = s2 * pb[2 * i + 1] + t2y;
+                const float wv = (w != nullptr) ? w[i] : 1.f;
+                float rx[9], ry[9];
+                build_rows(x1, y1, x2, y2, wv, rx, ry);
+                float e = 0.f;
+#pragma unroll
+                for (int k = 0; k < 9; ++k)
+                    if (k == ec) e = (ek & 1) ? ry[k] : rx[k];
+                val = (double)e;
+            }
+            g4 = __builtin_amdgcn_mfma_f64_16x16x4f64(val, val, g4, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = ek + 4 * r;
+            if (row < 9 && ec < 9) red[wave * 81 + row * 9 + ec] = g4[r];
+        }
+        __syncthreads();
+        if (threadIdx.x < 81) {
+            double sacc = 0.0;
+            for (int wv = 0; wv < HT / 64; ++wv) sacc += red[wv * 81 + threadIdx.x];
+            gram[threadIdx.x] = sacc;
+        }
+        __syncthreads();
+    }
+
+    // ---- one lane: solve, stages a - c -----------------------------------------------------------
+    if (threadIdx.x == 0) {
+        double L[36];
+        const bool ok = chol8_factor(gram, L);
+        fail_s = ok ? 0 : 1;
+        if (status != nullptr) status[0] = ok ? 0 : 2;
+        if (ok) {
+            double x[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = gram[k * 9 + 8];
+            chol8_solve_f64(L, x);
+            // T1 = [[sa, 0, ta], [0, sa, tb], [0, 0, 1]], T2^-1 = [[i2, 0, tc], [0, i2, td], [0, 0, 1]]: the products below are
+            // the 3x3 ones of stage (b) with the structural zeros left out (a lane has 128 registers)
+            const double hn[9] = {x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], 1.0};
+            const double sa = s1, ta = t1x, tb = t1y;
+            const double i2 = 1.0 / (double)s2, tc = -(double)t2x * i2, td = -(double)t2y * i2;
+            double P[9], hh[9], gH[9], Q[9];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {                           // P = Hn T1
+                P[3 * r] = sa * hn[3 * r];
+                P[3 * r + 1] = sa * hn[3 * r + 1];
+                P[3 * r + 2] = ta * hn[3 * r] + tb * hn[3 * r + 1] + hn[3 * r + 2];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {                           // H = T2^-1 P
+                hh[c] = i2 * P[c] + tc * P[6 + c];
+                hh[3 + c] = i2 * P[3 + c] + td * P[6 + c];
+                hh[6 + c] = P[6 + c];
+            }
+            // (a) out = H / (H33 + eps)
+            const double den = hh[8] + 1e-8;
+            double dot = 0.0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const double g = (double)gout[k];
+                gH[k] = g / den;
+                dot += g * hh[k];
+            }
+            gH[8] -= dot / (den * den);
+            // (b) with Q = T2^-T gH:  gHn = Q T1^T,  gT1 = (T2^-1 Hn)^T gH = Hn^T Q,
+            //     gT2 = -T2^-T (gH (Hn T1)^T) T2^-T = -Q (T2^-1 Hn T1)^T = -Q H^T
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                Q[c] = i2 * gH[c];
+                Q[3 + c] = i2 * gH[3 + c];
+                Q[6 + c] = tc * gH[c] + td * gH[3 + c] + gH[6 + c];
+            }
+            // (c) adjoint solve G u = gx (the first 8 entries of gHn) with the same factor
+            double u[8];
+            u[0] = sa * Q[0] + ta * Q[2]; u[1] = sa * Q[1] + tb * Q[2]; u[2] = Q[2];
+            u[3] = sa * Q[3] + ta * Q[5]; u[4] = sa * Q[4] + tb * Q[5]; u[5] = Q[5];
+            u[6] = sa * Q[6] + ta * Q[8]; u[7] = sa * Q[7] + tb * Q[8];
+            chol8_solve_f64(L, u);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                bw[k] = x[k];
+                bw[8 + k] = u[k];
+            }
+            bw[16] = hn[0] * Q[0] + hn[3] * Q[3] + hn[6] * Q[6];          // gT1[0][0]
+            bw[17] = hn[1] * Q[1] + hn[4] * Q[4] + hn[7] * Q[7];          // gT1[1][1]
+            bw[18] = hn[0] * Q[2] + hn[3] * Q[5] + hn[6] * Q[8];          // gT1[0][2]
+            bw[19] = hn[1] * Q[2] + hn[4] * Q[5] + hn[7] * Q[8];          // gT1[1][2]
+            bw[20] = -(Q[0] * hh[0] + Q[1] * hh[1] + Q[2] * hh[2]);       // gT2[0][0]
+            bw[21] = -(Q[3] * hh[3] + Q[4] * hh[4] + Q[5] * hh[5]);       // gT2[1][1]
+            bw[22] = -(Q[0] * hh[6] + Q[1] * hh[7] + Q[2] * hh[8]);       // gT2[0][2]
+            bw[23] = -(Q[3] * hh[6] + Q[4] * hh[7] + Q[5] * hh[8]);       // gT2[1][2]
+        }
+    }
+    __syncthreads();
+    if (fail_s) {
+        bwd_zero_rows(gpa, gpb, gw, 0, n_max);
+        return;
+    }
+
+    // ---- (d) per correspondence on the weighted rows ---------------------------------------------
+    const bool want_pts = (gpa != nullptr) || (gpb != nullptr);
+    double gpn[2][4];                       // gradient of (x1, y1, x2, y2) of this thread's two correspondences
+    double cen[2][4];                       // p - m of the same
+    double dots[2] = {0.0, 0.0};            // sum of gpn . (p - m), per point set
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int i = (int)threadIdx.x + j * HT;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gpn[j][k] = cen[j][k] = 0.0;
+        if (i < n) {
+            const float pax = pa[2 * i], pay = pa[2 * i + 1], pbx = pb[2 * i], pby = pb[2 * i + 1];
+            const float x1 = s1 * pax + t1x, y1 = s1 * pay + t1y;
+            const float x2 = s2 * pbx + t2x, y2 = s2 * pby + t2y;
+            const float wv = (w != nullptr) ? w[i] : 1.f;
+            float rx[9], ry[9], ax[9], ay[9];
+            build_rows(x1, y1, x2, y2, wv, rx, ry);          // weighted rows [A~ b~]
+            build_rows(x1, y1, x2, y2, 1.f, ax, ay);         // the rows themselves [A b]
+            double rX = -(double)rx[8], rY = -(double)ry[8], vX = 0.0, vY = 0.0;      // r = A~ x - b~, v = A~ u
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                rX += (double)rx[k] * bw[k];
+                rY += (double)ry[k] * bw[k];
+                vX += (double)rx[k] * bw[8 + k];
+                vY += (double)ry[k] * bw[8 + k];
+            }
+            if (gw != nullptr) {
+                // gw = sum over the two rows of (gA~_row . A_row + gb~_row b_row), gA~_row = -(r u^T + v x^T), gb~_row = v
+                double aUx = 0.0, aXx = 0.0, aUy = 0.0, aXy = 0.0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    aUx += (double)ax[k] * bw[8 + k];
+                    aXx += (double)ax[k] * bw[k];
+                    aUy += (double)ay[k] * bw[8 + k];
+                    aXy += (double)ay[k] * bw[k];
+                }
+                gw[i] = (float)((vX * (double)ax[8] - (rX * aUx + vX * aXx)) + (vY * (double)ay[8] - (rY * aUy + vY * aXy)));
+            }
+            if (want_pts) {
+                // only columns 3, 4, 6, 7 of the x-row, 0, 1, 6, 7 of the y-row and b depend on the points
+                const double W = (double)wv, X1 = x1, Y1 = y1, X2 = x2, Y2 = y2;
+                const double gAx3 = -(rX * bw[11] + vX * bw[3]), gAx4 = -(rX * bw[12] + vX * bw[4]);
+                const double gAx6 = -(rX * bw[14] + vX * bw[6]), gAx7 = -(rX * bw[15] + vX * bw[7]);
+                const double gAy0 = -(rY * bw[8] + vY * bw[0]), gAy1 = -(rY * bw[9] + vY * bw[1]);
+                const double gAy6 = -(rY * bw[14] + vY * bw[6]), gAy7 = -(rY * bw[15] + vY * bw[7]);
+                gpn[j][0] = W * (-gAx3 + Y2 * gAx6 + gAy0 - X2 * gAy6);
+                gpn[j][1] = W * (-gAx4 + Y2 * gAx7 + gAy1 - X2 * gAy7);
+                gpn[j][2] = W * (-X1 * gAy6 - Y1 * gAy7 + vY);
+                gpn[j][3] = W * (X1 * gAx6 + Y1 * gAx7 - vX);
+                cen[j][0] = (double)pax - (double)m1x;
+                cen[j][1] = (double)pay - (double)m1y;
+                cen[j][2] = (double)pbx - (double)m2x;
+                cen[j][3] = (double)pby - (double)m2y;
+                dots[0] += gpn[j][0] * cen[j][0] + gpn[j][1] * cen[j][1];
+                dots[1] += gpn[j][2] * cen[j][2] + gpn[j][3] * cen[j][3];
+            }
+        }
+    }
+    bwd_zero_rows(nullptr, nullptr, gw, n, n_max);
+    if (!want_pts) return;
+
+    // ---- (e) through p_n = s (p - m) and T, both point sets --------------------------------------
+    block_sum<2>(dots, red, tot);
+    const double S1 = s1, S2 = s2;
+    const double gs1 = tot[0] + bw[16] + bw[17] - bw[18] * (double)m1x - bw[19] * (double)m1y;
+    const double gs2 = tot[1] + bw[20] + bw[21] - bw[22] * (double)m2x - bw[23] * (double)m2y;
+    const double gdb1 = (-gs1 * S1 / (double)den1) / n, gdb2 = (-gs2 * S2 / (double)den2) / n;      // g_dbar / n
+    __syncthreads();
+    double gd[2][4];
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int i = (int)threadIdx.x + j * HT;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gd[j][k] = 0.0;
+        if (i < n) {
+            const double da = sqrt(cen[j][0] * cen[j][0] + cen[j][1] * cen[j][1]);
+            const double db = sqrt(cen[j][2] * cen[j][2] + cen[j][3] * cen[j][3]);
+            const double ia = (da > 0.0) ? 1.0 / da : 0.0, ib = (db > 0.0) ? 1.0 / db : 0.0;   // unit vector 0 at distance 0
+            gd[j][0] = S1 * gpn[j][0] + gdb1 * (cen[j][0] * ia);
+            gd[j][1] = S1 * gpn[j][1] + gdb1 * (cen[j][1] * ia);
+            gd[j][2] = S2 * gpn[j][2] + gdb2 * (cen[j][2] * ib);
+            gd[j][3] = S2 * gpn[j][3] + gdb2 * (cen[j][3] * ib);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sums[k] += gd[j][k];
+        }
+    }
+    block_sum<4>(sums, red, tot);
+    // gp_i = gd_i - mean(gd) + (-s gT02, -s gT12) / n
+    const double o0 = (-tot[0] - S1 * bw[18]) / n, o1 = (-tot[1] - S1 * bw[19]) / n;
+    const double o2 = (-tot[2] - S2 * bw[22]) / n, o3 = (-tot[3] - S2 * bw[23]) / n;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int i = (int)threadIdx.x + j * HT;
+        if (i < n) {
+            if (gpa != nullptr) ((float2*)gpa)[i] = make_float2((float)(gd[j][0] + o0), (float)(gd[j][1] + o1));
+            if (gpb != nullptr) ((float2*)gpb)[i] = make_float2((float)(gd[j][2] + o2), (float)(gd[j][3] + o3));
+        }
+    }
+    bwd_zero_rows(gpa, gpb, nullptr, n, n_max);
+}
+
+// Workgroup b differentiates element b of a [batch][n_max] problem: reads rows [0, n_b) of its own slices and gH[b], writes
+// its own gradient slices and status[b] only.
+__global__ __launch_bounds__(HT) void hfit_batched_bwd_kernel(const float* __restrict__ pa, const float* __restrict__ pb,
+                                                              const float* __restrict__ w, int n_max,
+                                                              const int* __restrict__ counts, const float* __restrict__ gH,
+                                                              float* __restrict__ gpa, float* __restrict__ gpb,
+                                                              float* __restrict__ gw, int* __restrict__ status) {
+    const int b = blockIdx.x;
+    const int64_t off = (int64_t)b * n_max;
+    int n = n_max;
+    if (counts != nullptr) n = min(counts[b], n_max);
+    hfit_bwd_one(pa + 2 * off, pb + 2 * off, (w != nullptr) ? w + off : nullptr, n, n_max, gH + 9 * b,
+                 (gpa != nullptr) ? gpa + 2 * off : nullptr, (gpb != nullptr) ? gpb + 2 * off : nullptr,
+                 (gw != nullptr) ? gw + off : nullptr, (status != nullptr) ? status + b : nullptr);
+}
+
 // frac[0] = mean_i( || proj(H, A_i) - B_i || <= thr )
 __global__ __launch_bounds__(HT) void inlier_frac_kernel(const float* __restrict__ pa, const float* __restrict__ pb,
                                                          int n_max, const int* __restrict__ count,
@@ -653,6 +984,18 @@ extern "C" int woft_hfit_batched(const float* pa, const float* pb, const float* 
         return WOFT_EINVAL;
     hipLaunchKernelGGL(hfit_batched_kernel, dim3(batch), dim3(HT), 0, (hipStream_t)stream, pa, pb, w, n_max, counts, reweight,
                        huber_k, n_irls + 1, Hout, status);
+    return woft_launch_status();
+}
+
+extern "C" int woft_hfit_batched_bwd(const float* pa, const float* pb, const float* w, int32_t batch, int32_t n_max,
+                                     const int32_t* counts, const float* gH, float* gpa, float* gpb, float* gw,
+                                     int32_t* status, void* stream) {
+    if (!pa || !pb || !gH || (!gpa && !gpb && !gw) || (gw && !w) || batch < 1 || batch > WOFT_HFIT_BATCH_MAX || n_max < 1 ||
+        n_max > WOFT_HFIT_SINGLE_MAX)
+        return WOFT_EINVAL;
+    static_assert(WOFT_HFIT_SINGLE_MAX <= 2 * HT, "hfit_bwd_one keeps two correspondences per thread");
+    hipLaunchKernelGGL(hfit_batched_bwd_kernel, dim3(batch), dim3(HT), 0, (hipStream_t)stream, pa, pb, w, n_max, counts, gH, gpa,
+                       gpb, gw, status);
     return woft_launch_status();
 }
 

@@ -49,14 +49,8 @@ def _operands(points1, points2, weights, b):
     return pa, pb, w
 
 
-def _fit(points1, points2, weights, reweight, huber_k, n_irls):
-    if not points1.is_cuda:
-        # The reference's QR estimator takes tensors of any device (least_squares_H.py:142-210 has no device check; only the IRLS
-        # variant asserts, :292-293 -- and so does find_homography_IRLSq_QR below).  Host tensors are copied to the HIP device,
-        # fitted by the same kernel and the result handed back on the caller's device: there is no CPU solver here.
-        dev = torch.device("cuda")
-        out = _fit(points1.to(dev), points2.to(dev), None if weights is None else weights.to(dev), reweight, huber_k, n_irls)
-        return out.to(points1.device)
+def _launch(points1, points2, weights, reweight, huber_k, n_irls):
+    """The fit of device tensors: one woft_hfit_batched launch for B > 1 and N <= HFIT_SINGLE_MAX, else woft_hfit per element."""
     B, N = points1.shape[0], points1.shape[1]
     out = torch.empty(B, 3, 3, dtype=torch.float32, device=points1.device)
     status = torch.zeros(B, dtype=torch.int32, device=points1.device)
@@ -72,6 +66,61 @@ def _fit(points1, points2, weights, reweight, huber_k, n_irls):
         pa, pb, w = _operands(points1, points2, weights, b)
         ops.hfit(pa, pb, w, out[b].view(9), status[b:b + 1], reweight=reweight, huber_k=huber_k, n_irls=n_irls)
     return out
+
+
+class _WeightedLSqFit(torch.autograd.Function):
+    """The plain weighted fit with a backward (csrc/hfit.hip hfit_batched_bwd_kernel).  forward makes the
+    launches of _launch, so H has the bits of the call without grad; backward is one launch that recomputes the small solve and
+    writes the gradients of the inputs that need one.  Once differentiable.  An element whose fit failed (NaN H) gets ZERO
+    gradients, where torch autograd through a QR would give NaN: one degenerate sample must not poison an optimiser step whose
+    loss masks it out."""
+
+    @staticmethod
+    def forward(ctx, points1, points2, weights):
+        ctx.save_for_backward(points1, points2, weights)
+        return _launch(points1.detach(), points2.detach(), None if weights is None else weights.detach(), 0, 0.0, 0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        points1, points2, weights = ctx.saved_tensors
+        B, N = points1.shape[0], points1.shape[1]
+        pa, pb = points1.float().contiguous(), points2.float().contiguous()
+        w = weights.float().reshape(B, -1).contiguous() if weights is not None else None
+        gH = grad_output.to(torch.float32).contiguous().view(B, 9)
+        need = ctx.needs_input_grad
+        gpa = torch.empty_like(pa) if need[0] else None
+        gpb = torch.empty_like(pb) if need[1] else None
+        gw = torch.empty_like(w) if (need[2] and w is not None) else None
+        ops.hfit_batched_bwd(pa, pb, w, gH, gpa, gpb, gw)
+        return (None if gpa is None else gpa.to(points1.dtype).view(points1.shape),
+                None if gpb is None else gpb.to(points2.dtype).view(points2.shape),
+                None if gw is None else gw.to(weights.dtype).view(weights.shape))
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _fit(points1, points2, weights, reweight, huber_k, n_irls):
+    differentiable = reweight == 0 and _wants_grad(points1, points2, weights)
+    if differentiable and points1.shape[1] > ops.HFIT_SINGLE_MAX:
+        # (before any device work: the streaming fit has no backward, and an H without a graph is what this refuses to return)
+        raise NotImplementedError(f"the weighted least-squares fit is differentiable for N <= {ops.HFIT_SINGLE_MAX} correspondences "
+                                  f"per element (HFIT_SINGLE_MAX), got N = {points1.shape[1]}: subsample, or detach the inputs")
+    if not points1.is_cuda:
+        # The reference's QR estimator takes tensors of any device (least_squares_H.py:142-210 has no device check; only the IRLS
+        # variant asserts, :292-293 -- and so does find_homography_IRLSq_QR below).  Host tensors are copied to the HIP device,
+        # fitted by the same kernel and the result handed back on the caller's device: there is no CPU solver here.  (.to() is a
+        # torch op: with gradients wanted, autograd carries them back over both copies.)
+        dev = torch.device("cuda")
+        out = _fit(points1.to(dev), points2.to(dev), None if weights is None else weights.to(dev), reweight, huber_k, n_irls)
+        return out.to(points1.device)
+    if differentiable:
+        if weights is not None and weights.numel() != points1.shape[0] * points1.shape[1]:
+            raise AssertionError(weights.shape)
+        return _WeightedLSqFit.apply(points1, points2, weights)
+    return _launch(points1, points2, weights, reweight, huber_k, n_irls)
 
 
 def _fit_callable(points1, points2, weights, reweighting_fn, n_iter):
@@ -96,7 +145,10 @@ def _fit_callable(points1, points2, weights, reweighting_fn, n_iter):
 
 def find_homography_nonhomogeneous_QR(points1, points2, weights=None):
     """Weighted inhomogeneous DLT, h33 = 1 (least_squares_H.py:142-210).
-    points (B,N,2), weights (B,N) -> (B,3,3) mapping points1 -> points2."""
+    points (B,N,2), weights (B,N) -> (B,3,3) mapping points1 -> points2.
+    Differentiable once, as the reference's is through torch.linalg.qr: with grad enabled and a points1, points2 or weights that
+    requires grad, H carries a graph whose backward is one HIP launch (N <= 2048 per element; above that NotImplementedError --
+    never an H without a graph).  An element whose fit fails (NaN H) gets zero gradients, not torch's NaN."""
     rec = recorder()
     if rec is not None:                  # (woft_amd.probe: the tracker is finding out what a config's estimator does)
         return rec.fit("lsq", points1, points2, weights)
@@ -108,7 +160,8 @@ def find_homography_IRLSq_QR(points1, points2, weights=None, reweighting_fn=IRLS
     """IRLS m-estimator (least_squares_H.py:280-346): n_iter + 1 solves, per-row re-weighting
     sqrt(reweighting_fn(A x - b)) from the weighted algebraic residual.  Losses built from IRLSq_L1 / IRLSq_Huber
     (what the reference's configs use, configs/..._wIRLSq.py:24-31) run in ONE launch; any other callable is
-    driven pass by pass on device tensors (_fit_callable)."""
+    driven pass by pass on device tensors (_fit_callable).  Forward only, built-in losses and callables alike: the H returned
+    carries no autograd graph."""
     rec = recorder()
     if rec is not None:
         return rec.fit("irls", points1, points2, weights, reweighting_fn, n_iter)
@@ -132,7 +185,7 @@ def find_homography_cvransac(pts_A, pts_B, weights=None, max_iters=10000, thr=1.
     (csrc/ransac.hip; semantics and deviations in DESIGN.md, "RANSAC").  pts (B,N,2) -> (B,3,3) float64, H / H[2,2], on
     pts_A's device; numpy in, numpy out.  `weights` is accepted and ignored, as cv2 ignores it.  Every batch element is fitted
     independently with the same `seed`.  Where no model is found (no hypothesis with 4 or more inliers) that element's H is
-    all NaN; the reference raises a TypeError there (None[2, 2])."""
+    all NaN; the reference raises a TypeError there (None[2, 2]).  Forward only (no autograd graph), as cv2 is."""
     rec = recorder()
     if rec is not None:
         return rec.fit("ransac", pts_A, pts_B, weights, ransac=(max_iters, thr, conf))
@@ -164,7 +217,8 @@ def find_homography_TRS(pts_A, pts_B, weights=None, max_iters=10000, thr=3.0, co
     fixed parameters are the defaults here), on the HIP device (csrc/trs.hip; semantics and deviations in DESIGN.md, "TRS").
     pts (B,N,2) -> (B,3,3) float64 with last row (0, 0, 1), on pts_A's device; numpy in, numpy out.  `weights` is accepted and
     ignored, as the reference ignores it.  Every batch element is fitted independently with the same `seed`.  Where no model
-    is found (no hypothesis with 2 or more inliers) that element's H is all NaN; the reference fails there on cv2's None."""
+    is found (no hypothesis with 2 or more inliers) that element's H is all NaN; the reference fails there on cv2's None.
+    Forward only (no autograd graph), as cv2 is."""
     rec = recorder()
     if rec is not None:
         return rec.fit("trs", pts_A, pts_B, weights, ransac=(max_iters, thr, conf))
@@ -205,9 +259,9 @@ def torch_proj_errors(GT_H, pts_A, pts_B):
 # ---- projection-error helpers (least_squares_H.py:400-505) -----------------------------------------------------------------
 # Plain torch ops on the caller's device, batched; not a hot path, no kernel.  The homogeneous conversions follow the rule
 # torch_proj_errors uses above (kornia's convert_points_from_homogeneous: scale = 1 / (z + 1e-8) where |z| > 1e-8, else 1).
-# They are differentiable as torch ops are, but the HIP estimators above are FORWARD ONLY: an H that came out of
-# find_homography_* carries no autograd graph, so a training loss built from these helpers does not reach the
-# correspondences through the fit.
+# They are differentiable as torch ops are.  Of the HIP estimators above, find_homography_nonhomogeneous_QR is differentiable
+# too (N <= 2048 per element): a training loss built from these helpers reaches the correspondences and the weights through
+# that fit.  The IRLS and RANSAC estimators are forward only: their H carries no autograd graph.
 def torch_e2p(pts):
     """Euclidean -> homogeneous: (B, 2, N) -> (B, 3, N), a row of ones appended (least_squares_H.py:440-449)."""
     return torch.cat([pts, torch.ones_like(pts[:, :1])], dim=1)
@@ -228,7 +282,8 @@ def torch_H_proj(H, pts):
 def torch_reproj_errors(GT_H, est_H, pts_A):
     """L2 distance between pts_A and inv(est_H) * GT_H * pts_A: forward by the ground truth, back by the estimate
     (least_squares_H.py:400-419; the training configs' loss_fn).  GT_H, est_H (B, 3, 3); pts_A (B, 2, N) -> (B, N).
-    Forward only with respect to the HIP estimators (see above)."""
+    A torch op: gradients flow to est_H, and on through find_homography_nonhomogeneous_QR where it made est_H (N <= 2048); the
+    IRLS and RANSAC estimators are forward only (see above)."""
     reproj = torch_p2e(torch.linalg.inv(est_H) @ torch.matmul(GT_H, torch_e2p(pts_A)))
     return torch.sqrt(torch.square(reproj - pts_A).sum(dim=1))
 

@@ -905,6 +905,21 @@ def hfit_batched(pa, pb, w, Hout, status, counts=None, reweight=0, huber_k=1.0, 
                  ptr(status[lo:hi]), stream_ptr()), "woft_hfit_batched")
 
 
+def hfit_batched_bwd(pa, pb, w, gH, gpa, gpb, gw, status=None, counts=None):
+    """Backward of the plain weighted fit (woft_hfit_batched_bwd; reweight 0, N <= HFIT_SINGLE_MAX) in one launch, one
+    workgroup per element: pa, pb (B, N, 2), w (B, N) or None, gH (B, 9) or (B, 3, 3) the gradient with respect to the fit's
+    output; gpa, gpb (B, N, 2), gw (B, N) receive the gradients, any of them None = not wanted (gw needs w); status (B,) int32
+    or None, counts (B,) int32 or None -- all contiguous, fp32, on one device.  An element whose fit fails gets zeros.  More than
+    HFIT_BATCH_MAX elements: one launch per HFIT_BATCH_MAX of them."""
+    B, n = pa.shape[0], pa.shape[1]
+    fn = _lib.load().woft_hfit_batched_bwd
+    sl = lambda t, lo, hi: ptr(t[lo:hi]) if t is not None else None
+    for lo in range(0, B, HFIT_BATCH_MAX):
+        hi = min(B, lo + HFIT_BATCH_MAX)
+        check(fn(ptr(pa[lo:hi]), ptr(pb[lo:hi]), sl(w, lo, hi), hi - lo, n, sl(counts, lo, hi), ptr(gH[lo:hi]), sl(gpa, lo, hi),
+                 sl(gpb, lo, hi), sl(gw, lo, hi), sl(status, lo, hi), stream_ptr()), "woft_hfit_batched_bwd")
+
+
 def hfit_step(pa, pb, w, rew, first, res, Hout, status, ws=None):
     """One re-weighted solve with externally supplied row re-weights; residuals of its solution -> res."""
     ws = ws if ws is not None else hfit_ws(pa.device)

@@ -1,6 +1,7 @@
 """Plain high-precision restatements of the per-frame kernels between the flow and the pose (a helper of the fp64 tests, not a
 conftest): the homography fit, the inlier count, the weight head's mean channel and closing 1x1 conv, the bilinear x8 upsampling
-with its crop, and the tracker's keep rule + Sobol selection on the crop geometry.  Everything here is float64 numpy / torch
+with its crop, the perspective warp / downscale of the frame, and the tracker's keep rule + Sobol selection on the crop geometry.
+Everything here is float64 numpy / torch
 (or exact integer logic); the GPU tests compare the HIP kernels against these, with tolerances derived from the kernels' own
 fp32 rounding."""
 import numpy as np
@@ -127,6 +128,190 @@ def upflow8_crop(flow, crop, h, w):
     (crop_top, crop_left, h, w): flow (1, C, hf, wf) -> (C, h, w)."""
     up = raft_ref.upflow8(_t64(flow))
     return up[0, :, crop[0]:crop[0] + h, crop[1]:crop[1] + w].numpy()
+
+
+# ---- perspective warp, downscale: the per-frame image geometry -----------------------------------------------------------------
+# The band of the classification rule: how far the kernel's fp32 value of one byte can lie from the fp64 value, derived (not
+# measured) from csrc/warp_pixel.h; resize_linear_kernel interpolates the same way.  In units of 2^-24:
+#   * the source coordinates are fp64 and the fractions fx, fy are rounded to fp32 once each: at most 2^-25 each, times a gradient
+#     |t01 - t00| <= 255                                                                                    -> 2 * 127.5
+#   * 1 - fx and 1 - fy are rounded (at most 2^-25, the values being <= 1) and then multiply a value <= 255   -> 2 * 127.5
+#     (top and bot both carry the error of 1 - fx, but enter v with weights (1 - fy) + fy = 1: it counts once)
+#   * top = t00 (1 - fx) + t01 fx is two products and a sum, each rounded to a value <= 255, so by at most half an ulp of a
+#     number below 256, 2^-17 = 128 * 2^-24; bot likewise, and again the pair counts once                     -> 3 * 128
+#   * v = top (1 - fy) + bot fy: two products and a sum                                                       -> 3 * 128
+# Sum 1278 < 8 * 255 = 2040 (contraction to FMA only removes roundings).  The fp64 coordinates of the kernel and of numpy differ
+# by some 1e-13 at most, times 255: nothing on this scale.
+WARP_BAND = 8 * 255 * 2.0 ** -24
+WARP_FAR = 1e9                       # a source coordinate beyond this (or not finite) is "nowhere": value 0, invalid
+
+
+def warp_source64(h, w, Hm):
+    """Source coordinates (sx, sy) and the denominator d of every destination pixel of an h x w frame, float64, with
+    Hinv = np.linalg.inv(Hm) as ops takes it.  Where d == 0 both coordinates are +inf (never NaN, and nothing is divided by 0)."""
+    Hi = np.linalg.inv(np.asarray(Hm, np.float64))
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    d = Hi[2, 0] * xs + Hi[2, 1] * ys + Hi[2, 2]
+    nx = Hi[0, 0] * xs + Hi[0, 1] * ys + Hi[0, 2]
+    ny = Hi[1, 0] * xs + Hi[1, 1] * ys + Hi[1, 2]
+    zero = d == 0
+    safe = np.where(zero, 1.0, d)
+    with np.errstate(over="ignore", under="ignore"):     # a tiny d may overflow to inf: that is a pixel "nowhere", as wanted
+        sx, sy = nx / safe, ny / safe
+    sx[zero], sy[zero] = np.inf, np.inf
+    return sx, sy, d
+
+
+def _warp_live(sx, sy):
+    """Pixels whose source lies somewhere: finite and within WARP_FAR (comparisons only; inf compares without a warning)."""
+    return (np.abs(sx) <= WARP_FAR) & (np.abs(sy) <= WARP_FAR)
+
+
+def warp_linear64(img, Hm):
+    """dst(x, y) = bilinear src(Hinv (x, y)) with a zero border, all in float64 and UNROUNDED: (v, sx, sy), v shaped like img.
+    A pixel whose source is not finite or beyond WARP_FAR has value 0 (no inf or NaN is ever cast to an integer)."""
+    img = np.asarray(img)
+    h, w = img.shape[:2]
+    sx, sy, _ = warp_source64(h, w, Hm)
+    live = _warp_live(sx, sy)
+    sxl, syl = np.where(live, sx, -2.0), np.where(live, sy, -2.0)          # -2: every tap outside, value 0
+    fx0, fy0 = np.floor(sxl), np.floor(syl)
+    fx, fy = (sxl - fx0)[..., None], (syl - fy0)[..., None]
+    x0, y0 = fx0.astype(np.int64), fy0.astype(np.int64)
+    src = img.astype(np.float64).reshape(h, w, -1)
+
+    def tap(yy, xx):
+        ok = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+        return src[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)] * ok[..., None]
+
+    top = tap(y0, x0) * (1 - fx) + tap(y0, x0 + 1) * fx
+    bot = tap(y0 + 1, x0) * (1 - fx) + tap(y0 + 1, x0 + 1) * fx
+    v = top * (1 - fy) + bot * fy
+    v[~live] = 0.0
+    return v.reshape(img.shape), sx, sy
+
+
+def warp_valid64(sx, sy, h, w):
+    """warp(ones) > 0: some tap inside the frame has positive weight, which is exactly -1 < sx < w and -1 < sy < h."""
+    return _warp_live(sx, sy) & (sx > -1) & (sx < w) & (sy > -1) & (sy < h)
+
+
+def warp_valid_excused(sx, sy, h, w, eps=1e-6):
+    """Pixels whose validity fp32 may decide either way: sx within eps of -1 or w, sy within eps of -1 or h (there
+    (float)(sx - floor(sx)) may round to 0 or 1)."""
+    live = _warp_live(sx, sy)
+    ex, ey = np.where(live, sx, 0.5), np.where(live, sy, 0.5)
+    return (np.abs(ex + 1) < eps) | (np.abs(ex - w) < eps) | (np.abs(ey + 1) < eps) | (np.abs(ey - h) < eps)
+
+
+def warp_nearest64(img, Hm):
+    """src(rint(sx), rint(sy)), rounding half to even, 0 outside: (bytes shaped like img, sx, sy, inside) with inside (h, w) the
+    pixels that read a source pixel."""
+    img = np.asarray(img)
+    h, w = img.shape[:2]
+    sx, sy, _ = warp_source64(h, w, Hm)
+    live = _warp_live(sx, sy)
+    rx = np.rint(np.where(live, sx, -2.0)).astype(np.int64)
+    ry = np.rint(np.where(live, sy, -2.0)).astype(np.int64)
+    inside = (rx >= 0) & (rx < w) & (ry >= 0) & (ry < h)
+    src = img.reshape(h, w, -1)
+    out = src[np.clip(ry, 0, h - 1), np.clip(rx, 0, w - 1)] * inside[..., None].astype(img.dtype)
+    return out.reshape(img.shape), sx, sy, inside
+
+
+def warp_nearest_excused(sx, sy, h, w, eps=1e-9):
+    """Pixels whose nearest source pixel may legitimately differ: sx or sy within eps of a half-integer, where contraction to FMA
+    in the fp64 coordinate can flip the tie -- and the source within a pixel of the frame (-1 < sx < w, -1 < sy < h): farther
+    out both neighbours of the tie lie outside and the byte is 0 either way."""
+    live = _warp_live(sx, sy)
+    ex, ey = np.where(live, sx, 0.0), np.where(live, sy, 0.0)
+    tie = (np.abs(ex - np.floor(ex) - 0.5) < eps) | (np.abs(ey - np.floor(ey) - 0.5) < eps)
+    return tie & live & (sx > -1) & (sx < w) & (sy > -1) & (sy < h)
+
+
+def resize_out_shape(h, w, factor):
+    """(ho, wo) = int(round(. / factor)), Python's round: half to even."""
+    return int(round(h / factor)), int(round(w / factor))
+
+
+def resize_linear64(img, factor):
+    """oracle.tracker_ref.resize_linear_u8's geometry (src = (dst + 0.5) * factor - 0.5, edge clamped, ho = int(round(h /
+    factor))) with float64 interpolation, UNROUNDED, shaped (ho, wo[, c])."""
+    img = np.asarray(img)
+    h, w = img.shape[:2]
+    ho, wo = resize_out_shape(h, w, factor)
+
+    def axis(n_out, n_in):
+        f = (np.arange(n_out, dtype=np.float64) + 0.5) * float(factor) - 0.5
+        i0 = np.floor(f)
+        wt = f - i0
+        i0 = i0.astype(np.int64)
+        wt[i0 < 0] = 0.0
+        i0 = np.clip(i0, 0, n_in - 1)
+        wt[i0 >= n_in - 1] = 0.0
+        return i0, np.minimum(i0 + 1, n_in - 1), wt
+
+    y0, y1, wy = axis(ho, h)
+    x0, x1, wx = axis(wo, w)
+    src = img.astype(np.float64).reshape(h, w, -1)
+    wxx, wyy = wx[None, :, None], wy[:, None, None]
+    top = src[y0][:, x0] * (1 - wxx) + src[y0][:, x1] * wxx
+    bot = src[y1][:, x0] * (1 - wxx) + src[y1][:, x1] * wxx
+    return (top * (1 - wyy) + bot * wyy).reshape((ho, wo) + img.shape[2:])
+
+
+def classify_bytes(v, g, band=WARP_BAND):
+    """The classification rule for bilinear bytes: with v the fp64 value the byte g must satisfy floor(v + 0.5 - band) <= g <=
+    floor(v + 0.5 + band): exactly rint(v), unless v lies within band of a .5 tie, where either neighbour is accepted.
+    Returns (bad, excused, used): bytes outside the rule, bytes within band of a tie, bytes that differ from rint(v)."""
+    v = np.asarray(v, np.float64)
+    g = np.asarray(g).astype(np.int64)
+    lo, hi = np.floor(v + 0.5 - band), np.floor(v + 0.5 + band)
+    return (g < lo) | (g > hi), lo != hi, g != np.rint(v)
+
+
+def rint_div(s, n):
+    """rint(s / n) for non-negative integer arrays s and an integer n > 0, in integers: ties go to the even neighbour."""
+    s = np.asarray(s, np.int64)
+    q, r = s // n, s % n
+    return q + ((2 * r > n) | ((2 * r == n) & (q % 2 == 1)))
+
+
+def warp_halves_exact(img, sx2, sy2):
+    """The bilinear zero-border warp for source coordinates that are integers or half-integers, given DOUBLED as integer arrays
+    (sx2 = 2 sx): in integer arithmetic throughout.  Every weight is 0, 1/2 or 1, so 4 v is an integer sum of taps and the byte
+    is rint_div(4 v, 4), ties half to even; absent taps count as 0.  Returns (bytes shaped like img, valid)."""
+    img = np.asarray(img)
+    h, w = img.shape[:2]
+    sx2, sy2 = np.asarray(sx2, np.int64), np.asarray(sy2, np.int64)
+    x0, y0, ax, ay = sx2 // 2, sy2 // 2, (sx2 % 2)[..., None], (sy2 % 2)[..., None]     # floor; weight of the far tap in halves
+    src = img.astype(np.int64).reshape(h, w, -1)
+
+    def tap(yy, xx):
+        ok = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+        return src[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)] * ok[..., None]
+
+    top = tap(y0, x0) * (2 - ax) + tap(y0, x0 + 1) * ax
+    bot = tap(y0 + 1, x0) * (2 - ax) + tap(y0 + 1, x0 + 1) * ax
+    v4 = top * (2 - ay) + bot * ay
+    valid = (sx2 > -2) & (sx2 < 2 * w) & (sy2 > -2) & (sy2 < 2 * h)
+    return rint_div(v4, 4).astype(np.uint8).reshape(img.shape), valid
+
+
+def nearest_halves_exact(img, sx2, sy2):
+    """The nearest-neighbour warp for doubled integer source coordinates: a half-integer goes to its EVEN neighbour (rint)."""
+    img = np.asarray(img)
+    h, w = img.shape[:2]
+
+    def near(s2):
+        s2 = np.asarray(s2, np.int64)
+        lo = s2 // 2
+        return np.where(s2 % 2 == 0, lo, lo + (lo % 2))
+    rx, ry = near(sx2), near(sy2)
+    inside = (rx >= 0) & (rx < w) & (ry >= 0) & (ry < h)
+    src = img.reshape(h, w, -1)
+    out = src[np.clip(ry, 0, h - 1), np.clip(rx, 0, w - 1)] * inside[..., None].astype(img.dtype)
+    return out.reshape(img.shape), inside
 
 
 # ---- correspondence keep rule + Sobol selection ---------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ pytestmark = pytest.mark.gpu
 
 from woft_amd import ops  # noqa: E402
 from woft_amd.window import Box  # noqa: E402
+import geometry_cases as G  # noqa: E402
 
 H, W = 123, 157                      # odd on purpose
 HOMOGRAPHIES = {
@@ -26,20 +27,16 @@ def _image(c, seed=0):
     return torch.from_numpy(rs.randint(0, 256, shape).astype(np.uint8)).cuda()
 
 
-@pytest.mark.parametrize("nearest", [False, True])
-@pytest.mark.parametrize("c", [1, 3])
-@pytest.mark.parametrize("hname", list(HOMOGRAPHIES))
-def test_windowed_warp_is_the_full_warp_sliced(hname, c, nearest):
-    img, Hm = _image(c, seed=c), HOMOGRAPHIES[hname]
+def _check_windows_against_full_frame(img, Hm, nearest, what):
+    """Every window of WINDOWS == the full-frame kernel's output sliced; and either output alone.  -> the full-frame validity."""
     full, full_valid = torch.empty_like(img), torch.empty((H, W), dtype=torch.uint8, device="cuda")
     ops.warp_perspective_u8(img, Hm, full, full_valid, nearest=nearest)
-    assert int(full_valid.sum()) > 0
     for name, (y0, x0, rows, cols) in WINDOWS.items():
         out = torch.full((rows, cols) + tuple(img.shape[2:]), 77, dtype=torch.uint8, device="cuda")
         valid = torch.full((rows, cols), 77, dtype=torch.uint8, device="cuda")
         ops.warp_perspective_window_u8(img, Hm, (y0, x0, rows, cols), out, valid, nearest=nearest)
-        assert torch.equal(out, full[y0:y0 + rows, x0:x0 + cols]), (hname, c, nearest, name)
-        assert torch.equal(valid, full_valid[y0:y0 + rows, x0:x0 + cols]), (hname, c, nearest, name)
+        assert torch.equal(out, full[y0:y0 + rows, x0:x0 + cols]), (what, nearest, name)
+        assert torch.equal(valid, full_valid[y0:y0 + rows, x0:x0 + cols]), (what, nearest, name)
     # either output alone (bilinear: validity only / image only)
     y0, x0, rows, cols = WINDOWS["inner"]
     out = torch.empty((rows, cols) + tuple(img.shape[2:]), dtype=torch.uint8, device="cuda")
@@ -49,6 +46,40 @@ def test_windowed_warp_is_the_full_warp_sliced(hname, c, nearest):
         valid = torch.empty((rows, cols), dtype=torch.uint8, device="cuda")
         ops.warp_perspective_window_u8(img, Hm, WINDOWS["inner"], None, valid)
         assert torch.equal(valid, full_valid[y0:y0 + rows, x0:x0 + cols])
+    return full_valid
+
+
+@pytest.mark.parametrize("nearest", [False, True])
+@pytest.mark.parametrize("c", [1, 3, 4])
+@pytest.mark.parametrize("hname", list(HOMOGRAPHIES))
+def test_windowed_warp_is_the_full_warp_sliced(hname, c, nearest):
+    full_valid = _check_windows_against_full_frame(_image(c, seed=c), HOMOGRAPHIES[hname], nearest, (hname, c))
+    assert int(full_valid.sum()) > 0
+
+
+# Where the shared per-pixel arithmetic has its edges (test_image_geometry_gpu pins the full-frame kernel there independently): a
+# horizon inside the frame, a denominator of exactly 0.0, a frame carried wholly outside, source coordinates on integers and on
+# half-integers.
+EDGE_HOMOGRAPHIES = {
+    "horizon": G.GENERIC["horizon"],
+    "horizon-inv": G.GENERIC["horizon-inv"],
+    "dzero": G.dzero(H, W)[0],
+    "far": G.FAR,
+    "shift(-7,2)": G.translation(-7, 2),
+    "half(-2.5,3.5)": G.translation(-2.5, 3.5),
+}
+
+
+@pytest.mark.parametrize("nearest", [False, True])
+@pytest.mark.parametrize("c", [1, 3, 4])
+@pytest.mark.parametrize("hname", list(EDGE_HOMOGRAPHIES))
+def test_windowed_warp_is_the_full_warp_sliced_at_the_edges(hname, c, nearest):
+    full_valid = _check_windows_against_full_frame(_image(c, seed=c), EDGE_HOMOGRAPHIES[hname], nearest, (hname, c))
+    assert (int(full_valid.sum()) == 0) == (hname == "far")
+    if hname == "dzero":
+        assert np.array_equal(np.linalg.inv(EDGE_HOMOGRAPHIES[hname]), G.dzero(H, W)[1])
+        ys, xs = np.mgrid[0:H, 0:W]
+        assert not full_valid.cpu().numpy()[xs + ys == G.dzero(H, W)[2]].any()
 
 
 @pytest.mark.parametrize("c", [1, 3, 4])

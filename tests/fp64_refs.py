@@ -1,6 +1,7 @@
 """Plain high-precision restatements of the per-frame kernels between the flow and the pose (a helper of the fp64 tests, not a
 conftest): the homography fit, the inlier count, the weight head's mean channel and closing 1x1 conv, the bilinear x8 upsampling
-with its crop, the perspective warp / downscale of the frame, and the tracker's keep rule + Sobol selection on the crop geometry.
+with its crop, the perspective warp / downscale of the frame, the tracker's keep rule + Sobol selection on the crop geometry,
+and -- at the end -- the correlation lookup, the flow-head gather and the convex upsampling of the refinement loop.
 Everything here is float64 numpy / torch
 (or exact integer logic); the GPU tests compare the HIP kernels against these, with tolerances derived from the kernels' own
 fp32 rounding."""
@@ -359,3 +360,97 @@ def select(dst, w, tmask, pwmask, gh, gw, u, cap):
     pb = np.stack([chosen % gw, chosen // gw], 1).astype(np.float32)
     wo = np.ones(len(chosen), np.float32) if w is None else np.asarray(w, np.float32).reshape(-1)[chosen]
     return pa, pb, wo, len(chosen), len(kept)
+
+
+# ---- correlation lookup ---------------------------------------------------------------------------------------------------------
+# What one fp32 bilinear sample of the lookup kernels can lie from the fp64 value, per unit of M = the largest |tap| of its
+# four.  The kernels compute fx = xs - floor(xs) exactly (xs = x * 2^-l is exact and |xs| < 2^23), so what remains are the
+# roundings of three lerps q0 * (1 - w) + q1 * w: 1 - w, two products and a sum each, the second-stage operands carrying the
+# first stage's error.  A CPU restatement of that arithmetic (tests/test_lookup_edges_cpu.py) measured at most 3.8 units of
+# 2^-24 M; the constant is twice the measured maximum, rounded up to a power of two (profiles/README.md records both).
+LOOKUP_BAND = 8 * 2.0 ** -24
+LOOKUP_FAR = 1.0e6                   # a coordinate beyond this at its level (or not finite) is "nowhere": value 0
+
+
+def lookup64(planes, coords, radius):
+    """The multi-scale correlation lookup in pixel coordinates, float64: planes[l] (P, H_l, W_l) (independent inputs, any
+    sizes), coords (P, 2) = (x, y) -> (value, M), both (P, L (2r+1)^2).  For level l and window element (i, j): xs = x / 2^l +
+    (i - r), ys = y / 2^l + (j - r), x0 = floor(xs), fx = xs - x0 (same for y), the four taps (x0 | x0 + 1, y0 | y0 + 1) with
+    zero outside [0, W_l) x [0, H_l); channel l (2r+1)^2 + i (2r+1) + j (x-major).  M is the largest |tap| of the four.  A
+    coordinate that is not finite or beyond LOOKUP_FAR at its level reads nothing: value 0, M 0."""
+    c = np.asarray(coords, np.float64)
+    P, n = len(c), 2 * radius + 1
+    vals, mags = [], []
+    for l, pl in enumerate(planes):
+        pl = np.asarray(pl, np.float64)
+        assert pl.shape[0] == P
+        H, W = pl.shape[1:]
+        x, y = c[:, 0] / 2.0 ** l, c[:, 1] / 2.0 ** l
+        with np.errstate(invalid="ignore"):            # (NaN compares false without this on current numpy; older ones warned)
+            live = (np.abs(x) <= LOOKUP_FAR) & (np.abs(y) <= LOOKUP_FAR)
+        xl, yl = np.where(live, x, 0.0), np.where(live, y, 0.0)
+        x0, y0 = np.floor(xl), np.floor(yl)
+        fx, fy = (xl - x0)[:, None, None], (yl - y0)[:, None, None]
+        xs = x0.astype(np.int64)[:, None] - radius + np.arange(n + 1)[None]
+        ys = y0.astype(np.int64)[:, None] - radius + np.arange(n + 1)[None]
+        ok = ((ys >= 0) & (ys < H))[:, :, None] & ((xs >= 0) & (xs < W))[:, None, :] & live[:, None, None]
+        patch = pl[np.arange(P)[:, None, None], np.clip(ys, 0, H - 1)[:, :, None], np.clip(xs, 0, W - 1)[:, None, :]] * ok
+        tl, tr, bl, br = patch[:, :n, :n], patch[:, :n, 1:], patch[:, 1:, :n], patch[:, 1:, 1:]       # [P, j (y), i (x)]
+        v = (tl * (1 - fx) + tr * fx) * (1 - fy) + (bl * (1 - fx) + br * fx) * fy
+        m = np.maximum(np.maximum(np.abs(tl), np.abs(tr)), np.maximum(np.abs(bl), np.abs(br)))
+        vals.append(v.transpose(0, 2, 1).reshape(P, n * n))                                       # -> [P, i, j]
+        mags.append(m.transpose(0, 2, 1).reshape(P, n * n))
+    return np.concatenate(vals, 1), np.concatenate(mags, 1)
+
+
+# ---- flow-head gather -----------------------------------------------------------------------------------------------------------
+def flow_head_gather64(part, n_planes, hf, wf, bias=None):
+    """delta[p, o] = bias[o] + sum over the 9 taps (ky, kx) and the planes of part[plane P + q, (3 ky + kx) 2 + o], q the
+    neighbour (y + ky - 1, x + kx - 1) of p, taps outside the grid zero; float64.  part (>= n_planes P, >= 18), P = hf wf.
+    Returns (delta (P, 2), sum of the absolute terms (P, 2)): a fixed-order fp32 sum of n terms lies within n 2^-24 times the
+    latter of the former (gather_band)."""
+    P = hf * wf
+    pt = np.asarray(part, np.float64)[:n_planes * P, :18].reshape(n_planes, hf, wf, 9, 2)
+    b = np.zeros(2) if bias is None else np.asarray(bias, np.float64).reshape(-1)[:2]
+    pad = np.zeros((n_planes, hf + 2, wf + 2, 9, 2))
+    pad[:, 1:-1, 1:-1] = pt
+    delta, mag = np.zeros((hf, wf, 2)) + b, np.zeros((hf, wf, 2)) + np.abs(b)
+    for ky in range(3):
+        for kx in range(3):
+            t = pad[:, ky:ky + hf, kx:kx + wf, 3 * ky + kx]
+            delta += t.sum(0)
+            mag += np.abs(t).sum(0)
+    return delta.reshape(P, 2), mag.reshape(P, 2)
+
+
+def gather_band(n_planes, mag):
+    """The standard bound of a fixed-order fp32 sum: (number of additions + 1) 2^-24 sum |terms|; the kernels add 9 n_planes
+    terms to the bias (n_planes - 1 additions per tap, then 9 onto the running sum)."""
+    return (9 * n_planes + 1) * U32 * np.asarray(mag, np.float64)
+
+
+# ---- convex upsampling ----------------------------------------------------------------------------------------------------------
+# fp32 softmax over 9 logits and a 9-term weighted sum: exp of a difference (one rounding in the difference, about one unit in
+# expf), the denominator's 8 additions, a division and a product per tap, 8 additions of terms bounded by max |8 v_k|: below
+# 32 units of 2^-24 max |8 v_k| (the CPU restatement in tests/test_lookup_edges_cpu.py stays inside it with zero violations).
+CONVEX_BAND = 32 * 2.0 ** -24
+
+
+def convex_upsample64(values, mask, hf, wf):
+    """out[c, 8 hc + i, 8 wc + j] = sum_k softmax_k(mask[p, k 64 + 8 i + j]) 8 values[c, q_k], q_k the neighbour (hc + k // 3 -
+    1, wc + k % 3 - 1) of cell p = (hc, wc), zero outside the grid; float64.  values (C, hf wf), mask (hf wf, >= 576) ->
+    (out (C, 8 hf, 8 wf), M (C, 8 hf, 8 wf) = max_k |8 values[c, q_k]| per output)."""
+    v = np.asarray(values, np.float64)
+    C = v.shape[0]
+    m = np.asarray(mask, np.float64)[:, :576].reshape(hf, wf, 9, 8, 8)
+    e = np.exp(m - m.max(2, keepdims=True))
+    s = e / e.sum(2, keepdims=True)                                         # (hf, wf, 9, 8, 8)
+    pad = np.zeros((C, hf + 2, wf + 2))
+    pad[:, 1:-1, 1:-1] = 8.0 * v.reshape(C, hf, wf)
+    out, mag = np.zeros((C, hf, wf, 8, 8)), np.zeros((C, hf, wf, 8, 8))
+    for k in range(9):
+        nb = pad[:, k // 3:k // 3 + hf, k % 3:k % 3 + wf][..., None, None]
+        out += s[None, :, :, k] * nb
+        mag = np.maximum(mag, np.abs(nb))
+    tr = lambda a: a.transpose(0, 1, 3, 2, 4).reshape(C, 8 * hf, 8 * wf)    # noqa: E731
+    return tr(out), tr(mag)

@@ -153,6 +153,15 @@ typedef struct woft_conv_params {
        (column, tap, chunk) block the lane half supplies (L / 32 = 0: first tap, 1: second tap; value = 2^(scale - 127)).
        Measured: 2.2-2.3 x the error of precision 1 at 1.64 x its matrix-pipe rate (tools/micro/mx_split_probe.hip). */
     const void* wgt_mx;
+    /* Output rectangle (halo 8 / 12 / 16 only): the launch computes and stores only the output pixels (y, x) with
+       roi_y0 <= y < roi_y0 + roi_h and roi_x0 <= x < roi_x0 + roi_w of every image -- its tile grid covers the rectangle (origin at
+       (roi_y0, roi_x0): 8x16 / 4x16-pixel tiles, or 64-pixel runs along the rectangle's rows for halo 16), every other output pixel
+       is left untouched.  The input is still the whole h x w map: a tile's halo reads it wherever it lies and is zero-padded at
+       the true image border only, so every pixel inside the rectangle is bit-identical to the whole-map launch's.  All four zero
+       = the whole map.  Otherwise 0 <= roi_y0, roi_y0 + roi_h <= ho (x alike), roi_h, roi_w > 0, no statistics; any other kernel
+       (halo 0 / 1 / 2 / 4 / 7) or a rectangle outside the map: WOFT_EINVAL -- never a silent whole-map launch.  The two layers of
+       woft_conv2d_pair carry a rectangle each. */
+    int32_t roi_y0, roi_x0, roi_h, roi_w;
 } woft_conv_params;
 
 int woft_conv2d(const woft_conv_params* p, void* stream);
@@ -294,6 +303,14 @@ typedef struct woft_lookup_otf_params {
     float* fh_flow4;        /* [hf*wf][4] or NULL                                                   */
     float* fh_flow_cat;     /* [hf*wf][fh_ld_cat] (2 values written) or NULL                        */
     int32_t fh_planes, fh_ld, fh_ld_delta, fh_ld_cat;
+    /* Region-restricted launch.  roi_* (all zero: the whole map): only the 8 x 8 blocks (origins at multiples of 8) that intersect the
+       pixel rectangle [roi_y0, roi_y0 + roi_h) x [roi_x0, roi_x0 + roi_w) are launched; they run whole (all their pixels inside the
+       map), every other block's coordinates and output rows are left untouched.  smp_* (all zero: every launched block): of the
+       launched blocks only those that intersect this second rectangle compute samples; the others stop after the folded flow-head
+       gather / coordinate update (fh_part != NULL) of their pixels -- the next iteration's flow input is needed further out than its
+       lookup samples.  Both rectangles must lie inside the map with positive sizes, else WOFT_EINVAL. */
+    int32_t roi_y0, roi_x0, roi_h, roi_w;
+    int32_t smp_y0, smp_x0, smp_h, smp_w;
 } woft_lookup_otf_params;
 int woft_corr_lookup_otf(const woft_lookup_otf_params* p, void* stream);
 /* NHWC map [h][w][c] -> its rows in 4x4-tile order [(ceil(h/4)*ceil(w/4)*16)][c], zero rows outside

@@ -32,6 +32,7 @@ class ConvParams(C.Structure):
         ("out_index", vp),
         ("wh0_lookup", vp), ("wh0_ld", i32), ("wh0_mean", vp), ("wh0_w", vp), ("wh0_bias", vp), ("wh0_index", vp),
         ("wgt_frag", vp), ("wgt_mx", vp),
+        ("roi_y0", i32), ("roi_x0", i32), ("roi_h", i32), ("roi_w", i32),
     ]
 
 
@@ -50,6 +51,8 @@ class LookupOtfParams(C.Structure):
         ("alpha", f32), ("coords", vp), ("out", vp), ("need", vp), ("ldo", i32), ("ablate", i32),
         ("fh_part", vp), ("fh_bias", vp), ("fh_delta", vp), ("fh_flow4", vp), ("fh_flow_cat", vp),
         ("fh_planes", i32), ("fh_ld", i32), ("fh_ld_delta", i32), ("fh_ld_cat", i32),
+        ("roi_y0", i32), ("roi_x0", i32), ("roi_h", i32), ("roi_w", i32),
+        ("smp_y0", i32), ("smp_x0", i32), ("smp_h", i32), ("smp_w", i32),
     ]
 
 

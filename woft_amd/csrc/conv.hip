@@ -749,7 +749,7 @@ __global__ __launch_bounds__(256, (STAGES == 1 ? 4 : (TY == 9 ? 3 : 1))) void co
             return;
         }
     }
-    const HaloRowMap<TY, TX> rowmap{img0, p.n_img, y0, x0, p.ho, p.wo};
+    const HaloRowMap<TY, TX> rowmap{img0, p.n_img, y0, x0, p.ho, p.wo, p.ho, p.wo};
     woft::conv_epilogue_t<TM, TN, WROWS, WCOLS>(p, acc, (float*)smem + wave * woft::STAGE_FLOATS, rowmap, n0, wm, wn,
                                                 lane, m_tile);
 }
@@ -1055,6 +1055,12 @@ static int conv_check(const woft_conv_params& p) {
         if (p.cout % 4 != 0 && (!simple || p.stat_sum != nullptr || p.bias_map != nullptr)) return WOFT_EINVAL;
     }
     if (p.in_norm < 0 || p.in_norm > 2) return WOFT_EINVAL;
+    // output rectangle (woft_conv_params.roi_*): the register-streamed kernel and the streamed GEMM kernel only, inside the map --
+    // a kernel without it must refuse, never run the whole map
+    if ((p.roi_y0 | p.roi_x0 | p.roi_h | p.roi_w) != 0 &&
+        ((p.halo != 8 && p.halo != 12 && p.halo != 16) || p.roi_h <= 0 || p.roi_w <= 0 || p.roi_y0 < 0 || p.roi_x0 < 0 ||
+         p.roi_y0 > p.ho - p.roi_h || p.roi_x0 > p.wo - p.roi_w || p.stat_sum != nullptr || p.precision == 0))
+        return WOFT_EINVAL;
     if (p.bias_map != nullptr && (p.cout % 4 != 0 || p.ld_bias_map < p.cout || p.ld_bias_map % 4 != 0 ||
                                   p.epi == WOFT_EPI_CTX || p.epi == WOFT_EPI_WH_MEAN || p.out_pitch != 0))
         return WOFT_EINVAL;

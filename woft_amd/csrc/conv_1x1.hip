@@ -57,8 +57,18 @@ __device__ __forceinline__ void tile_1x1(const woft_conv_params& p, const int m_
     const int r32 = lane & 31, hh = lane >> 5;
     const int row = tid >> 2, v = tid & 3;                                // loader: pixel row of the tile, 8-channel group of the chunk
 
-    const int64_t M = (int64_t)p.n_img * p.ho * p.wo;
-    const int64_t m0 = (int64_t)m_tile * G::BM;
+    // rows of this tile: the pixels [m0, M) (at most 64 of them).  Whole map: 64 consecutive pixels of the linear order; an output
+    // rectangle (woft_conv_params.roi_*): a 64-pixel run of ONE row of the rectangle -- tile = (image, row, run) -- cut at its right edge
+    int64_t M = (int64_t)p.n_img * p.ho * p.wo;
+    int64_t m0 = (int64_t)m_tile * G::BM;
+    if ((p.roi_y0 | p.roi_x0 | p.roi_h | p.roi_w) != 0) {
+        const int runs = (p.roi_w + G::BM - 1) / G::BM;
+        const int line = m_tile / runs, run = m_tile - line * runs;          // line = image * roi_h + row of the rectangle
+        const int img = line / p.roi_h, ry = line - img * p.roi_h;
+        m0 = ((int64_t)img * p.ho + p.roi_y0 + ry) * p.wo + p.roi_x0 + run * G::BM;
+        const int left = p.roi_w - run * G::BM;
+        M = m0 + (left < G::BM ? left : G::BM);
+    }
     const int n0 = n_tile * BN;
     const int nchunk = FLAT ? p.taps_y : p.cin_pad / BK;                   // K chunks of 32 (FLAT: one per tap row)
 
@@ -231,6 +241,12 @@ __device__ __forceinline__ void tile_1x1(const woft_conv_params& p, const int m_
                                                         woft::LinearRows{m0, M}, n0, 0, wave, lane, m_tile);
 }
 
+// 64-pixel tiles of a launch: of the linear pixel order, or -- with an output rectangle -- runs along the rectangle's rows
+__host__ __device__ __forceinline__ int m_tiles_1x1(const woft_conv_params& p) {
+    if ((p.roi_y0 | p.roi_x0 | p.roi_h | p.roi_w) != 0) return p.n_img * p.roi_h * ((p.roi_w + 63) / 64);
+    return (int)(((int64_t)p.n_img * p.ho * p.wo + 63) / 64);
+}
+
 // the two tile forms: 1x1 layers 256 columns per workgroup, flat layers 128
 
 template <int TERMS>
@@ -242,9 +258,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const woft_conv_params 
     const bool second_layer = (int)blockIdx.x >= split;
     const woft_conv_params p = second_layer ? pb : pa;     // (a copy: see conv_regb_kernel)
     const int bid = second_layer ? (int)blockIdx.x - split : (int)blockIdx.x;
-    const int64_t M = (int64_t)p.n_img * p.ho * p.wo;
     int m_tile, n_tile;
-    woft::tile_of_block(bid, (int)((M + 63) / 64), p.cout_pad / (p.flat ? 128 : 256), m_tile, n_tile);
+    woft::tile_of_block(bid, m_tiles_1x1(p), p.cout_pad / (p.flat ? 128 : 256), m_tile, n_tile);
     if (!p.flat) tile_1x1<TERMS, 2, false, 4, 4>(p, m_tile, n_tile, smem);
     else tile_1x1<TERMS, 1, true, 4, 4>(p, m_tile, n_tile, smem);
 }
@@ -271,7 +286,7 @@ int woft_conv_1x1_launch(const woft_conv_params& a, const woft_conv_params* seco
         if ((int64_t)p.n_img * p.h * p.w * cs_max >= (1ll << 31)) return WOFT_EINVAL;       // 32-bit element offsets
     }
     auto blocks = [](const woft_conv_params& q) {
-        return ceil_div64((int64_t)q.n_img * q.ho * q.wo, 64) * (q.cout_pad / (q.flat ? 128 : 256));
+        return (int64_t)m_tiles_1x1(q) * (q.cout_pad / (q.flat ? 128 : 256));
     };
     const woft_conv_params& pb = second ? *second : a;
     const int split = (int)blocks(a);

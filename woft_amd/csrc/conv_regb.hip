@@ -25,7 +25,8 @@ __global__ __launch_bounds__(256, 2) void conv_regb_kernel(const woft_conv_param
     const int bid = second_layer ? (int)blockIdx.x - split : (int)blockIdx.x;
     using G = RegbGeom<TY, TX, KY, KX, WM, TERMS>;
     __shared__ __attribute__((aligned(16))) __bf16 smem[G::SMEM_ELEMS];
-    const int tyn = (p.ho + TY - 1) / TY, txn = (p.wo + TX - 1) / TX;
+    const OutRect rc = out_rect(p);
+    const int tyn = (rc.h + TY - 1) / TY, txn = (rc.w + TX - 1) / TX;
     int m_tile, n_tile;
     woft::tile_of_block(bid, p.n_img * tyn * txn, p.cout_pad / G::BN, m_tile, n_tile);
     // developer probe (tools/regb_probe.py): s_memtime stamps of wave 0 -> in_rstd (unused by this kernel otherwise)
@@ -38,7 +39,8 @@ template <int WM, int TY = 8>
 int launch_regb(const woft_conv_params& p, const woft_conv_params* second, hipStream_t s) {
     constexpr int TX = 16, BN = 128 / WM;
     auto blocks = [](const woft_conv_params& q) {
-        const int tyn = (q.ho + TY - 1) / TY, txn = (q.wo + TX - 1) / TX;
+        const OutRect rc = out_rect(q);                 // (a restricted launch: the tiles of its output rectangle only)
+        const int tyn = (rc.h + TY - 1) / TY, txn = (rc.w + TX - 1) / TX;
         return (int64_t)q.n_img * tyn * txn * (q.cout_pad / BN);
     };
     const woft_conv_params& pb = second ? *second : p;

@@ -92,10 +92,13 @@ __device__ __forceinline__ void regb_tile(const ParamsT& p, const int m_tile, co
     const int r32 = lane & 31, hh = lane >> 5;
     const int v = tid & 7, r0 = tid >> 3;
 
-    const int tyn = (p.ho + TY - 1) / TY, txn = (p.wo + TX - 1) / TX;
+    // the tile grid covers the launch's output rectangle (the whole map, or woft_conv_params.roi_*); the halo below still reads the
+    // whole input map and is zero-padded at the true image border only
+    const OutRect rc = out_rect(p);
+    const int tyn = (rc.h + TY - 1) / TY, txn = (rc.w + TX - 1) / TX;
     const int img0 = m_tile / (tyn * txn);
     const int trem = m_tile - img0 * (tyn * txn);
-    const int y0 = (trem / txn) * TY, x0 = (trem % txn) * TX;
+    const int y0 = rc.y0 + (trem / txn) * TY, x0 = rc.x0 + (trem % txn) * TX;
     const int n0 = n_tile * BN;
     const int nchunk = p.cin_pad / BK;
     const int nsteps = nchunk * TAPS;
@@ -453,7 +456,7 @@ __device__ __forceinline__ void regb_tile(const ParamsT& p, const int m_tile, co
     run_phase(nchunk - 1, std::false_type{});
     __syncthreads();                                     // halo buffers are dead: reuse them as epilogue staging
 
-    const HaloRowMap<TY, TX> rowmap{img0, p.n_img, y0, x0, p.ho, p.wo};
+    const HaloRowMap<TY, TX> rowmap{img0, p.n_img, y0, x0, p.ho, p.wo, rc.y0 + rc.h, rc.x0 + rc.w};
     if (p.epi == WOFT_EPI_FLOWHEAD) {
         // (f16mx8: the epilogue's small second conv keeps the split-bf16 arithmetic; its W2 fragments are packed for it)
         constexpr int ET = MX ? 3 : TERMS, ENP = (ET == 3) ? 2 : 1;

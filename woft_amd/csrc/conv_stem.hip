@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(const woft_conv_param
             }
         __syncthreads();                                           // the patch planes are free for the next tile
         const int img = m_tile / (tyn * txn), trem = m_tile - img * (tyn * txn);
-        const HaloRowMap<S_TY, S_TX> rowmap{img, p.n_img, (trem / txn) * S_TY, (trem % txn) * S_TX, p.ho, p.wo};
+        const HaloRowMap<S_TY, S_TX> rowmap{img, p.n_img, (trem / txn) * S_TY, (trem % txn) * S_TX, p.ho, p.wo, p.ho, p.wo};
         woft::conv_epilogue_t<TM, 1, 64, 32>(p, acc, stage + wave * woft::STAGE_FLOATS, rowmap, n0, wm, wn, lane, m_tile);
     }
 }

@@ -108,16 +108,27 @@ __device__ __forceinline__ int halo_row_pixel(int row, bool& valid) {
     }
 }
 
+// (y1, x1): end of the rows / columns the launch stores -- ho, wo, or the end of its output rectangle (woft_conv_params.roi_*)
 template <int TY, int TX>
 struct HaloRowMap {
-    int img0, n_img, y0, x0, ho, wo;
+    int img0, n_img, y0, x0, ho, wo, y1, x1;
     __device__ __forceinline__ int64_t operator()(int row) const {
         bool valid;
         const int pl = halo_row_pixel<TY, TX>(row, valid);
         if (!valid) return -1;
         const int y = y0 + pl / TX, x = x0 + pl % TX;
-        return (y < ho && x < wo) ? ((int64_t)img0 * ho + y) * wo + x : -1;
+        return (y < y1 && x < x1) ? ((int64_t)img0 * ho + y) * wo + x : -1;
     }
 };
+
+// Output rectangle of a launch (woft_conv_params.roi_*; all zero = the whole ho x wo map): origin and size of its tile grid.
+struct OutRect {
+    int y0, x0, h, w;
+};
+template <class ParamsT>
+__host__ __device__ __forceinline__ OutRect out_rect(const ParamsT& p) {
+    if ((p.roi_y0 | p.roi_x0 | p.roi_h | p.roi_w) == 0) return OutRect{0, 0, p.ho, p.wo};
+    return OutRect{p.roi_y0, p.roi_x0, p.roi_h, p.roi_w};
+}
 
 }  // namespace

@@ -85,6 +85,16 @@ __device__ __forceinline__ void lds_dma16x2(const void* gbase, uint32_t o0_plus_
                  : "memory", "vcc");
 }
 
+// 8 x 8 blocks of a launch: first block and block counts per axis
+struct BlockRect {
+    int by0, bx0, ny, nx;
+};
+__host__ __device__ __forceinline__ BlockRect block_rect(const woft_lookup_otf_params& p) {
+    if ((p.roi_y0 | p.roi_x0 | p.roi_h | p.roi_w) == 0) return BlockRect{0, 0, (p.hf + 7) / 8, (p.wf + 7) / 8};
+    const int by0 = p.roi_y0 / 8, bx0 = p.roi_x0 / 8;
+    return BlockRect{by0, bx0, (p.roi_y0 + p.roi_h - 1) / 8 - by0 + 1, (p.roi_x0 + p.roi_w - 1) / 8 - bx0 + 1};
+}
+
 template <int TERMS, int R, int K, int ABL>
 __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_lookup_otf_params p) {
     constexpr int NPX = 64, NT = 256;
@@ -113,13 +123,19 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
     const int wm = wave >> 1, wn = wave & 1;
     const int r32 = lane & 31, hh = lane >> 5;
     constexpr int ld = LD, nk = NK;
-    const int tiles_x = (p.wf + 7) / 8, ntiles = tiles_x * ((p.hf + 7) / 8);
+    // the launch's 8 x 8 blocks: all of the map, or those that intersect the rectangle roi_* (woft_lookup_otf_params)
+    const BlockRect br = block_rect(p);
+    const int tiles_x = br.nx, ntiles = br.nx * br.ny;
     int tile;
     {
         const int q = ntiles / 8, rr = ntiles % 8, xcd = blockIdx.x % 8, idx = blockIdx.x / 8;
         tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
     }
-    const int px0 = (tile % tiles_x) * 8, py0 = (tile / tiles_x) * 8;
+    const int px0 = (br.bx0 + tile % tiles_x) * 8, py0 = (br.by0 + tile / tiles_x) * 8;
+    // samples are wanted from the blocks that intersect smp_* (all zero: from every launched block); the others only finish the
+    // folded flow-head gather of their pixels
+    const bool sampled = (p.smp_y0 | p.smp_x0 | p.smp_h | p.smp_w) == 0 ||
+                         (py0 < p.smp_y0 + p.smp_h && py0 + 8 > p.smp_y0 && px0 < p.smp_x0 + p.smp_w && px0 + 8 > p.smp_x0);
     if (p.need != nullptr) {      // nobody wants this block's samples (the weight head on a subset of the source pixels)
         int any = 0;
         if (tid < NPX) {
@@ -129,9 +145,9 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
         if (!__syncthreads_or(any)) return;
     }
     // lookup centre of source pixel `tid` (wave 0), read once: requested BEFORE the A fragments (loads return in order)
+    float cx = 0.f, cy = 0.f;
     if (tid < NPX) {
         const int y = py0 + (tid >> 3), x = px0 + (tid & 7);
-        float cx = 0.f, cy = 0.f;
         if (y < p.hf && x < p.wf) {
             const int64_t i = (int64_t)y * p.wf + x;
             cx = p.coords[i * 2];
@@ -170,6 +186,10 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
                 }
             }
         }
+    }
+    if (!sampled) return;                                // (block-uniform, before the first barrier)
+    if (tid < NPX) {
+        const int y = py0 + (tid >> 3), x = px0 + (tid & 7);
         // window origins, interpolation weights, drop-test operands and bounding boxes of ALL levels, while the other waves fetch
         // their A fragments (the DPP reductions cost this wave ~1 k cycles per level)
         const bool cvalid = y < p.hf && x < p.wf;
@@ -447,10 +467,16 @@ extern "C" int woft_corr_lookup_otf(const woft_lookup_otf_params* pp, void* stre
         if (p.h[l] > 16384 || p.w[l] > 16384) return WOFT_EINVAL;                       // (packed 16-bit map positions in the drop test)
         if ((int64_t)p.h[l] * p.w[l] * row_bytes >= (1ll << 32) - 4096) return WOFT_EINVAL;   // (lane offsets carry + 4 KiB: lds_dma16x2)
     }
+    auto rect_bad = [&](int y0, int x0, int h, int w) {     // (all zero: not given)
+        return (y0 | x0 | h | w) != 0 && (h <= 0 || w <= 0 || y0 < 0 || x0 < 0 || y0 > p.hf - h || x0 > p.wf - w);
+    };
+    if (rect_bad(p.roi_y0, p.roi_x0, p.roi_h, p.roi_w) || rect_bad(p.smp_y0, p.smp_x0, p.smp_h, p.smp_w)) return WOFT_EINVAL;
+    if (p.ablate != 0 && ((p.roi_y0 | p.roi_x0 | p.roi_h | p.roi_w) != 0 || (p.smp_y0 | p.smp_x0 | p.smp_h | p.smp_w) != 0)) return WOFT_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     // 8 x 8 source pixels per workgroup.  (16 x 8: 40 % less target-row traffic, but one 8-wave workgroup per CU and 20 % more steps
     // per workgroup: measured 110 vs 98 us at 1080p in round 1, -1.7 % frames/s in round 2 -- the per-workgroup chain of K steps binds.)
-    dim3 grid((unsigned)(((p.wf + 7) / 8) * ((p.hf + 7) / 8)));
+    const BlockRect br = block_rect(p);
+    dim3 grid((unsigned)(br.nx * br.ny));
 #define OTF(T, RR, KK, AB) woft_launch(0, corr_lookup_otf_kernel<T, RR, KK, AB>, grid, dim3(256), 0, s, p)
     if (p.ablate != 0) {          // developer instances (tools/bench_lookup_otf.py): full model, split-bf16 only
         if (!(p.k == 256 && p.radius == 4 && p.terms == 3)) return WOFT_EINVAL;

@@ -22,7 +22,7 @@ import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, flow_region, ops
 from .ops import Act, new_act
 
 EPI = _lib
@@ -38,6 +38,8 @@ PYRAMID_ONE_LAUNCH = os.environ.get("WOFT_PYRAMID", "1") != "0"    # target pyra
 # the flow-head gather of iteration k runs inside the lookup launch of iteration k + 1 (volume-free lookup; the last
 # iteration's as its own launch): one launch fewer per iteration, same operations in the same order (0: always its own launch)
 FOLD_GATHER = os.environ.get("WOFT_FOLD_GATHER", "1") != "0"
+# kernels that take an output rectangle (woft_conv_params.roi_*): the register-streamed conv and the streamed 1x1 / flat GEMM
+ROI_HALOS = (8, 12, 16)
 
 
 def _ru(x, m):
@@ -360,6 +362,8 @@ class _Plan:
                 self.prog_iter_last = (self.prog_iter[:k] + [("conv2", (self.prog_iter[k][1], self.prog_mask[0]), "fh1+mk1")]
                                        + self.prog_iter[k + 1:])
         self._fold = self._fold_gather_programs()
+        self.flow_region = None                          # None = every launch on the whole map (set_flow_region)
+        self._flow_regions = {}
         if eng.weighted:
             n = sp.nwin
             self.x8 = new_act(P, n, n, 5, cs=8, zero=True)
@@ -480,6 +484,101 @@ class _Plan:
             assert fused
             self._wh_regions[key] = (index, prog)
         self.wh_region = self._wh_regions[key]
+
+    # ---- the refinement loop restricted to what a rectangle of the flow depends on -----------------
+    def _layer_taps(self):
+        """{layer: (reach along y, along x)} of the update block's convs, from the packed layers themselves."""
+        e = self.eng
+        r = lambda pc: (flow_region.reach(pc.kh or pc.taps_y, pc.pad_y), flow_region.reach(pc.kw or pc.taps_x, pc.pad_x))
+        return {"convc1": r(e.convc1), "convc2": r(e.convc2), "convf1": r(e.convf1), "convf2": r(e.convf2), "convm": r(e.convm),
+                "gru0": r(e.zr_dyn[0]), "gru1": r(e.zr_dyn[1]), "fh1": r(e.fh1), "fh2": r(e.fh2), "mk1": r(e.mk1), "mk2": r(e.mk2)}
+
+    def set_flow_region(self, rect, iters=None):
+        """The caller reads the full-resolution flow (flow_up / dst, and the weights) of the next flow() of `iters` iterations only
+        inside the 1/8-resolution cells rect = (y0, x0, h, w) (None: everywhere).  The launches of the last iterations are then
+        restricted to the rectangles those cells depend on (woft_amd/flow_region.py: derived backwards from the convex
+        upsampling's 3x3 support, layer by layer, from the layers' own taps); an iteration whose every rectangle is the whole map
+        runs today's program objects.  Inside the rectangle's pixels the results are bit-identical to the unrestricted flow;
+        outside they are unspecified but finite (as the weights outside finish_weights()' pixels).  Programs are built once per
+        (rectangle, iteration count).  Full model on the volume-free correlation with the folded flow head only -- anything else
+        (and a trace, or a warm start, in flow()) runs every launch on the whole map; -> whether anything is restricted."""
+        self.flow_region = None
+        sp = self.eng.spec
+        if rect is None or iters is None or iters < 2 or sp.small or not self.otf or self._fold is None \
+                or getattr(self, "prog_iter_last", None) is None or len(self.eng.zr_dyn) != 2:
+            return False
+        key = (tuple(int(v) for v in rect), int(iters))
+        if key not in self._flow_regions:
+            self._flow_regions[key] = self._flow_region_programs(*key)
+        self.flow_region = self._flow_regions[key]
+        return self.flow_region is not None
+
+    def _flow_region_programs(self, rect, iters):
+        """-> {"key", "iters": {iteration: restricted program}, "rects": [(iteration, tag, [rect per part])]} or None when no launch is
+        smaller than the whole map."""
+        hf, wf = self.hf, self.wf
+        taps = self._layer_taps()
+        parts = {}
+        for first in (True, False):
+            for _, pp in flow_region.iteration_launches(taps, first=first, last=True, folded=True):
+                for part in pp:
+                    parts[(first, part[0])] = part
+        base = lambda it: self._fold[id(self.prog_iter_first if it == 0 else (self.prog_iter_last if it == iters - 1 else self.prog_iter))]
+        launches, where = [], []
+        for it in range(iters):
+            for k, ent in enumerate(base(it)):
+                if ent[0] == "lookup":
+                    names = (["gather"] if ent[1].fh_part else []) + ["lookup"]
+                elif ent[0] in ("conv", "conv2") and len(ent) > 2:
+                    names = ent[2].split("+")
+                else:
+                    return None                              # (a launch this derivation does not know: nothing is restricted)
+                if any((it == 0, n) not in parts for n in names):
+                    return None
+                launches.append((it, ent[2] if len(ent) > 2 else "lookup", [parts[(it == 0, n)] for n in names]))
+                where.append((it, k))
+        launches += [(-1, tag, pp) for tag, pp in flow_region.closing_launches(taps)]
+        rects, _ = flow_region.schedule(launches, flow_region.final_need(rect, hf, wf), hf, wf)
+        cd = lambda a, b: -(-a // b)
+
+        def tiles(halo, r):
+            """Workgroups per column tile of a launch on rectangle r (None: the whole map) of a kernel's pixel tiling."""
+            y0, x0, h, w = r or (0, 0, hf, wf)
+            if halo == 16:                                   # 64-pixel runs: along the rectangle's rows / of the linear pixel order
+                return h * cd(w, 64) if r else cd(hf * wf, 64)
+            ty = {8: 8, 12: 4}.get(halo)
+            return cd(h, ty) * cd(w, 16) if ty else (cd(y0 + h, 8) - y0 // 8) * (cd(x0 + w, 8) - x0 // 8)     # (else: the lookup's 8x8 blocks)
+
+        # a rectangle is handed to a kernel only where it saves a tenth of the launch's workgroups: a launch may always compute more
+        # than it must, and e.g. 64-pixel runs along the rows of a rectangle a little narrower than the map are MORE workgroups
+        # than the map's linear tiling (measured slower: profiles/flow_region_ab.txt)
+        small = lambda r, halo=None: (r is not None and not flow_region.is_full(r, hf, wf)
+                                      and 10 * tiles(halo, r) <= 9 * tiles(halo, None))
+
+        def restricted(p, r):
+            q = type(p).from_buffer_copy(p)
+            q.__dict__.update(p.__dict__)                    # (the tensors the struct points to stay alive with it)
+            q.roi_y0, q.roi_x0, q.roi_h, q.roi_w = r
+            return q
+
+        progs = {}
+        for (it, k), (_, tag, _), rr in zip(where, launches, rects):
+            ent = base(it)[k]
+            new = None
+            if ent[0] == "lookup" and small(rr[-1]):
+                lk = restricted(ent[1], rr[0])               # launched blocks: the gather's pixels (or, without one, the samples')
+                lk.smp_y0, lk.smp_x0, lk.smp_h, lk.smp_w = rr[-1]
+                new = ("lookup", lk)
+            elif ent[0] == "conv" and ent[1].halo in ROI_HALOS and small(rr[0], ent[1].halo):
+                new = ("conv", restricted(ent[1], rr[0]), tag + "@roi")
+            elif ent[0] == "conv2" and ent[1][0].halo in ROI_HALOS and any(small(r, ent[1][0].halo) for r in rr):
+                new = ("conv2", tuple(restricted(p, r) if small(r, p.halo) else p for p, r in zip(ent[1], rr)), tag + "@roi")
+            if new is not None:
+                progs.setdefault(it, list(base(it)))[k] = new
+        if not progs:
+            return None
+        return {"key": (rect, iters), "iters": progs,
+                "rects": [(it, tag, rr) for (it, tag, _), rr in zip(launches, rects)]}
 
     def _cp(self, *a, **kw):
         kw.setdefault("precision", self.prec)
@@ -799,10 +898,16 @@ class _Plan:
                 trace(self, -1)
         last = getattr(self, "prog_iter_last", None) if iters > 1 else None
         fold = self._fold if trace is None else None        # (a trace reads the coordinates after every iteration)
+        # restricted iterations (set_flow_region): not under a trace (it reads whole maps) nor a warm start (flow_low is read everywhere)
+        region = self.flow_region if (trace is None and flow_init is None) else None
+        if region is not None and region["key"][1] != iters:
+            region = None
         for it in range(iters):
             prog = self.prog_iter_first if it == 0 else (last if (last is not None and it == iters - 1) else self.prog_iter)
             if fold is not None:
                 prog = fold[id(prog)]
+            if region is not None:
+                prog = region["iters"].get(it, prog)
             self.run(prog)
             if trace is not None:
                 trace(self, it)

@@ -153,12 +153,16 @@ class RAFTWrapper:
         # flow config key `volume_storage` ("fp32" | "bf16"): element type of the correlation volume (corr = "volume")
         self.engine = RaftEngine(state_dict, small=small, weighted=weighted, precision=self.precision, corr=self.corr,
                                  volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked)
+        # restricted refinement iterations for callers that declare where they read the flow (pin_flow_region + flow_region=True)
+        v = getattr(self.C, "flow_region", None)
+        self.flow_region_on = (os.environ.get("WOFT_FLOW_REGION", "1") != "0") if (v is None or isinstance(v, type(self.C))) else bool(v)
         # opt-in (flow config key `graph`, env WOFT_GRAPH=1): the ~330 launches of a flow -- a static list per
         # resolution, fixed buffers, no allocation -- are captured once into a hipGraph and replayed per frame
         self.use_graph = (os.environ.get("WOFT_GRAPH") or str(int(bool(getattr(self.C, "graph", False))))) == "1"
         self._pinned = None
         self._pinned_key = None
         self._wmask, self._wregion, self._all_pixels = None, {}, {}
+        self._fmask, self._fregion = None, {}
         self.weights_deferred, self._deferred = False, None
         self.defer_min_ratio = 6           # defer_weights: region windows per named pixel from which deferring pays
         self._out = {}
@@ -206,8 +210,10 @@ class RAFTWrapper:
             return eager()
         graphs = plan.__dict__.setdefault("_graphs", {})
         region = plan.wh_region
+        fregion = plan.flow_region if not has_init else None     # (restricted iterations are other launches: other graphs)
         key = (iters, crop, oh, ow, weighted, do_sigmoid, want_flow, bool(defer_wh), o["flow"].data_ptr(),
-               region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid), bool(has_init))
+               region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid), bool(has_init),
+               fregion["key"] if fregion is not None else None)
         g = graphs.get(key)
         if g is None:
             eager()                                        # this call's results; also the warm-up the capture needs
@@ -239,6 +245,30 @@ class RAFTWrapper:
         self._pinned = src_img
         self._pinned_key = None
         self._wmask, self._wregion = None, {}
+        self._fmask, self._fregion = None, {}
+
+    def pin_flow_region(self, mask):
+        """Declare that, for flows FROM the pinned source image requested with flow_region=True, the caller reads the flow (and the
+        weights) only at the pixels where `mask` (bool ndarray, source-image size; None = everywhere) is set.  The last refinement
+        iterations then run only on the part of the 1/8-resolution map that the bounding rectangle of those pixels depends on
+        (engine._Plan.set_flow_region): at the masked pixels flow, correspondences and weights are bit-identical, elsewhere they are
+        unspecified but finite -- the contract finish_weights() has for the weights.  A mask that fills the frame restricts
+        nothing and costs nothing."""
+        self._fmask = None if mask is None else np.ascontiguousarray(np.asarray(mask) > 0)
+        self._fregion = {}
+
+    def _flow_region(self, key, hp, wp, top, left, oh, ow):
+        """-> (y0, x0, h, w): the 1/8-resolution cells of the padded image that hold a pixel of the pinned flow mask, or None."""
+        if self._fmask is None:
+            return None
+        if key not in self._fregion:
+            ys, xs = np.nonzero(self._fmask[:oh, :ow])
+            rect = None
+            if ys.size:
+                y0, y1, x0, x1 = (ys.min() + top) >> 3, (ys.max() + top) >> 3, (xs.min() + left) >> 3, (xs.max() + left) >> 3
+                rect = (int(y0), int(x0), int(y1 - y0 + 1), int(x1 - x0 + 1))
+            self._fregion[key] = rect
+        return self._fregion[key]
 
     def pin_weight_region(self, mask):
         """Declare that, for flows FROM the pinned source image, the caller consumes the flow weights only at the
@@ -368,7 +398,7 @@ class RAFTWrapper:
 
     def compute_flow(self, src_img, dst_img, mode="TC", vis=False, src_img_identifier=None,
                      numpy_out=False, do_sigmoid=False, borrow=False, defer_weights=False, weight_region=False,
-                     src_is_previous_dst=False, visibility=False, flow_init=None, iters=None):
+                     src_is_previous_dst=False, visibility=False, flow_init=None, iters=None, flow_region=False):
         """src_img / dst_img: (H, W, 3) uint8 BGR (numpy, or CUDA tensors already on the device).
         mode 'TC' -> (src_coords (2,HW) int64, dst_coords (2,HW) f32, weights (1,HW) f32 | None)
         mode 'flow' -> (flow (2,H,W), weights (1,H,W) | None).
@@ -391,7 +421,11 @@ class RAFTWrapper:
         tensor (either device) or a numpy float array; any other shape raises a ValueError that names the expected one.  Ignored
         on a flow-cache hit (the cache bypasses the network).  flow_low() after a call returns what the next call of a video
         would pass through woft_amd.warm.forward_interpolate.
-        iters (extension, default None = the flow config's `iters`): the number of refinement iterations of THIS call."""
+        iters (extension, default None = the flow config's `iters`): the number of refinement iterations of THIS call.
+        flow_region (extension, default off): the caller reads flow, correspondences and weights only inside the region declared
+        with pin_flow_region() (flows from the pinned source, no flow_init, no visibility mask, no weights_postprocessing_fn; config
+        key `flow_region` = False / env WOFT_FLOW_REGION=0 switch it off): identical values there, unspecified but finite ones
+        elsewhere.  Without it every call computes the whole map, as the reference does."""
         if visibility and not self.masked:
             raise ValueError("compute_flow(visibility=True) needs raft_type 'weighted_masked': no other type has a mask output")
         assert mode in ["flow", "TC"]
@@ -464,6 +498,10 @@ class RAFTWrapper:
                     self._all_pixels[plan.P] = torch.arange(plan.P, dtype=torch.int32, device="cuda")
                 region = self._all_pixels[plan.P]
         plan.set_weight_region(region)
+        frect = None
+        if flow_region and self.flow_region_on and pinned_here and not post and flow_init is None and not self.masked:
+            frect = self._flow_region(key, hp, wp, top, left, oh, ow)
+        plan.set_flow_region(frect, n_iters)
         d = up(dst_img)
         plan.load_image(1, d, top, left)
         self._last_dst[id(plan)] = (id(dst_img), key)         # (what this buffer set's target features will belong to after this call)

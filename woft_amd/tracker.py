@@ -286,6 +286,14 @@ class YAOFTrackerSingleControl:
             # evaluates the head everywhere for the tracker too, as the reference's network does.
             if hasattr(self.flower, "pin_weight_region"):
                 self.flower.pin_weight_region(inside if self._mask_weight_head() else None)
+            # The same keep rule bounds the FLOW this tracker reads of a template flow: the update block is a stack of small
+            # convolutions, so the last refinement iterations run only on the part of the 1/8-resolution map the mask's bounding
+            # rectangle depends on (flow_provider.pin_flow_region; 11 cells more per iteration going backwards) -- identical
+            # flow, correspondences and weights inside the mask, identical homographies (tested).  Asked for by the global
+            # stage's own calls only (_global_stage), with the weight head's switch: mask_weight_head = False keeps the
+            # reference's whole work.  Not with a visibility mode (the mask head reads every pixel) nor with the warm start.
+            if hasattr(self.flower, "pin_flow_region"):
+                self.flower.pin_flow_region(inside if self._flow_region_on() else None)
             # ... and with a subsampler in front of the fit (the default config draws 500 correspondences), only the weights
             # of the DRAWN correspondences are read, and the draw does not depend on the weights: the head is evaluated after
             # the selection, on the windows under the drawn pixels' upsampling support (config key sparse_weight_head =
@@ -386,13 +394,16 @@ class YAOFTrackerSingleControl:
             return os.environ.get("WOFT_MASK_WEIGHT_HEAD", "1") != "0"
         return bool(v)
 
+    def _flow_region_on(self):
+        return bool(self._mask_weight_head() and self.visibility_mode is None and not self.warm_start_local)
+
     def _set_pose(self, H, good):
         self.prev_H2init = H
         if good:
             self.last_good_H2init = H.copy()
 
     # ---- the two flow stages ------------------------------------------------------------------------
-    def _flow(self, src, dst, src_is_previous_dst=False, flow_init=None, iters=None):
+    def _flow(self, src, dst, src_is_previous_dst=False, flow_init=None, iters=None, flow_region=False):
         """-> (grid coords (2, n) int64, target coords (2, n) f32, weights (1, n) f32 | None, visibility probabilities (1, n) f32 |
         None (a visibility mode only), (gh, gw)); borrowed buffers of the provider: consumed before the next flow."""
         # (borrowed buffers, and -- only for THIS caller -- weights restricted to the region pinned in init(): a direct
@@ -404,6 +415,8 @@ class YAOFTrackerSingleControl:
             kw["defer_weights"] = int(self._fused["n_draw"])
         if src_is_previous_dst and "borrow" in kw:
             kw["src_is_previous_dst"] = True
+        if flow_region and hasattr(self.flower, "pin_flow_region"):
+            kw["flow_region"] = True                                 # (flows from the pinned template only: the global stage)
         if flow_init is not None:                                    # (warm start: the local stage only)
             kw["flow_init"] = flow_init
             if iters is not None:
@@ -439,7 +452,7 @@ class YAOFTrackerSingleControl:
             ops.warp_perspective_u8(frame, prewarp_H, prewarped, valid)
         if self.C.do_not_mask_TCs_by_prewarped:
             valid = None
-        src_xy, dst_xy, w, p, grid = self._flow(self.template_img, prewarped)
+        src_xy, dst_xy, w, p, grid = self._flow(self.template_img, prewarped, flow_region=self._flow_region_on())
         return self._solve(src_xy, dst_xy, w, grid, frame.shape[:2], self._template_mask_u8, valid, bounds=True,
                            judge=True, vis=p)
 

@@ -473,8 +473,8 @@ def test_launch_merging_switches_are_bit_identical(monkeypatch, small):
         prov = c.of_class(c)
         flow, w = prov.compute_flow(a, b, mode="flow")
         plan = prov.engine.plan(136, 200)
-        assert (plan._fold is not None) == (fold and plan.prog_iter[-1][0] == "fh_gather")
-        n_launch = len(plan._fold[id(plan.prog_iter)]) if plan._fold is not None else len(plan.prog_iter)
+        assert (plan.folded is not None) == (fold and plan.prog_iter[-1][0] == "fh_gather")
+        n_launch = len(plan.folded.prog_iter) if plan.folded is not None else len(plan.prog_iter)
         outs.append((flow.clone(), None if w is None else w.clone(), n_launch))
     for f, w, _ in outs[1:]:
         assert torch.equal(f, outs[0][0]) and (w is None or torch.equal(w, outs[0][1]))

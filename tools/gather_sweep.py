@@ -7,7 +7,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 
 from woft_amd import ops, synth
-from woft_amd.engine import RaftEngine
+from woft_amd.engine import RaftEngine, Step
 
 
 def main():
@@ -22,9 +22,9 @@ def main():
     plan.flow(2, (0, 0), h, w, flow_up=torch.zeros(2, h, w, device="cuda"), dst=torch.zeros(2, h * w, device="cuda"),
               wout=torch.zeros(1, h * w, device="cuda"))
     torch.cuda.synchronize()
-    progs = [("f_dst", plan.prog_f_dst), ("iter", plan.prog_iter), ("mask", [("conv", p) for p in plan.prog_mask])]
+    progs = [("f_dst", plan.prog_f_dst), ("iter", plan.prog_iter), ("mask", [Step("conv", p) for p in plan.prog_mask])]
     for name, prog in progs:
-        for idx, (kind, p) in enumerate(prog):
+        for idx, (kind, p, _) in enumerate(prog):
             if kind != "conv" or p.halo != 0:
                 continue
             keep = (p.tile_m, p.tile_n, p.cout_pad)

@@ -8,7 +8,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 
 from woft_amd import ops, synth
-from woft_amd.engine import RaftEngine
+from woft_amd.engine import RaftEngine, Step
 
 
 def main():
@@ -31,32 +31,24 @@ def main():
               wout=torch.zeros(1, h * w, device="cuda"))
     torch.cuda.synchronize()
     progs = [("f_dst", plan.prog_f_dst, 1), ("c_src", plan.prog_c_src, 0), ("volume", plan.prog_volume, 1),
-             ("iter", plan.prog_iter, 12), ("mask", [("conv", p) for p in plan.prog_mask], 1),
-             ("wh", [("conv", p) for p in plan.prog_wh], 1)]
+             ("iter", plan.prog_iter, 12), ("mask", [Step("conv", p) for p in plan.prog_mask], 1),
+             ("wh", [Step("conv", p) for p in plan.prog_wh], 1)]
     total = 0.0
-    if getattr(plan, "wh0_direct", False) and not getattr(plan, "wh0_fused", False):
-        from woft_amd import _lib
-        lib = _lib.load()
-        n = eng.spec.nwin
-        progs.append(("wh0", [("call", lambda: _lib.check(lib.woft_wh_conv0(
-            _lib.ptr(plan.corr.t), plan.corr.cs, _lib.ptr(plan.wmean), plan.P, n, _lib.ptr(plan.wh0_t),
-            _lib.ptr(eng.wh0.bias), _lib.ptr(plan.a1.t), None, _lib.stream_ptr()), "wh_conv0"))], 1))
-    if getattr(plan, "wh0_direct", False) and not getattr(plan, "wh_fused", False):
-        from woft_amd import _lib
-        lib = _lib.load()
-        n = eng.spec.nwin
-        progs.append(("whred", [("call", lambda: _lib.check(lib.woft_wh_reduce(
-            _lib.ptr(plan.a1.t), 128, n * n, _lib.ptr(eng.wh6_w), eng.wh6_b, plan.P, _lib.ptr(plan.wlow),
-            _lib.stream_ptr()), "wh_reduce"))], 1))
+    n = eng.spec.nwin
+    if plan.wh0_direct and not plan.wh0_fused:
+        progs.append(("wh0", [Step("call", lambda: ops.wh_conv0(plan.corr, plan.wmean, plan.P, n, plan.wh0_t, eng.wh0.bias,
+                                                                  plan.a1))], 1))
+    if plan.wh0_direct and not plan.wh_fused:
+        progs.append(("whred", [Step("call", lambda: ops.wh_reduce(plan.a1, n * n, eng.wh6_w, eng.wh6_b, plan.P, plan.wlow))], 1))
     for name, prog, mult in progs:
         sub = 0.0
         for idx, ent in enumerate(prog):
-            kind, arg = ent[0], ent[1]
+            kind, arg = ent.kind, ent.arg
             ts = []
             for _ in range(5):
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 s.record()
-                arg() if kind == "call" else plan.run([(kind, arg)])
+                arg() if kind == "call" else plan.run([ent])
                 e.record()
                 torch.cuda.synchronize()
                 ts.append(s.elapsed_time(e))

@@ -16,9 +16,14 @@ weighted_raft.py:240-255); pyramid levels built as correlations against 2x2-pool
 (linearity; the reference's own AlternateCorrBlock does the same, corr.py:77-81); the weight
 head's mean-response channel in algebraic form; template-side tensors (fmap1, net, inp) cached
 when the caller pins the source image.
+
+Launch programs: lists of Step(kind, arg, tag) replayed by _Plan.run().  A refinement iteration has up to three (first / middle /
+merged last) and, with the flow-head gather folded into the next lookup, a second set (_Plan.folded): _Plan._iteration() alone
+picks among them.  The heads after the loop (prog_mask, prog_wh, prog_mh) are plain lists of conv parameter structs.
 """
 import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -44,6 +49,44 @@ ROI_HALOS = (8, 12, 16)
 
 def _ru(x, m):
     return (x + m - 1) // m * m
+
+
+class Step(NamedTuple):
+    """One entry of a launch program: what _Plan.run() dispatches on, its argument(s), the layer's name where it has one."""
+    kind: str
+    arg: object
+    tag: str = None
+
+
+class _Folded(NamedTuple):
+    """The iteration programs with the flow-head gather that ends iteration k done by the lookup launch that starts iteration
+    k + 1 (woft_lookup_otf_params.fh_*), the launch that closes the last iteration, and that lookup's parameter struct."""
+    prog_iter_first: list
+    prog_iter: list
+    prog_iter_last: list       # None where the plan has no merged last iteration
+    gather: list
+    lookup: object
+
+
+def _timed(sink, launch, *args, extra=None):
+    """launch(*args); with a sink (a bench hook's list) between two HIP events, appended as (start, end[, extra()])."""
+    if sink is None:
+        return launch(*args)
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    launch(*args)
+    e.record()
+    sink.append((s, e) if extra is None else (s, e, extra()))
+
+
+def _head_layers(sd, prefix, cin):
+    """Layers `prefix`0, `prefix`2, ... of a WeightHead / MaskHead in a state dict -> (their indices, their weight shapes, whether
+    they form such a head on cin input channels: odd square kernels, matching channels, a closing 1x1 conv to one channel)."""
+    idx = sorted(int(k.split(".")[2]) for k in sd if k.startswith(prefix) and k.endswith(".weight"))
+    shapes = [tuple(sd[f"{prefix}{i}.weight"].shape) for i in idx]
+    ok = not (len(idx) < 2 or shapes[-1][0] != 1 or shapes[-1][2:] != (1, 1) or shapes[0][1] != cin
+              or any(a[0] != b[1] for a, b in zip(shapes, shapes[1:])) or any(sh[2] != sh[3] or sh[2] % 2 == 0 for sh in shapes))
+    return idx, shapes, ok
 
 
 class _Spec:
@@ -133,15 +176,32 @@ class RaftEngine:
         if not torch.cuda.is_available():
             raise _lib.WoftHipError("woft_amd needs a HIP device: there is no CPU fallback")
         sd = {k: v.detach().float().cpu() for k, v in state_dict.items()}
-        self.weighted = weighted
+        self.weighted, self.small, self.mask_head = weighted, small, bool(mask_head)
         self.spec = sp = _Spec(small)
-        self.small = small
         self.radius, self.levels = sp.radius, sp.levels
-        self.fnet = _Enc(sd, "fnet", sp.fnorm, sp)
-        self.cnet = _Enc(sd, "cnet", sp.cnorm, sp, out_split=sp.hdim)
+        if self.mask_head and not weighted:
+            raise ValueError("mask_head: the MaskHead belongs to WeightedRAFT (weighted_raft.py:75-76), not to plain RAFT")
+        # (what only some models have: the full model's second correlation conv and upsampling-mask head, the two heads)
+        self.convc2 = self.mk1 = self.mk2 = None
+        self.wh_std = self.wh_flat0 = False
+        self.wh0 = self.wh2 = self.wh4 = self.wh0_frag = self.wh_layers = self.wh6_c = self.wh6_w = self.wh6_b = None
+        self.mh_shapes = self.mh_layers = self.mh_c = self.mh_wlast = self.mh_b = None
+        self._pack_encoders(sd)
+        self._pack_update_block(sd)
+        if weighted:
+            self._pack_weight_head(sd)
+        if self.mask_head:
+            self._pack_mask_head(sd)
+        self._plans = {}
+
+    def _pack_encoders(self, sd):
+        self.fnet = _Enc(sd, "fnet", self.spec.fnorm, self.spec)
+        self.cnet = _Enc(sd, "cnet", self.spec.cnorm, self.spec, out_split=self.spec.hdim)
+
+    def _pack_update_block(self, sd):
+        sp, small, precision = self.spec, self.small, self.precision
         u = "update_block."
         g = lambda n, **kw: ops.pack_conv(sd[u + n + ".weight"], sd[u + n + ".bias"], **kw)
-        cat = lambda a, b, s: torch.cat([sd[u + a + s], sd[u + b + s]], 0)
         self.convc1 = g("encoder.convc1")
         self.convf1 = g("encoder.convf1", flat_cs=4)
         self.convf2 = g("encoder.convf2")
@@ -152,88 +212,72 @@ class RaftEngine:
         self.fh2_frag = (ops.pack_flowhead_frags(sd[u + "flow_head.conv2.weight"], 2 if precision in ("bf16x3", "f16mx8") else 1,
                                                  f16=precision == "fp16")
                          if precision != "fp32" and FUSE_FLOWHEAD else None)
-        if small:
-            self.zr = [ops.pack_conv(cat("gru.convz", "gru.convr", ".weight"), cat("gru.convz", "gru.convr", ".bias"))]
-            self.q = [g("gru.convq")]
-        else:
+        if not small:
             self.convc2 = g("encoder.convc2")
-            self.zr = [ops.pack_conv(cat("gru.convz1", "gru.convr1", ".weight"),
-                                     cat("gru.convz1", "gru.convr1", ".bias"), padding=(0, 2)),
-                       ops.pack_conv(cat("gru.convz2", "gru.convr2", ".weight"),
-                                     cat("gru.convz2", "gru.convr2", ".bias"), padding=(2, 0))]
-            self.q = [g("gru.convq1", padding=(0, 2)), g("gru.convq2", padding=(2, 0))]
             self.mk1 = g("mask.0")
             self.mk2 = g("mask.2", scale=0.25)         # ".25 * self.mask(net)"  update.py:135
         # The GRU convs see [h | inp | motion] (update.py:22-31, 45-60, 127-131) and `inp` (the context features) is the
         # same in every iteration: conv(W, [h, inp, motion]) = conv(W_[h,motion], [h, motion]) + conv(W_inp, inp).
-        # The second term (+ bias) is computed once per source image (gate_inp) and enters the iterations as a
-        # per-pixel bias; the per-iteration convs (gate_dyn) run without the context channels.
+        # The second term (+ bias) is computed once per source image (zr_inp / q_inp -> the plan's gate_bias) and enters the
+        # iterations as a per-pixel bias; the per-iteration convs (zr_dyn / q_dyn) run without the context channels.
+        # One entry per GRU (half) step: the small model's single 3x3 step, the full model's 1x5 and 5x1 steps.
         hd_, cd_, mot = sp.hdim, sp.cdim, (82 if small else 128)
         dyn = [(0, hd_, 0), (hd_ + cd_, hd_ + cd_ + mot, hd_)]              # h -> 0.., motion(+flow) -> hd..
         ctx = [(hd_, hd_ + cd_, 0)]
-        if small:
-            zr_w = [(cat("gru.convz", "gru.convr", ".weight"), cat("gru.convz", "gru.convr", ".bias"), None)]
-            q_w = [(sd[u + "gru.convq.weight"], sd[u + "gru.convq.bias"], None)]
+        self.zr_dyn, self.zr_inp, self.q_dyn, self.q_inp = [], [], [], []
+        for sfx, pd in (("", None),) if small else (("1", (0, 2)), ("2", (2, 0))):
+            zr_w, zr_b = (torch.cat([sd[f"{u}gru.convz{sfx}{s}"], sd[f"{u}gru.convr{sfx}{s}"]], 0) for s in (".weight", ".bias"))
+            q_w, q_b = sd[f"{u}gru.convq{sfx}.weight"], sd[f"{u}gru.convq{sfx}.bias"]
+            self.zr_dyn.append(ops.pack_conv(zr_w, None, padding=pd, cin_layout=dyn))
+            self.zr_inp.append(ops.pack_conv(zr_w, zr_b, padding=pd, cin_layout=ctx))
+            self.q_dyn.append(ops.pack_conv(q_w, None, padding=pd, cin_layout=dyn))
+            self.q_inp.append(ops.pack_conv(q_w, q_b, padding=pd, cin_layout=ctx))
+
+    def _pack_weight_head(self, sd):
+        sp, precision = self.spec, self.precision
+        w = "weight_head.net."
+        # class_params.weight_head_structure (weighted_raft.py:318-345) = the state-dict's layers net.0, net.2, ..., a ReLU after
+        # each, then the closing 1x1 conv.  The shipped configs' [(128, 3)] * 3 (optical_flow/configs/v2_SNOB_large_g05_RAFT.py:16)
+        # has its own kernels (first layer fused into the second's launch, mean fused into the third's epilogue, evaluated on
+        # a subset of the windows); any other structure runs layer by layer on every window (wh_std = False).
+        idx, shapes, ok = _head_layers(sd, w, sp.levels + 1)
+        if not ok:
+            raise ValueError(f"weight head layers {shapes}: not a WeightHead (weighted_raft.py:318-345)")
+        self.wh_std = shapes == [(128, 5, 3, 3), (128, 128, 3, 3), (128, 128, 3, 3), (1, 128, 1, 1)]
+        last = idx[-1]
+        if self.wh_std:
+            self.wh0 = ops.pack_conv(sd[w + "0.weight"], sd[w + "0.bias"], flat_cs=8)
+            self.wh2 = ops.pack_conv(sd[w + "2.weight"], sd[w + "2.bias"])
+            self.wh4 = ops.pack_conv(sd[w + "4.weight"], sd[w + "4.bias"])
+            # first conv as MFMA fragments for the fused two-layer launch (split-bf16 precisions, 9x9 windows)
+            self.wh0_frag = (ops.pack_wh0_frags(sd[w + "0.weight"], 2 if self.prec_wh == "bf16x3" else 1)
+                             if precision != "fp32" and sp.nwin == 9 else None)
         else:
-            zr_w = [(cat("gru.convz1", "gru.convr1", ".weight"), cat("gru.convz1", "gru.convr1", ".bias"), (0, 2)),
-                    (cat("gru.convz2", "gru.convr2", ".weight"), cat("gru.convz2", "gru.convr2", ".bias"), (2, 0))]
-            q_w = [(sd[u + "gru.convq1.weight"], sd[u + "gru.convq1.bias"], (0, 2)),
-                   (sd[u + "gru.convq2.weight"], sd[u + "gru.convq2.bias"], (2, 0))]
-        self.zr_dyn = [ops.pack_conv(w_, None, padding=pd, cin_layout=dyn) for w_, _, pd in zr_w]
-        self.zr_inp = [ops.pack_conv(w_, b_, padding=pd, cin_layout=ctx) for w_, b_, pd in zr_w]
-        self.q_dyn = [ops.pack_conv(w_, None, padding=pd, cin_layout=dyn) for w_, _, pd in q_w]
-        self.q_inp = [ops.pack_conv(w_, b_, padding=pd, cin_layout=ctx) for w_, b_, pd in q_w]
-        if weighted:
-            w = "weight_head.net."
-            # class_params.weight_head_structure (weighted_raft.py:318-345) = the state-dict's layers net.0, net.2, ..., a ReLU after
-            # each, then the closing 1x1 conv.  The shipped configs' [(128, 3)] * 3 (optical_flow/configs/v2_SNOB_large_g05_RAFT.py:16)
-            # has its own kernels (first layer fused into the second's launch, mean fused into the third's epilogue, evaluated on
-            # a subset of the windows); any other structure runs layer by layer on every window (wh_std = False).
-            idx = sorted(int(k.split(".")[2]) for k in sd if k.startswith(w) and k.endswith(".weight"))
-            shapes = [tuple(sd[f"{w}{i}.weight"].shape) for i in idx]
-            if len(idx) < 2 or shapes[-1][0] != 1 or shapes[-1][2:] != (1, 1) or shapes[0][1] != sp.levels + 1 \
-                    or any(a[0] != b[1] for a, b in zip(shapes, shapes[1:])) or any(sh[2] != sh[3] or sh[2] % 2 == 0 for sh in shapes):
-                raise ValueError(f"weight head layers {shapes}: not a WeightHead (weighted_raft.py:318-345)")
-            self.wh_std = shapes == [(128, 5, 3, 3), (128, 128, 3, 3), (128, 128, 3, 3), (1, 128, 1, 1)]
-            last = idx[-1]
-            if self.wh_std:
-                self.wh0 = ops.pack_conv(sd[w + "0.weight"], sd[w + "0.bias"], flat_cs=8)
-                self.wh2 = ops.pack_conv(sd[w + "2.weight"], sd[w + "2.bias"])
-                self.wh4 = ops.pack_conv(sd[w + "4.weight"], sd[w + "4.bias"])
-                # first conv as MFMA fragments for the fused two-layer launch (split-bf16 precisions, 9x9 windows)
-                self.wh0_frag = (ops.pack_wh0_frags(sd[w + "0.weight"], 2 if self.prec_wh == "bf16x3" else 1)
-                                 if precision != "fp32" and self.spec.nwin == 9 else None)
-            else:
-                # generic head: the first layer reads the 5-channel patches -- "flat" packing (8 floats per window position)
-                # while kernel * 8 <= 32, else 32-channel rows; the other layers are ordinary convs on (windows, n, n, C)
-                k0 = shapes[0][2]
-                self.wh_flat0 = k0 * 8 <= 32
-                self.wh_layers = [ops.pack_conv(sd[f"{w}{idx[0]}.weight"], sd[f"{w}{idx[0]}.bias"], flat_cs=8 if self.wh_flat0 else 0)]
-                self.wh_layers += [ops.pack_conv(sd[f"{w}{i}.weight"], sd[f"{w}{i}.bias"]) for i in idx[1:-1]]
-                self.wh0_frag = None
-            self.wh6_c = shapes[-1][1]
-            self.wh6_w = torch.zeros(_ru(self.wh6_c, 4))
-            self.wh6_w[:self.wh6_c] = sd[f"{w}{last}.weight"].reshape(-1)
-            self.wh6_w = self.wh6_w.contiguous().cuda()
-            self.wh6_b = float(sd[f"{w}{last}.bias"].item())
-        self.mask_head = bool(mask_head)
-        if self.mask_head:
-            if not weighted:
-                raise ValueError("mask_head: the MaskHead belongs to WeightedRAFT (weighted_raft.py:75-76), not to plain RAFT")
-            m = "mask_head.net."
-            # class_params.mask_head_structure (weighted_raft.py:387-409) = the layers net.0, net.2, ... on [fmap1 | warped fmap2]
-            # (2 * fdim channels), a ReLU after each, then the closing 1x1 conv to one logit channel
-            idx = sorted(int(k.split(".")[2]) for k in sd if k.startswith(m) and k.endswith(".weight"))
-            shapes = [tuple(sd[f"{m}{i}.weight"].shape) for i in idx]
-            if len(idx) < 2 or shapes[-1][0] != 1 or shapes[-1][2:] != (1, 1) or shapes[0][1] != 2 * sp.fdim \
-                    or any(a[0] != b[1] for a, b in zip(shapes, shapes[1:])) or any(sh[2] != sh[3] or sh[2] % 2 == 0 for sh in shapes):
-                raise ValueError(f"mask head layers {shapes}: not a MaskHead on {2 * sp.fdim} channels (weighted_raft.py:387-409)")
-            self.mh_shapes = shapes
-            self.mh_layers = [ops.pack_conv(sd[f"{m}{i}.weight"], sd[f"{m}{i}.bias"]) for i in idx[:-1]]
-            self.mh_c = shapes[-1][1]
-            self.mh_wlast = sd[f"{m}{idx[-1]}.weight"].reshape(-1).clone()
-            self.mh_b = float(sd[f"{m}{idx[-1]}.bias"].item())
-        self._plans = {}
+            # generic head: the first layer reads the 5-channel patches -- "flat" packing (8 floats per window position)
+            # while kernel * 8 <= 32, else 32-channel rows; the other layers are ordinary convs on (windows, n, n, C)
+            k0 = shapes[0][2]
+            self.wh_flat0 = k0 * 8 <= 32
+            self.wh_layers = [ops.pack_conv(sd[f"{w}{idx[0]}.weight"], sd[f"{w}{idx[0]}.bias"], flat_cs=8 if self.wh_flat0 else 0)]
+            self.wh_layers += [ops.pack_conv(sd[f"{w}{i}.weight"], sd[f"{w}{i}.bias"]) for i in idx[1:-1]]
+        self.wh6_c = shapes[-1][1]
+        self.wh6_w = torch.zeros(_ru(self.wh6_c, 4))
+        self.wh6_w[:self.wh6_c] = sd[f"{w}{last}.weight"].reshape(-1)
+        self.wh6_w = self.wh6_w.contiguous().cuda()
+        self.wh6_b = float(sd[f"{w}{last}.bias"].item())
+
+    def _pack_mask_head(self, sd):
+        sp = self.spec
+        m = "mask_head.net."
+        # class_params.mask_head_structure (weighted_raft.py:387-409) = the layers net.0, net.2, ... on [fmap1 | warped fmap2]
+        # (2 * fdim channels), a ReLU after each, then the closing 1x1 conv to one logit channel
+        idx, shapes, ok = _head_layers(sd, m, 2 * sp.fdim)
+        if not ok:
+            raise ValueError(f"mask head layers {shapes}: not a MaskHead on {2 * sp.fdim} channels (weighted_raft.py:387-409)")
+        self.mh_shapes = shapes
+        self.mh_layers = [ops.pack_conv(sd[f"{m}{i}.weight"], sd[f"{m}{i}.bias"]) for i in idx[:-1]]
+        self.mh_c = shapes[-1][1]
+        self.mh_wlast = sd[f"{m}{idx[-1]}.weight"].reshape(-1).clone()
+        self.mh_b = float(sd[f"{m}{idx[-1]}.bias"].item())
 
     def plan(self, hp, wp, slot=0):
         """Buffers + launch programs for one padded input size.  slot: an independent second set for the same size (the
@@ -256,37 +300,54 @@ class _Plan:
     def __init__(self, eng, hp, wp):
         assert hp % 8 == 0 and wp % 8 == 0
         self.eng, self.hp, self.wp = eng, hp, wp
-        self.prec = eng.precision
+        self.prec, self.prec_corr, self.prec_wh = eng.precision, eng.prec_corr, eng.prec_wh
+        self.otf = eng.corr == "otf"
+        self.hf, self.wf, self.P = hp // 8, wp // 8, (hp // 8) * (wp // 8)
         self.source_tag = None
-        self.lookup_events = None
-        self.wh_events = None      # bench hook: list collecting (start, end) HIP events per lookup launch
+        self.target_valid = False  # the level-0 target map + operand belong to the image in img[1] (set by flow())
+        self.lookup_events = None  # bench hook: list collecting (start, end) HIP events per lookup launch
+        self.wh_events = None      # bench hook: (start, end, windows) around the weight head's first 128->128 layer
         self.conv_events = None    # bench hook: {tag: [(start, end)]} for the tagged conv launches of the iteration program
-        sp = eng.spec
-        hf, wf = hp // 8, wp // 8
-        self.hf, self.wf, self.P = hf, wf, hf * wf
-        P = self.P
-        dev = "cuda"
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        cp = self._cp
+        self._graphs = {}          # the flow provider's captured hipGraphs of this plan's flow(), by call signature
+        # what only some plans have: the full model's upsampling mask, a merged last iteration, the folded programs, fh_part (flow
+        # head folded into one conv launch: per-pixel partial products of its second conv), the two heads
+        self.mk = self.mask = self.prog_iter_last = self.folded = self.fh_part = None
+        self.x8 = self.x32 = self.wmean = self.wlow = self.cs_ws = self.cs_tot = self.wh6_b = self._wh6_pad = None
+        self.a1 = self.a2 = self.wh0_t = self.wh_last = None
+        self.wh0_direct = self.wh0_fused = self.wh_fused = False
+        self.prog_mask, self.prog_wh, self.prog_mh = [], [], []
+        self.mh_warped = self.mh_last = self.mh_w = self.mh_low = None
+        self.flow_region, self._flow_regions = None, {}        # None = every launch on the whole map (set_flow_region)
+        self.wh_region, self._wh_regions = None, {}            # None = every source pixel (set_weight_region)
+        self._wh_dyn = {}                                      # per region: (dynamic window list, its programs, scratch)
+        self._plan_features()
+        self._plan_update_block()
+        if eng.weighted:
+            self._plan_weight_head()
+        if eng.mask_head:
+            self._plan_mask_head()
 
+    @staticmethod
+    def _z(*s, dtype=torch.float32):
+        return torch.zeros(*s, dtype=dtype, device="cuda")
+
+    def _plan_features(self):
+        """Images, feature maps, the target pyramid / volumes, the context buffers; the encoder and volume programs."""
+        eng, sp, hp, wp, hf, wf, P, z = self.eng, self.eng.spec, self.hp, self.wp, self.hf, self.wf, self.P, self._z
         self.img = [new_act(1, hp, wp, 3, cs=4), new_act(1, hp, wp, 3, cs=4)]
-        # feature maps: f1 (source) and f2 rows (target, zero padded to the GEMM N tile)
         # source features: rows padded to the 128-row GEMM tile (pad rows stay zero), + their bf16 hi/lo planes
         self.f1rows = z(_ru(P, 128), sp.fdim)
         self.f1 = Act(self.f1rows[:P], 1, hf, wf, sp.fdim)
-        self.prec_corr, self.prec_wh = eng.prec_corr, eng.prec_wh
         x3 = self.prec_corr == "bf16x3"
-        bf = lambda rows: (torch.zeros(rows.shape[0], rows.shape[1] * (2 if x3 else 1), dtype=torch.bfloat16, device=dev)
+        bf = lambda rows: (z(rows.shape[0], rows.shape[1] * (2 if x3 else 1), dtype=torch.bfloat16)
                            if self.prec != "fp32" else None)       # GEMM operand: [hi|lo] lines / bf16 plane
         self.f1s = bf(self.f1rows)
-        if eng.corr == "otf" and self.prec == "fp32":
+        if self.otf and self.prec == "fp32":
             self.f1s = self.f1rows      # exact fp32 (terms = 0): the volume-free lookup reads the fp32 feature rows themselves
         # target feature pyramid: linear NHWC maps (f2act) and their rows in 4x4-tile order (f2rows, the B
         # operand of the correlation GEMM, zero padded to the N tile) -> volumes in the tiled layout
         # (corr = "otf": no volume; the lookup reads the row-major split maps f2s directly)
-        self.otf = eng.corr == "otf"
-        self.dims, self.f2rows, self.f2act, self.vol = [], [], [], []
-        self.f2s = []
+        self.dims, self.f2rows, self.f2act, self.vol, self.f2s = [], [], [], [], []
         h, w = hf, wf
         for _ in range(sp.levels):
             self.dims.append((h, w))
@@ -298,16 +359,16 @@ class _Plan:
                 rows = z(_ru(n, 128), sp.fdim)
                 self.f2rows.append(rows)
                 self.f2s.append(bf(rows))
-                vdt = torch.bfloat16 if eng.volume_storage == "bf16" else torch.float32
-                self.vol.append(torch.zeros(P, n, dtype=vdt, device=dev))
+                self.vol.append(z(P, n, dtype=torch.bfloat16 if eng.volume_storage == "bf16" else torch.float32))
             h, w = h // 2, w // 2
-        # context: GRU state and the GRU input buffer [inp | motion | flow | pad]
+        # context: GRU state and the GRU input buffer [inp | motion | flow | pad]; flow_cat = its flow channels onwards
         self.net0 = new_act(1, hf, wf, sp.hdim, zero=True)
         self.xbuf = new_act(1, hf, wf, sp.xdim, zero=True)
+        self.flow_cat = self.xbuf.t[:, sp.flow_off:]
         self._enc_scratch = {}
         n_stat = 2 * math.ceil((hp // 2) * (wp // 2) / 64) * 128
         self.stats = (z(n_stat), z(n_stat))
-        self.fin_ws = ops.inorm_ws(dev)
+        self.fin_ws = ops.inorm_ws("cuda")
         self._norm_slots = {}
         self.prog_f_src = self._encoder_program(eng.fnet, self.img[0], [(eng.fnet.conv2, self.f1, 0, EPI.EPI_LINEAR)])
         self.prog_f_dst = self._encoder_program(eng.fnet, self.img[1],
@@ -317,135 +378,125 @@ class _Plan:
                                                  (eng.cnet.conv2_inp, self.xbuf, 0, EPI.EPI_RELU)])
         self.prog_volume = self._volume_program()
 
-        # update block
+    def _plan_update_block(self):
+        """Buffers of the refinement loop, the lookup's parameters, the iteration programs and the upsampling-mask convs."""
+        eng, sp, hf, wf, P, z, cp = self.eng, self.eng.spec, self.hf, self.wf, self.P, self._z, self._cp
         self.coords = z(P, 2)
         self.corr = new_act(1, hf, wf, sp.corr_c, cs=sp.corr_cs, zero=True)
         self.c1 = new_act(1, hf, wf, 96 if sp.small else 256, zero=True)
         self.cf = new_act(1, hf, wf, 128 if sp.small else 256, zero=True)     # [cor | flo]
         self.fl1 = new_act(1, hf, wf, 64 if sp.small else 128, zero=True)
         self.flow4 = new_act(1, hf, wf, 2, cs=4, zero=True)
-        # per-pixel gate biases conv(W_inp, inp) + b: z|r and q of every GRU (half) step
+        # per-pixel gate biases conv(W_inp, inp) + b: z|r and q of every GRU (half) step ([h | motion] convs: see RaftEngine)
         self.inp_c = new_act(1, hf, wf, sp.cdim, zero=True)
         self.gate_bias = [(new_act(1, hf, wf, 2 * sp.hdim, zero=True), new_act(1, hf, wf, sp.hdim, zero=True))
                           for _ in eng.zr_inp]
         self.prog_gate_bias = []
         for k in range(len(eng.zr_inp)):
-            self.prog_gate_bias += [("conv", cp(self.inp_c, eng.zr_inp[k], self.gate_bias[k][0])),
-                                    ("conv", cp(self.inp_c, eng.q_inp[k], self.gate_bias[k][1]))]
+            self.prog_gate_bias += [Step("conv", cp(self.inp_c, eng.zr_inp[k], self.gate_bias[k][0])),
+                                    Step("conv", cp(self.inp_c, eng.q_inp[k], self.gate_bias[k][1]))]
         self.zbuf = new_act(1, hf, wf, sp.hdim, zero=True)
         self.rh = new_act(1, hf, wf, sp.hdim, zero=True)
         self.hA = new_act(1, hf, wf, sp.hdim, zero=True)
         self.hB = new_act(1, hf, wf, sp.hdim, zero=True)
         self.fh = new_act(1, hf, wf, 128 if sp.small else 256, zero=True)
-        self.fh_part = None        # flow head folded into one conv launch: per-pixel partial products of its second conv
         self.delta = new_act(1, hf, wf, 2, cs=4, zero=True)
         # warm start: the caller's flow_init is copied here, so that a captured graph reads it from a fixed address
         self.flow_init = z(2, hf, wf)
         if self.otf:
+            terms = 3 if self.prec_corr == "bf16x3" else (0 if self.prec == "fp32" else 1)
             self.lookup = ops.make_lookup_otf_params(self.f1s, self.f2s, self.dims, hf, wf, sp.fdim, self.coords,
-                                                     self.corr.t, sp.radius, 3 if x3 else (0 if self.prec == "fp32" else 1))
+                                                     self.corr.t, sp.radius, terms)
         else:
             self.lookup = ops.make_lookup_params(self.vol, self.dims, self.coords, self.corr.t, sp.radius)
         self.prog_iter_first = self._iter_program(first=True)
         self.prog_iter = self._iter_program(first=False)
-        self.prog_mask = []
         if not sp.small:
             self.mk = new_act(1, hf, wf, 256, zero=True)
             self.mask = new_act(1, hf, wf, 576, zero=True)
+            # (prog_mask, prog_wh and prog_mh are lists of conv parameter structs, not of Steps: flow() and the heads launch
+            #  them one by one, and the benchmark's roofline and the tests read the structs' fields)
             self.prog_mask = [cp(self.hB, eng.mk1, self.mk, epi=EPI.EPI_RELU),
                               cp(self.mk, eng.mk2, self.mask)]
             # last iteration: the flow head's conv and the mask head's first conv both read the final GRU state and are
             # independent (update.py:132-135) -> one launch when they select the same kernel instance (woft_conv2d_pair)
-            self.prog_iter_last = None
-            k = next((i for i, ent in enumerate(self.prog_iter) if len(ent) > 2 and ent[2] == "fh1"), None)
-            if PAIR_BRANCHES and k is not None and ops.pair_ok(self.prog_iter[k][1], self.prog_mask[0]):
-                self.prog_iter_last = (self.prog_iter[:k] + [("conv2", (self.prog_iter[k][1], self.prog_mask[0]), "fh1+mk1")]
+            k = next((i for i, st in enumerate(self.prog_iter) if st.tag == "fh1"), None)
+            if PAIR_BRANCHES and k is not None and ops.pair_ok(self.prog_iter[k].arg, self.prog_mask[0]):
+                self.prog_iter_last = (self.prog_iter[:k] + [Step("conv2", (self.prog_iter[k].arg, self.prog_mask[0]), "fh1+mk1")]
                                        + self.prog_iter[k + 1:])
-        self._fold = self._fold_gather_programs()
-        self.flow_region = None                          # None = every launch on the whole map (set_flow_region)
-        self._flow_regions = {}
-        if eng.weighted:
-            n = sp.nwin
-            self.x8 = new_act(P, n, n, 5, cs=8, zero=True)
-            self.wmean = z(P)
-            self.wlow = z(P)
-            self.cs_ws = torch.zeros(256, sp.fdim, dtype=torch.float64, device=dev)
-            self.cs_tot = torch.zeros(sp.fdim, dtype=torch.float64, device=dev)
-            self.wh6_b = torch.tensor([eng.wh6_b], dtype=torch.float32, device=dev)
-            self.wh_region = None                        # None = every source pixel
-            self._wh_regions = {}
-            self._wh_dyn = {}                            # per region: (dynamic window list, its programs, scratch)
-            if eng.wh_std:
-                self.a2 = new_act(P, n, n, 128)
-                # first conv (5 -> 128): scalar-operand VALU kernel straight from the lookup buffer for the 7x7 / 9x9
-                # windows (woft_wh_conv0), the generic conv on the packed x8 patches otherwise
-                self.wh0_direct = n in (7, 9)
-                self.wh0_fused = (eng.wh0_frag is not None and os.environ.get("WOFT_WH0_FUSED", "1") != "0"
-                                  and cp(self.a2, eng.wh2, self.a2, epi=EPI.EPI_RELU, precision=self.prec_wh).halo == 2)
-                # (with the first layer AND the tail fused into the two 128->128 launches only ONE activation exists)
-                self.a1 = self.a2 if self.wh0_fused else new_act(P, n, n, 128)
-                self.wh0_t = eng.wh0.wgt[:128].t().contiguous()          # [ky*32 + kx*8 + ci][co]
-                self.prog_wh, self.wh_fused = self._wh_program(P, None)
-                # the head restricted to a subset of the source pixels (set_weight_region): programs per region
-            else:
-                # any other weight_head_structure: layer by layer on every window, the closing 1x1 conv + window mean by
-                # woft_wh_reduce (no window subsets, no fused layers: a correct path, not a tuned one)
-                self.wh0_direct = self.wh0_fused = self.wh_fused = False
-                cpw = lambda *a, **kw: self._cp(*a, precision=self.prec_wh, **kw)
-                x = self.x8
-                if not eng.wh_flat0:                     # first kernel wider than 3: 32-channel rows instead of the flat 8
-                    self.x32 = new_act(P, n, n, 5, cs=32, zero=True)
-                    x = self.x32
-                # one activation per layer, zeroed once: a layer writes its cout channels only, so the pad channels that the next
-                # layer's 32-channel K chunks (and woft_wh_reduce) read against zero weights stay exact zeros for ever -- a buffer
-                # shared between layers of different widths would show a narrower layer what a wider one left behind (0 * inf = NaN)
-                self.prog_wh = []
-                for pc in eng.wh_layers:
-                    out = new_act(P, n, n, pc.cout, cs=_ru(_ru(pc.cout, 4), 32), zero=True)
-                    self.prog_wh.append(cpw(x, pc, out, epi=EPI.EPI_RELU))
-                    x = out
-                self.wh_last = x
-        if eng.mask_head:
-            # MaskHead (weighted_raft.py:295-309,387-422), after the last iteration on every source pixel (3x3 cross-pixel terms):
-            # woft_warp_features -> layers on the conv kernels (the first reads [f1 | warped] as two sources, no concatenated copy)
-            # -> closing 1x1 conv by woft_wh_reduce (nwin2 = 1) -> 1/8-resolution logits mh_low.  Arithmetic: the weight head's
-            # rule (prec_wh; the reference runs the head outside autocast).  One activation per layer, zeroed once (see above).
-            self.mh_warped = new_act(1, hf, wf, sp.fdim, zero=True)
-            self.prog_mh = []
-            x = None
-            for k, pc in enumerate(eng.mh_layers):
-                out = new_act(1, hf, wf, pc.cout, cs=_ru(_ru(pc.cout, 4), 32), zero=True)
-                if k == 0:
-                    self.prog_mh.append(self._cp(self.f1, pc, out, x2=self.mh_warped, c_split=sp.fdim, epi=EPI.EPI_RELU,
-                                                 precision=self.prec_wh))
-                else:
-                    self.prog_mh.append(self._cp(x, pc, out, epi=EPI.EPI_RELU, precision=self.prec_wh))
-                x = out
-            self.mh_last = x
-            self.mh_w = torch.zeros(x.cs, dtype=torch.float32)
-            self.mh_w[:eng.mh_c] = eng.mh_wlast
-            self.mh_w = self.mh_w.to(dev)
-            self.mh_low = z(P)
+        self.folded = self._fold_gather_programs()
+
+    def _plan_weight_head(self):
+        eng, sp, P, z, n = self.eng, self.eng.spec, self.P, self._z, self.eng.spec.nwin
+        self.x8 = new_act(P, n, n, 5, cs=8, zero=True)
+        self.wmean = z(P)
+        self.wlow = z(P)
+        self.cs_ws = z(256, sp.fdim, dtype=torch.float64)
+        self.cs_tot = z(sp.fdim, dtype=torch.float64)
+        self.wh6_b = torch.tensor([eng.wh6_b], dtype=torch.float32, device="cuda")
+        cpw = lambda *a, **kw: self._cp(*a, precision=self.prec_wh, **kw)
+        if eng.wh_std:
+            self.a2 = new_act(P, n, n, 128)
+            # first conv (5 -> 128): scalar-operand VALU kernel straight from the lookup buffer for the 7x7 / 9x9
+            # windows (woft_wh_conv0), the generic conv on the packed x8 patches otherwise
+            self.wh0_direct = n in (7, 9)
+            self.wh0_fused = (eng.wh0_frag is not None and os.environ.get("WOFT_WH0_FUSED", "1") != "0"
+                              and cpw(self.a2, eng.wh2, self.a2, epi=EPI.EPI_RELU).halo == 2)
+            # (with the first layer AND the tail fused into the two 128->128 launches only ONE activation exists)
+            self.a1 = self.a2 if self.wh0_fused else new_act(P, n, n, 128)
+            self.wh0_t = eng.wh0.wgt[:128].t().contiguous()          # [ky*32 + kx*8 + ci][co]
+            # (the head restricted to a subset of the source pixels -- set_weight_region -- has its own programs per region)
+            self.prog_wh, self.wh_fused = self._wh_program(P, None)
+            return
+        # any other weight_head_structure: layer by layer on every window, the closing 1x1 conv + window mean by
+        # woft_wh_reduce (no window subsets, no fused layers: a correct path, not a tuned one)
+        x = self.x8
+        if not eng.wh_flat0:                     # first kernel wider than 3: 32-channel rows instead of the flat 8
+            self.x32 = x = new_act(P, n, n, 5, cs=32, zero=True)
+        # one activation per layer, zeroed once: a layer writes its cout channels only, so the pad channels that the next
+        # layer's 32-channel K chunks (and woft_wh_reduce) read against zero weights stay exact zeros for ever -- a buffer
+        # shared between layers of different widths would show a narrower layer what a wider one left behind (0 * inf = NaN)
+        for pc in eng.wh_layers:
+            out = new_act(P, n, n, pc.cout, cs=_ru(_ru(pc.cout, 4), 32), zero=True)
+            self.prog_wh.append(cpw(x, pc, out, epi=EPI.EPI_RELU))
+            x = out
+        self.wh_last = x
+
+    def _plan_mask_head(self):
+        # MaskHead (weighted_raft.py:295-309,387-422), after the last iteration on every source pixel (3x3 cross-pixel terms):
+        # woft_warp_features -> layers on the conv kernels (the first reads [f1 | warped] as two sources, no concatenated copy)
+        # -> closing 1x1 conv by woft_wh_reduce (nwin2 = 1) -> 1/8-resolution logits mh_low.  Arithmetic: the weight head's
+        # rule (prec_wh; the reference runs the head outside autocast).  One activation per layer, zeroed once (_plan_weight_head).
+        eng, sp, hf, wf = self.eng, self.eng.spec, self.hf, self.wf
+        self.mh_warped = new_act(1, hf, wf, sp.fdim, zero=True)
+        x = None
+        for k, pc in enumerate(eng.mh_layers):
+            out = new_act(1, hf, wf, pc.cout, cs=_ru(_ru(pc.cout, 4), 32), zero=True)
+            src = dict(x2=self.mh_warped, c_split=sp.fdim) if k == 0 else {}
+            self.prog_mh.append(self._cp(self.f1 if k == 0 else x, pc, out, epi=EPI.EPI_RELU, precision=self.prec_wh, **src))
+            x = out
+        self.mh_last = x
+        self.mh_w = torch.zeros(x.cs, dtype=torch.float32)
+        self.mh_w[:eng.mh_c] = eng.mh_wlast
+        self.mh_w = self.mh_w.to("cuda")
+        self.mh_low = self._z(self.P)
 
     def _fold_gather_programs(self):
-        """Variants of the iteration programs in which the flow-head gather that ends iteration k is done by the lookup
-        launch that starts iteration k + 1 (woft_lookup_otf_params.fh_*): {id(program): variant, "gather": the last one}."""
-        progs = [self.prog_iter_first, self.prog_iter] + ([self.prog_iter_last] if getattr(self, "prog_iter_last", None) else [])
-        if not (FOLD_GATHER and self.otf and all(p and p[-1][0] == "fh_gather" and p[0][0] == "lookup" for p in progs)):
+        """-> the _Folded variants of the iteration programs, or None (switched off, the volume lookup, an unfused flow head)."""
+        progs = [p for p in (self.prog_iter_first, self.prog_iter, self.prog_iter_last) if p is not None]
+        if not (FOLD_GATHER and self.otf and all(p and p[-1].kind == "fh_gather" and p[0].kind == "lookup" for p in progs)):
             return None
-        n_planes, bias2 = self.prog_iter[-1][1]
-        lk = type(self.lookup).from_buffer_copy(self.lookup)
-        off = self.eng.spec.flow_off
-        flow_cat = self.xbuf.t[:, off:]
+        n_planes, bias2 = self.prog_iter[-1].arg
+        lk = ops.copy_params(self.lookup)
         lk.fh_part, lk.fh_bias, lk.fh_delta = _lib.ptr(self.fh_part), _lib.ptr(bias2), _lib.ptr(self.delta.t)
-        lk.fh_flow4, lk.fh_flow_cat = _lib.ptr(self.flow4.t), flow_cat.data_ptr()
+        lk.fh_flow4, lk.fh_flow_cat = _lib.ptr(self.flow4.t), self.flow_cat.data_ptr()
         lk.fh_planes, lk.fh_ld, lk.fh_ld_delta, lk.fh_ld_cat = n_planes, self.fh_part.shape[1], self.delta.cs, self.xbuf.cs
         lk._keep = (self.lookup._keep, bias2, self.fh_part)
-        out = {"gather": [self.prog_iter[-1]], "lookup": lk}
-        for p in progs:
-            head = p[0] if p is self.prog_iter_first else ("lookup", lk)
-            out[id(p)] = [head] + p[1:-1]
-        return out
+        # (the first iteration's lookup has no gather before it)
+        first, mid, last = ([head] + p[1:-1] if p is not None else None
+                            for p, head in ((self.prog_iter_first, self.prog_iter_first[0]), (self.prog_iter, Step("lookup", lk)),
+                                            (self.prog_iter_last, Step("lookup", lk))))
+        return _Folded(first, mid, last, [self.prog_iter[-1]], lk)
 
     def _wh_program(self, n_win, index):
         """Launch list of the head's 128->128 layers on n_win windows (all source pixels, or those listed in the
@@ -504,18 +555,28 @@ class _Plan:
         (and a trace, or a warm start, in flow()) runs every launch on the whole map; -> whether anything is restricted."""
         self.flow_region = None
         sp = self.eng.spec
-        if rect is None or iters is None or iters < 2 or sp.small or not self.otf or self._fold is None \
-                or getattr(self, "prog_iter_last", None) is None or len(self.eng.zr_dyn) != 2:
+        if rect is None or iters is None or iters < 2 or sp.small or not self.otf or self.folded is None \
+                or self.prog_iter_last is None or len(self.eng.zr_dyn) != 2:
             return False
         key = (tuple(int(v) for v in rect), int(iters))
         if key not in self._flow_regions:
-            self._flow_regions[key] = self._flow_region_programs(*key)
+            self._flow_regions[key] = self._flow_region_programs(*key, [self._iteration(it, key[1], True) for it in range(key[1])])
         self.flow_region = self._flow_regions[key]
         return self.flow_region is not None
 
-    def _flow_region_programs(self, rect, iters):
-        """-> {"key", "iters": {iteration: restricted program}, "rects": [(iteration, tag, [rect per part])]} or None when no launch is
-        smaller than the whole map."""
+    def _iteration(self, it, iters, folded):
+        """The launch program of refinement iteration `it` of `iters` (folded: from the set whose gathers run inside the next
+        iteration's lookup).  The merged last program is an iteration of its own kind: a single iteration is a first one."""
+        progs = self.folded if folded else self
+        if it == 0:
+            return progs.prog_iter_first
+        if it == iters - 1 and progs.prog_iter_last is not None:
+            return progs.prog_iter_last
+        return progs.prog_iter
+
+    def _flow_region_programs(self, rect, iters, base):
+        """base: the unrestricted (folded) program of every iteration -> {"key", "iters": {iteration: restricted program},
+        "rects": [(iteration, tag, [rect per part])]} or None when no launch is smaller than the whole map."""
         hf, wf = self.hf, self.wf
         taps = self._layer_taps()
         parts = {}
@@ -523,19 +584,18 @@ class _Plan:
             for _, pp in flow_region.iteration_launches(taps, first=first, last=True, folded=True):
                 for part in pp:
                     parts[(first, part[0])] = part
-        base = lambda it: self._fold[id(self.prog_iter_first if it == 0 else (self.prog_iter_last if it == iters - 1 else self.prog_iter))]
         launches, where = [], []
         for it in range(iters):
-            for k, ent in enumerate(base(it)):
-                if ent[0] == "lookup":
-                    names = (["gather"] if ent[1].fh_part else []) + ["lookup"]
-                elif ent[0] in ("conv", "conv2") and len(ent) > 2:
-                    names = ent[2].split("+")
+            for k, st in enumerate(base[it]):
+                if st.kind == "lookup":
+                    names = (["gather"] if st.arg.fh_part else []) + ["lookup"]
+                elif st.kind in ("conv", "conv2") and st.tag is not None:
+                    names = st.tag.split("+")
                 else:
                     return None                              # (a launch this derivation does not know: nothing is restricted)
                 if any((it == 0, n) not in parts for n in names):
                     return None
-                launches.append((it, ent[2] if len(ent) > 2 else "lookup", [parts[(it == 0, n)] for n in names]))
+                launches.append((it, st.tag or "lookup", [parts[(it == 0, n)] for n in names]))
                 where.append((it, k))
         launches += [(-1, tag, pp) for tag, pp in flow_region.closing_launches(taps)]
         rects, _ = flow_region.schedule(launches, flow_region.final_need(rect, hf, wf), hf, wf)
@@ -556,25 +616,24 @@ class _Plan:
                                       and 10 * tiles(halo, r) <= 9 * tiles(halo, None))
 
         def restricted(p, r):
-            q = type(p).from_buffer_copy(p)
-            q.__dict__.update(p.__dict__)                    # (the tensors the struct points to stay alive with it)
+            q = ops.copy_params(p)
             q.roi_y0, q.roi_x0, q.roi_h, q.roi_w = r
             return q
 
         progs = {}
         for (it, k), (_, tag, _), rr in zip(where, launches, rects):
-            ent = base(it)[k]
+            st = base[it][k]
             new = None
-            if ent[0] == "lookup" and small(rr[-1]):
-                lk = restricted(ent[1], rr[0])               # launched blocks: the gather's pixels (or, without one, the samples')
+            if st.kind == "lookup" and small(rr[-1]):
+                lk = restricted(st.arg, rr[0])               # launched blocks: the gather's pixels (or, without one, the samples')
                 lk.smp_y0, lk.smp_x0, lk.smp_h, lk.smp_w = rr[-1]
-                new = ("lookup", lk)
-            elif ent[0] == "conv" and ent[1].halo in ROI_HALOS and small(rr[0], ent[1].halo):
-                new = ("conv", restricted(ent[1], rr[0]), tag + "@roi")
-            elif ent[0] == "conv2" and ent[1][0].halo in ROI_HALOS and any(small(r, ent[1][0].halo) for r in rr):
-                new = ("conv2", tuple(restricted(p, r) if small(r, p.halo) else p for p, r in zip(ent[1], rr)), tag + "@roi")
+                new = Step("lookup", lk)
+            elif st.kind == "conv" and st.arg.halo in ROI_HALOS and small(rr[0], st.arg.halo):
+                new = Step("conv", restricted(st.arg, rr[0]), tag + "@roi")
+            elif st.kind == "conv2" and st.arg[0].halo in ROI_HALOS and any(small(r, st.arg[0].halo) for r in rr):
+                new = Step("conv2", tuple(restricted(p, r) if small(r, p.halo) else p for p, r in zip(st.arg, rr)), tag + "@roi")
             if new is not None:
-                progs.setdefault(it, list(base(it)))[k] = new
+                progs.setdefault(it, list(base[it]))[k] = new
         if not progs:
             return None
         return {"key": (rect, iters), "iters": progs,
@@ -613,7 +672,7 @@ class _Plan:
             if x[4] is None:
                 _, raw_x, mode, ms, _ = x
                 x[4] = self._scratch(f"{tag}_mat_{len(prog)}", 1, raw_x.h, raw_x.w, raw_x.c)
-                prog.append(("apply", (raw_x, x[4], mode - 1, None, ms, None, 0)))   # apply modes: 0 norm, 1 norm + relu
+                prog.append(Step("apply", (raw_x, x[4], mode - 1, None, ms, None, 0)))   # apply modes: 0 norm, 1 norm + relu
             return x[4]
 
         def layer(x, pc, name, relu, res=None, defer=False):
@@ -635,22 +694,22 @@ class _Plan:
             kw = dict(in_norm=in_norm, in_stats=in_stats) if in_norm else {}
             if not inorm:
                 epi = EPI.EPI_RELU_RES_RELU if res is not None else (EPI.EPI_RELU if relu else EPI.EPI_LINEAR)
-                prog.append(("conv", self._cp(xin, pc, out, epi=epi, e0=materialise(res) if res is not None else None, **kw)))
+                prog.append(Step("conv", self._cp(xin, pc, out, epi=epi, e0=materialise(res) if res is not None else None, **kw)))
                 return out
             raw = self._scratch(f"{tag}_raw_{name}", 1, ho, wo, pc.cout)
             p = self._cp(xin, pc, raw, stats=self.stats, **kw)
             rows = 2 * p._m_tiles
             ms = slot(name)
-            prog.append(("conv", p))
-            prog.append(("fin", (rows, pc.cout_pad, pc.cout, raw.cs, p._m, ms)))
+            prog.append(Step("conv", p))
+            prog.append(Step("fin", (rows, pc.cout_pad, pc.cout, raw.cs, p._m, ms)))
             if defer and res is None:
                 return ["raw", raw, 2 if relu else 1, ms, None]
             if res is None:
-                prog.append(("apply", (raw, out, 1 if relu else 0, None, ms, None, 0)))
+                prog.append(Step("apply", (raw, out, 1 if relu else 0, None, ms, None, 0)))
             elif isinstance(res, list) and res[4] is None:      # shortcut still raw: normalised inside this kernel
-                prog.append(("apply", (raw, out, 2, res[1], ms, res[3], res[2])))
+                prog.append(Step("apply", (raw, out, 2, res[1], ms, res[3], res[2])))
             else:
-                prog.append(("apply", (raw, out, 2, materialise(res), ms, None, 0)))
+                prog.append(Step("apply", (raw, out, 2, materialise(res), ms, None, 0)))
             return out
 
         # conv1's output and the 1x1 downsample branch stay raw where every consumer can normalise on the fly (the LDS-halo
@@ -666,7 +725,7 @@ class _Plan:
             x = layer(y, blk["convs"][-1], f"b{i}_o", True, res=res)
         x = materialise(x)
         for pc, out, co_off, epi in outputs:
-            prog.append(("conv", self._cp(x, pc, out, co_off=co_off, epi=epi)))
+            prog.append(Step("conv", self._cp(x, pc, out, co_off=co_off, epi=epi)))
         return prog
 
     def _volume_program(self):
@@ -676,20 +735,20 @@ class _Plan:
         x3 = self.prec_corr == "bf16x3"
         if self.otf and self.prec != "fp32" and PYRAMID_ONE_LAUNCH and sp.fdim % 32 == 0 and self.f2act[0].cs == sp.fdim and sp.levels <= 4:
             # pooled maps and split operands of all levels in one launch (was 2 * levels - 1 launches)
-            return [("pyramid", ops.PyramidArgs(self.f2act[:sp.levels], self.f2s[:sp.levels], 3 if x3 else 1))]
+            return [Step("pyramid", ops.PyramidArgs(self.f2act[:sp.levels], self.f2s[:sp.levels], 3 if x3 else 1))]
         for l in range(sp.levels):
             if l > 0:
-                prog.append(("pool", (self.f2act[l - 1], self.f2act[l])))
+                prog.append(Step("pool", (self.f2act[l - 1], self.f2act[l])))
             if self.otf:        # only the operands: pooled maps, split once (exact fp32: the maps themselves)
                 if self.prec != "fp32":
-                    prog.append(("split", (self.f2act[l].t, self.f2s[l])))
+                    prog.append(Step("split", (self.f2act[l].t, self.f2s[l])))
                 continue
-            prog.append(("tile", (self.f2act[l], self.f2rows[l])))
+            prog.append(Step("tile", (self.f2act[l], self.f2rows[l])))
             if self.prec == "fp32":
-                prog.append(("conv", ops.corr_volume(self.f1, self.f2rows[l], self.vol[l].shape[1], self.vol[l], alpha)))
+                prog.append(Step("conv", ops.corr_volume(self.f1, self.f2rows[l], self.vol[l].shape[1], self.vol[l], alpha)))
             else:               # both operands pre-split once, GEMM fed by LDS-DMA (woft_corr_gemm_bf16)
-                prog.append(("split", (self.f2rows[l], self.f2s[l])))
-                prog.append(("cgemm", (self.f1s, self.f2s[l], self.P, self.vol[l].shape[1], alpha, self.vol[l],
+                prog.append(Step("split", (self.f2rows[l], self.f2s[l])))
+                prog.append(Step("cgemm", (self.f1s, self.f2s[l], self.P, self.vol[l].shape[1], alpha, self.vol[l],
                                        3 if x3 else 1)))
         return prog
 
@@ -698,84 +757,65 @@ class _Plan:
         e, cp, sp = self.eng, self._cp, self.eng.spec
         hd = sp.hdim
         h_in = self.net0 if first else self.hB
-        prog = [("lookup", self.lookup)]
+        prog = [Step("lookup", self.lookup)]
         if sp.small:            # SmallMotionEncoder update.py:71-77: cor(96) | flo(32) -> 80, cat flow
-            prog += [("conv", cp(self.corr, e.convc1, self.cf, co_off=0, epi=EPI.EPI_RELU)),
-                     ("conv", cp(self.flow4, e.convf1, self.fl1, epi=EPI.EPI_RELU)),
-                     ("conv", cp(self.fl1, e.convf2, self.cf, co_off=96, epi=EPI.EPI_RELU)),
-                     ("conv", cp(self.cf, e.convm, self.xbuf, co_off=sp.cdim, epi=EPI.EPI_RELU))]
+            prog += [Step("conv", cp(self.corr, e.convc1, self.cf, co_off=0, epi=EPI.EPI_RELU)),
+                     Step("conv", cp(self.flow4, e.convf1, self.fl1, epi=EPI.EPI_RELU)),
+                     Step("conv", cp(self.fl1, e.convf2, self.cf, co_off=96, epi=EPI.EPI_RELU)),
+                     Step("conv", cp(self.cf, e.convm, self.xbuf, co_off=sp.cdim, epi=EPI.EPI_RELU))]
         else:                   # BasicMotionEncoder update.py:89-97: cor(192) | flo(64) -> 126, cat flow
-            flo = [("conv", cp(self.flow4, e.convf1, self.fl1, epi=EPI.EPI_RELU), "convf1"),
-                   ("conv", cp(self.fl1, e.convf2, self.cf, co_off=192, epi=EPI.EPI_RELU), "convf2")]
-            cor = [("conv", cp(self.corr, e.convc1, self.c1, epi=EPI.EPI_RELU), "convc1"),
-                   ("conv", cp(self.c1, e.convc2, self.cf, co_off=0, epi=EPI.EPI_RELU), "convc2")]
+            flo = [Step("conv", cp(self.flow4, e.convf1, self.fl1, epi=EPI.EPI_RELU), "convf1"),
+                   Step("conv", cp(self.fl1, e.convf2, self.cf, co_off=192, epi=EPI.EPI_RELU), "convf2")]
+            cor = [Step("conv", cp(self.corr, e.convc1, self.c1, epi=EPI.EPI_RELU), "convc1"),
+                   Step("conv", cp(self.c1, e.convc2, self.cf, co_off=0, epi=EPI.EPI_RELU), "convc2")]
             if PAIR_BRANCHES:
                 for c_, f_ in zip(cor, flo):             # (larger layer first: its workgroups are dispatched first)
-                    if ops.pair_ok(c_[1], f_[1]):
-                        prog.append(("conv2", (c_[1], f_[1]), c_[2] + "+" + f_[2]))
+                    if ops.pair_ok(c_.arg, f_.arg):
+                        prog.append(Step("conv2", (c_.arg, f_.arg), c_.tag + "+" + f_.tag))
                     else:
                         prog += [c_, f_]
             else:
                 prog += cor + flo
-            prog.append(("conv", cp(self.cf, e.convm, self.xbuf, co_off=sp.cdim, epi=EPI.EPI_RELU), "convm"))
-        # GRU half steps: z|r conv (sigmoid, r*h fused), q conv (tanh + state blend fused)
-        states = [h_in, self.hA, self.hB] if len(e.zr) == 2 else [h_in, self.hB]
-        if len(e.zr) == 1 and not first:
+            prog.append(Step("conv", cp(self.cf, e.convm, self.xbuf, co_off=sp.cdim, epi=EPI.EPI_RELU), "convm"))
+        # GRU half steps on [h | motion] (the inp term is the per-pixel gate bias, see RaftEngine): z|r conv (sigmoid, r*h fused),
+        # q conv (tanh + state blend fused)
+        steps = len(e.zr_dyn)
+        states = [h_in, self.hA, self.hB] if steps == 2 else [h_in, self.hB]
+        if steps == 1 and not first:
             states = [self.hB, self.hA]          # single-step GRU: ping-pong hB -> hA, copied back below
-        for k, (zr, q) in enumerate(zip(e.zr, e.q)):
+        for k in range(steps):
             hi, ho = states[k], states[k + 1]
-            if self.gate_bias is not None:      # [h | motion] only; the inp term is the per-pixel bias (see RaftEngine)
-                gz, gq = self.gate_bias[k]
-                pzr = cp(hi, e.zr_dyn[k], self.zbuf, x2=self.xbuf, x2_off=sp.cdim, c_split=hd,
-                         epi=EPI.EPI_GRU_ZR, split=hd, e0=hi, out1=self.rh, bias_map=gz)
-                pq = cp(self.rh, e.q_dyn[k], ho, x2=self.xbuf, x2_off=sp.cdim, c_split=hd,
-                        epi=EPI.EPI_GRU_Q, e0=hi, e1=self.zbuf, bias_map=gq)
-                prog += [("conv", pzr, f"gru_zr{k}"), ("conv", pq, f"gru_q{k}")]
-                continue
-            prog += [("conv", cp(hi, zr, self.zbuf, x2=self.xbuf, c_split=hd, epi=EPI.EPI_GRU_ZR, split=hd, e0=hi,
-                                 out1=self.rh)),
-                     ("conv", cp(self.rh, q, ho, x2=self.xbuf, c_split=hd, epi=EPI.EPI_GRU_Q, e0=hi, e1=self.zbuf))]
-        if len(e.zr) == 1 and not first:
-            prog.append(("copy", (self.hA.t, self.hB.t)))
+            gz, gq = self.gate_bias[k]
+            pzr = cp(hi, e.zr_dyn[k], self.zbuf, x2=self.xbuf, x2_off=sp.cdim, c_split=hd,
+                     epi=EPI.EPI_GRU_ZR, split=hd, e0=hi, out1=self.rh, bias_map=gz)
+            pq = cp(self.rh, e.q_dyn[k], ho, x2=self.xbuf, x2_off=sp.cdim, c_split=hd,
+                    epi=EPI.EPI_GRU_Q, e0=hi, e1=self.zbuf, bias_map=gq)
+            prog += [Step("conv", pzr, f"gru_zr{k}"), Step("conv", pq, f"gru_q{k}")]
+        if steps == 1 and not first:
+            prog.append(Step("copy", (self.hA.t, self.hB.t)))
         fused = None
         if e.fh2_frag is not None and e.fh2.cout == 2:
             if self.fh_part is None:
                 self.fh_part = torch.zeros(4 * self.P, 20, dtype=torch.float32, device="cuda")
             fused = ops.flowhead_params(self.hB, e.fh1, self.fh_part, e.fh2_frag, precision=self.prec)
         if fused is not None:                            # conv1 with conv2's partial products in its epilogue + the gather
-            prog += [("conv", fused, "fh1"), ("fh_gather", (fused._n_planes, e.fh2.bias[:2].contiguous()))]
+            prog += [Step("conv", fused, "fh1"), Step("fh_gather", (fused._n_planes, e.fh2.bias[:2].contiguous()))]
             return prog
-        prog.append(("conv", cp(self.hB, e.fh1, self.fh, epi=EPI.EPI_RELU), "fh1"))
+        prog.append(Step("conv", cp(self.hB, e.fh1, self.fh, epi=EPI.EPI_RELU), "fh1"))
         if ops.narrow_ok(self.fh, e.fh2):                # second conv + coords1 += delta in one launch
-            prog.append(("fh_update", (self.fh, e.fh2, self.delta)))
+            prog.append(Step("fh_update", (self.fh, e.fh2, self.delta)))
         else:
-            prog += [("conv", cp(self.fh, e.fh2, self.delta)), ("coords", None)]
+            prog += [Step("conv", cp(self.fh, e.fh2, self.delta)), Step("coords", None)]
         return prog
 
     # ---- execution ------------------------------------------------------------------------
     def run(self, prog):
-        for ent in prog:
-            kind, a = ent[0], ent[1]
-            if kind == "conv2":
-                ev = self.conv_events
-                if ev is not None and len(ent) > 2 and ent[2] in ev:
-                    s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    s.record()
-                    ops.run_conv_pair(*a)
-                    t.record()
-                    ev[ent[2]].append((s, t))
-                else:
-                    ops.run_conv_pair(*a)
-            elif kind == "conv":
-                ev = self.conv_events
-                if ev is not None and len(ent) > 2 and ent[2] in ev:
-                    s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    s.record()
-                    ops.run_conv(a)
-                    t.record()
-                    ev[ent[2]].append((s, t))
-                else:
-                    ops.run_conv(a)
+        ev = self.conv_events
+        for kind, a, tag in prog:
+            if kind == "conv":                               # (ev, a bench hook: HIP events around the launches whose tag it names)
+                ops.run_conv(a) if ev is None else _timed(ev.get(tag), ops.run_conv, a)
+            elif kind == "conv2":
+                ops.run_conv_pair(*a) if ev is None else _timed(ev.get(tag), ops.run_conv_pair, *a)
             elif kind == "fin":
                 rows, ld, c, c_pad, count, ms = a
                 ops.inorm_finalize(self.stats, rows, ld, c, count, ms[0], ms[1], channels_pad=c_pad, ws=self.fin_ws)
@@ -792,36 +832,22 @@ class _Plan:
                 ops.tile_rows(a[0], a[1])
             elif kind == "cgemm":
                 ops.corr_gemm_bf16(*a)
-            elif kind == "narrow":
-                ops.conv3x3_narrow(*a)
             elif kind == "lookup":
                 self._lookup(a)
             elif kind == "copy":
                 a[1].copy_(a[0])
             elif kind == "fh_gather":
-                off = self.eng.spec.flow_off
                 ops.flow_head_gather(self.fh_part, a[0], self.hf, self.wf, a[1], self.delta, self.coords, self.flow4.t,
-                                     self.xbuf.t[:, off:], self.xbuf.cs)
+                                     self.flow_cat, self.xbuf.cs)
             elif kind == "fh_update":
-                off = self.eng.spec.flow_off
-                ops.flow_head_update(a[0], a[1], a[2], self.coords, self.flow4.t, self.xbuf.t[:, off:], self.xbuf.cs)
+                ops.flow_head_update(a[0], a[1], a[2], self.coords, self.flow4.t, self.flow_cat, self.xbuf.cs)
             elif kind == "coords":
-                off = self.eng.spec.flow_off
-                ops.coords_update(self.coords, self.delta.t, self.delta.cs, self.wf, self.flow4.t,
-                                  self.xbuf.t[:, off:], self.xbuf.cs)
+                ops.coords_update(self.coords, self.delta.t, self.delta.cs, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
             else:
                 raise ValueError(kind)
 
     def _lookup(self, params):
-        run = ops.run_lookup_otf if self.otf else ops.run_lookup
-        if self.lookup_events is None:
-            run(params)
-            return
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        run(params)
-        e.record()
-        self.lookup_events.append((s, e))
+        _timed(self.lookup_events, ops.run_lookup_otf if self.otf else ops.run_lookup, params)
 
     def _split(self, rows, out):
         """fp32 rows -> the correlation GEMM's bf16 operand: [hi | lo] lines (bf16x3) or the bf16 plane (bf16)."""
@@ -840,7 +866,7 @@ class _Plan:
         target map: copied (fp32 map + correlation operand, two device copies) instead of a second fnet pass over the same image by
         the same launch program (bit-identical).  Volume-free correlation only (the volume mode keeps the target operand in
         4x4-tile order); -> whether the features were reused."""
-        reused = bool(reuse_target) and self.otf and getattr(self, "target_valid", False)
+        reused = bool(reuse_target) and self.otf and self.target_valid
         if reused:
             self.f1rows[:self.P].copy_(self.f2act[0].t.view(self.P, -1))
             if self.prec != "fp32":
@@ -850,9 +876,8 @@ class _Plan:
         self.run(self.prog_c_src)
         if self.prec != "fp32" and not reused:
             self._split(self.f1rows, self.f1s)
-        if self.gate_bias is not None:
-            self.inp_c.t.copy_(self.xbuf.t[:, :self.eng.spec.cdim])
-            self.run(self.prog_gate_bias)
+        self.inp_c.t.copy_(self.xbuf.t[:, :self.eng.spec.cdim])
+        self.run(self.prog_gate_bias)
         return reused
 
     def set_flow_init(self, flow_init):
@@ -887,59 +912,50 @@ class _Plan:
         self.run(self.prog_f_dst)
         self.run(self.prog_volume)
         self.target_valid = True                             # (level-0 target map + operand now belong to the image in img[1])
-        off = sp.flow_off
         if flow_init is None:
-            ops.coords_init(self.coords, self.hf, self.wf, self.flow4.t, self.xbuf.t[:, off:], self.xbuf.cs)
+            ops.coords_init(self.coords, self.hf, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
         else:
             if flow_init is not True:
                 self.set_flow_init(flow_init)
-            ops.coords_init_flow(self.coords, self.flow_init, self.hf, self.wf, self.flow4.t, self.xbuf.t[:, off:], self.xbuf.cs)
+            ops.coords_init_flow(self.coords, self.flow_init, self.hf, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
             if trace is not None:
                 trace(self, -1)
-        last = getattr(self, "prog_iter_last", None) if iters > 1 else None
-        fold = self._fold if trace is None else None        # (a trace reads the coordinates after every iteration)
+        folded = self.folded is not None and trace is None   # (a trace reads the coordinates after every iteration)
         # restricted iterations (set_flow_region): not under a trace (it reads whole maps) nor a warm start (flow_low is read everywhere)
         region = self.flow_region if (trace is None and flow_init is None) else None
         if region is not None and region["key"][1] != iters:
             region = None
         for it in range(iters):
-            prog = self.prog_iter_first if it == 0 else (last if (last is not None and it == iters - 1) else self.prog_iter)
-            if fold is not None:
-                prog = fold[id(prog)]
-            if region is not None:
-                prog = region["iters"].get(it, prog)
-            self.run(prog)
+            prog = self._iteration(it, iters, folded)
+            self.run(prog if region is None else region["iters"].get(it, prog))
             if trace is not None:
                 trace(self, it)
-        if fold is not None:
-            self.run(fold["gather"])
-        for p in (self.prog_mask[1:] if last is not None else self.prog_mask):
+        if folded:
+            self.run(self.folded.gather)
+        # (the merged last iteration ran the upsampling-mask head's first conv with the flow head's)
+        for p in self.prog_mask[1 if iters > 1 and self.prog_iter_last is not None else 0:]:
             ops.run_conv(p)
-        wlow = None
         if defer_wh:
             assert e.weighted and not sp.small and self.wh_region is not None and not e.mask_head
-            ops.convex_upsample(self.coords, None, self.mask.t, self.hf, self.wf, crop, h, w, flow_up=flow_up, dst=dst,
-                                wout=None, do_sigmoid=do_sigmoid)
+            self._upsample(None, crop, h, w, flow_up=flow_up, dst=dst, wout=None, do_sigmoid=do_sigmoid)
             return
         if e.weighted:
             self._weight_head(self.wh_region[1] if self.wh_region is not None else self.prog_wh,
                               self.wh_region[0] if self.wh_region is not None else None)
-            wlow = self.wlow
         wout = wout if e.weighted else None
-        if sp.small:                                                 # no mask head: bilinear x8 (utils.py:82-84)
-            ops.upflow8(self.coords, wlow, self.hf, self.wf, crop, h, w, flow_up=flow_up, dst=dst, wout=wout,
-                        do_sigmoid=do_sigmoid)
-        else:
-            ops.convex_upsample(self.coords, wlow, self.mask.t, self.hf, self.wf, crop, h, w, flow_up=flow_up,
-                                dst=dst, wout=wout, do_sigmoid=do_sigmoid)
+        self._upsample(self.wlow, crop, h, w, flow_up=flow_up, dst=dst, wout=wout, do_sigmoid=do_sigmoid)
         if e.mask_head:
             self._mask_head()
             if mout is not None:        # the weight channel of the same upsampling kernels, on the mask logits (weighted_raft.py:305-308)
-                if sp.small:
-                    ops.upflow8(self.coords, self.mh_low, self.hf, self.wf, crop, h, w, wout=mout, do_sigmoid=mask_sigmoid)
-                else:
-                    ops.convex_upsample(self.coords, self.mh_low, self.mask.t, self.hf, self.wf, crop, h, w, wout=mout,
-                                        do_sigmoid=mask_sigmoid)
+                self._upsample(self.mh_low, crop, h, w, wout=mout, do_sigmoid=mask_sigmoid)
+
+    def _upsample(self, wlow, crop, h, w, **outputs):
+        """Flow (and the 1/8-resolution map wlow) to full resolution: convex x8, or bilinear x8 on the small model, which has no
+        upsampling mask (utils.py:82-84)."""
+        if self.eng.spec.small:
+            ops.upflow8(self.coords, wlow, self.hf, self.wf, crop, h, w, **outputs)
+        else:
+            ops.convex_upsample(self.coords, wlow, self.mask.t, self.hf, self.wf, crop, h, w, **outputs)
 
     def _mask_head(self):
         """MaskHead on the final coordinates (weighted_raft.py:295-304, 411-422) -> self.mh_low (1/8-resolution logits)."""
@@ -947,9 +963,7 @@ class _Plan:
         ops.warp_features(self.f2act[0], self.coords, self.mh_warped)
         for p in self.prog_mh:
             ops.run_conv(p)
-        last = self.mh_last
-        _lib.check(_lib.load().woft_wh_reduce(_lib.ptr(last.t), last.cs, 1, _lib.ptr(self.mh_w), e.mh_b, self.P,
-                                              _lib.ptr(self.mh_low), _lib.stream_ptr()), "woft_wh_reduce")
+        ops.wh_reduce(self.mh_last, 1, self.mh_w, e.mh_b, self.P, self.mh_low)
 
     def finish_weights(self, pts, count, n_max, pad, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False,
                        w_points=None):
@@ -973,12 +987,11 @@ class _Plan:
             ops.convex_weights_at(pts, count, n_max, self.wlow, self.mask.t, self.hf, self.wf, crop, w_points,
                                   do_sigmoid=do_sigmoid)
             return
-        ops.convex_upsample(self.coords, self.wlow, self.mask.t, self.hf, self.wf, crop, h, w, flow_up=flow_up, dst=dst,
-                            wout=wout, do_sigmoid=do_sigmoid)
+        self._upsample(self.wlow, crop, h, w, flow_up=flow_up, dst=dst, wout=wout, do_sigmoid=do_sigmoid)
 
     def _wh6_padded(self, cs):
         """The closing 1x1 conv's weights padded with zeros to the activation's channel stride (woft_wh_reduce walks whole rows)."""
-        if getattr(self, "_wh6_pad", None) is None or self._wh6_pad.numel() != cs:
+        if self._wh6_pad is None or self._wh6_pad.numel() != cs:
             self._wh6_pad = torch.zeros(cs, dtype=torch.float32, device="cuda")
             self._wh6_pad[:self.eng.wh6_c] = self.eng.wh6_w[:self.eng.wh6_c]
         return self._wh6_pad
@@ -987,41 +1000,27 @@ class _Plan:
         """Final lookup + the weight head (weighted_raft.py:266-272, 347-384) on all source pixels (index None) or on the
         windows listed in `index` -> self.wlow."""
         e, sp = self.eng, self.eng.spec
-        if need is not None and self.otf:                        # final lookup, weighted_raft.py:266 -- only the 8x8
-            self.lookup.need = _lib.ptr(need)                    # blocks that hold a wanted window (volume-free lookup)
-            self._lookup(self.lookup)
+        if self.otf:                                             # final lookup, weighted_raft.py:266 -- with `need`, only the
+            self.lookup.need = _lib.ptr(need)                    # 8x8 blocks that hold a wanted window (volume-free lookup)
+        self._lookup(self.lookup)
+        if self.otf:
             self.lookup.need = None
-        else:
-            self._lookup(self.lookup)
-        lib = _lib.load()
         n = sp.nwin
-        _lib.check(lib.woft_colsum(_lib.ptr(self.f2act[0].t), self.P, sp.fdim, _lib.ptr(self.cs_ws), 256,
-                                   _lib.ptr(self.cs_tot), _lib.stream_ptr()), "woft_colsum")
-        _lib.check(lib.woft_wh_pack(_lib.ptr(self.corr.t), self.corr.cs, _lib.ptr(self.f1.t), sp.fdim,
-                                    _lib.ptr(self.cs_tot), 1.0 / (math.sqrt(float(sp.fdim)) * self.P), self.P, n,
-                                    _lib.ptr(self.wmean), None if self.wh0_direct else _lib.ptr(self.x8.t),
-                                    _lib.stream_ptr()), "woft_wh_pack")
-        if not e.wh_std and not e.wh_flat0:
+        ops.colsum(self.f2act[0].t, self.P, sp.fdim, self.cs_ws, self.cs_tot)
+        ops.wh_pack(self.corr, self.f1, self.cs_tot, 1.0 / (math.sqrt(float(sp.fdim)) * self.P), n, self.wmean,
+                    None if self.wh0_direct else self.x8)
+        if self.x32 is not None:
             self.x32.t[:, :8].copy_(self.x8.t)                   # (generic head, first kernel wider than 3)
         n_win = int(index.numel()) if index is not None else self.P
         if index is not None:
             self.wlow.zero_()                                    # pixels outside the region
         if self.wh0_direct and not self.wh0_fused:
-            _lib.check(lib.woft_wh_conv0(_lib.ptr(self.corr.t), self.corr.cs, _lib.ptr(self.wmean), n_win, n,
-                                         _lib.ptr(self.wh0_t), _lib.ptr(e.wh0.bias), _lib.ptr(self.a1.t),
-                                         _lib.ptr(index) if index is not None else None,
-                                         _lib.stream_ptr()), "woft_wh_conv0")
-        for k, p in enumerate(prog_wh):
-            if k == 0 and self.wh_events is not None:            # bench.py: HIP events around the first 128->128 layer
-                s, t = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record()
-                ops.run_conv(p)
-                t.record()
-                # (dynamic window list: the number of windows that really ran is on the device)
-                self.wh_events.append((s, t, n_win if n_needed is None else n_needed.clone()))
-            else:
-                ops.run_conv(p)
+            ops.wh_conv0(self.corr, self.wmean, n_win, n, self.wh0_t, e.wh0.bias, self.a1, index)
+        # bench hook: HIP events around the first 128->128 layer (dynamic window list: the number of windows that really ran is
+        # on the device)
+        _timed(self.wh_events, ops.run_conv, prog_wh[0], extra=lambda: n_win if n_needed is None else n_needed.clone())
+        for p in prog_wh[1:]:
+            ops.run_conv(p)
         if not self.wh_fused:
             last = self.a1 if e.wh_std else self.wh_last
-            _lib.check(lib.woft_wh_reduce(_lib.ptr(last.t), last.cs, n * n, _lib.ptr(self._wh6_padded(last.cs)), e.wh6_b, self.P,
-                                          _lib.ptr(self.wlow), _lib.stream_ptr()), "woft_wh_reduce")
+            ops.wh_reduce(last, n * n, self._wh6_padded(last.cs), e.wh6_b, self.P, self.wlow)

@@ -208,20 +208,19 @@ class RAFTWrapper:
                       flow_init=True if has_init else None)
         if not self.use_graph or plan.lookup_events is not None or plan.wh_events is not None or plan.conv_events is not None:
             return eager()
-        graphs = plan.__dict__.setdefault("_graphs", {})
         region = plan.wh_region
         fregion = plan.flow_region if not has_init else None     # (restricted iterations are other launches: other graphs)
         key = (iters, crop, oh, ow, weighted, do_sigmoid, want_flow, bool(defer_wh), o["flow"].data_ptr(),
                region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid), bool(has_init),
                fregion["key"] if fregion is not None else None)
-        g = graphs.get(key)
+        g = plan._graphs.get(key)
         if g is None:
             eager()                                        # this call's results; also the warm-up the capture needs
-            if key in graphs:                              # (second sighting: capture for the calls to come)
+            if key in plan._graphs:                              # (second sighting: capture for the calls to come)
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     eager()
-            graphs[key] = g
+            plan._graphs[key] = g
         else:
             g.replay()
 

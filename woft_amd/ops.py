@@ -711,6 +711,38 @@ def wh_needed(pts, count, n_max, top, left, hf, wf, index, bitmap, dyn_index, n_
                                      ptr(dyn_index), ptr(n_needed), stream_ptr()), "woft_wh_needed")
 
 
+def colsum(f, n_pix, c, ws, total):
+    """total[0..c) = fp64 column sums of the (n_pix, c) fp32 rows f; ws: (n_part, c) fp64 partial sums (woft_colsum)."""
+    check(_lib.load().woft_colsum(ptr(f), n_pix, c, ptr(ws), ws.shape[0], ptr(total), stream_ptr()), "woft_colsum")
+
+
+def wh_pack(lookup, f1, f2_total, alpha, nwin, mean, x8=None):
+    """The weight head's mean-response channel mean[p] = alpha * <f1[p], f2_total> and, with x8, the (p, nwin, nwin, 8) input
+    patches [4 lookup levels | mean] of its first conv (woft_wh_pack)."""
+    check(_lib.load().woft_wh_pack(ptr(lookup.t), lookup.cs, ptr(f1.t), f1.c, ptr(f2_total), alpha, f1.n_pix, nwin, ptr(mean),
+                                   ptr(x8.t) if x8 is not None else None, stream_ptr()), "woft_wh_pack")
+
+
+def wh_conv0(lookup, mean, n_win, nwin, wt, bias, out, index=None):
+    """The weight head's first conv + ReLU straight from the lookup buffer, on n_win windows (those of the source pixels listed
+    in `index`, else all) (woft_wh_conv0)."""
+    check(_lib.load().woft_wh_conv0(ptr(lookup.t), lookup.cs, ptr(mean), n_win, nwin, ptr(wt), ptr(bias), ptr(out.t), ptr(index),
+                                    stream_ptr()), "woft_wh_conv0")
+
+
+def wh_reduce(act, nwin2, w, bias, n_pix, out):
+    """out[p] = bias + mean over the nwin2 window positions of <w, act[p][t]>: closing 1x1 conv + window mean (woft_wh_reduce)."""
+    check(_lib.load().woft_wh_reduce(ptr(act.t), act.cs, nwin2, ptr(w), bias, n_pix, ptr(out), stream_ptr()), "woft_wh_reduce")
+
+
+def copy_params(p):
+    """A copy of a ctypes parameter struct that shares what the original carries besides its fields (_keep: the tensors its
+    pointers refer to stay alive with the copy too)."""
+    q = type(p).from_buffer_copy(p)
+    q.__dict__.update(p.__dict__)
+    return q
+
+
 def warp_features(f, coords, out):
     """out[p, :f.c] = bilinear_sampler(f, coords[p]) for the out.n_pix pixels (woft_warp_features; grid_sample, align_corners=True,
     zero padding: utils/utils.py:59-73)."""

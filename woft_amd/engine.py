@@ -27,7 +27,8 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib, flow_region, ops
+from . import _lib, conv_select, flow_region, ops
+from .conv_select import KERNELS, Kernel
 from .ops import Act, new_act
 
 EPI = _lib
@@ -43,8 +44,6 @@ PYRAMID_ONE_LAUNCH = os.environ.get("WOFT_PYRAMID", "1") != "0"    # target pyra
 # the flow-head gather of iteration k runs inside the lookup launch of iteration k + 1 (volume-free lookup; the last
 # iteration's as its own launch): one launch fewer per iteration, same operations in the same order (0: always its own launch)
 FOLD_GATHER = os.environ.get("WOFT_FOLD_GATHER", "1") != "0"
-# kernels that take an output rectangle (woft_conv_params.roi_*): the register-streamed conv and the streamed 1x1 / flat GEMM
-ROI_HALOS = (8, 12, 16)
 
 
 def _ru(x, m):
@@ -441,7 +440,7 @@ class _Plan:
             # windows (woft_wh_conv0), the generic conv on the packed x8 patches otherwise
             self.wh0_direct = n in (7, 9)
             self.wh0_fused = (eng.wh0_frag is not None and os.environ.get("WOFT_WH0_FUSED", "1") != "0"
-                              and cpw(self.a2, eng.wh2, self.a2, epi=EPI.EPI_RELU).halo == 2)
+                              and ops.select_conv(self.a2, eng.wh2, precision=self.prec_wh).kernel is Kernel.WINDOW_9X9)
             # (with the first layer AND the tail fused into the two 128->128 launches only ONE activation exists)
             self.a1 = self.a2 if self.wh0_fused else new_act(P, n, n, 128)
             self.wh0_t = eng.wh0.wgt[:128].t().contiguous()          # [ky*32 + kx*8 + ci][co]
@@ -509,11 +508,11 @@ class _Plan:
         prog = ([] if self.wh0_direct else [cp(self.x8, eng.wh0, a1, epi=EPI.EPI_RELU)]) + [
             cp(a1, eng.wh2, a2, epi=EPI.EPI_RELU), cp(a2, eng.wh4, a1, epi=EPI.EPI_RELU)]
         if self.wh0_fused:          # layers 1 + 2 in one launch: the first activation (1.3 GB at 1080p) never exists
-            assert prog[0].halo == 2
+            assert Kernel(prog[0].halo) is Kernel.WINDOW_9X9
             prog[0] = cp(a1, eng.wh2, a2, epi=EPI.EPI_RELU,
                          wh0=(self.corr, self.wmean, eng.wh0_frag, eng.wh0.bias, index))
         last = prog[-1]
-        fused = last.halo == 2
+        fused = Kernel(last.halo) is Kernel.WINDOW_9X9
         if fused:
             last.epi = EPI.EPI_WH_MEAN
             last.e0, last.e1 = _lib.ptr(eng.wh6_w), _lib.ptr(self.wh6_b)
@@ -599,21 +598,20 @@ class _Plan:
                 where.append((it, k))
         launches += [(-1, tag, pp) for tag, pp in flow_region.closing_launches(taps)]
         rects, _ = flow_region.schedule(launches, flow_region.final_need(rect, hf, wf), hf, wf)
-        cd = lambda a, b: -(-a // b)
 
-        def tiles(halo, r):
-            """Workgroups per column tile of a launch on rectangle r (None: the whole map) of a kernel's pixel tiling."""
+        def tiles(kernel, r):
+            """Workgroups per column tile of a launch on rectangle r (None: the whole map): a conv kernel's, or the lookup's 8x8 blocks."""
+            if kernel is not None:
+                return conv_select.roi_tiles(kernel, r, hf, wf)
             y0, x0, h, w = r or (0, 0, hf, wf)
-            if halo == 16:                                   # 64-pixel runs: along the rectangle's rows / of the linear pixel order
-                return h * cd(w, 64) if r else cd(hf * wf, 64)
-            ty = {8: 8, 12: 4}.get(halo)
-            return cd(h, ty) * cd(w, 16) if ty else (cd(y0 + h, 8) - y0 // 8) * (cd(x0 + w, 8) - x0 // 8)     # (else: the lookup's 8x8 blocks)
+            return (-(-(y0 + h) // 8) - y0 // 8) * (-(-(x0 + w) // 8) - x0 // 8)
 
         # a rectangle is handed to a kernel only where it saves a tenth of the launch's workgroups: a launch may always compute more
         # than it must, and e.g. 64-pixel runs along the rows of a rectangle a little narrower than the map are MORE workgroups
         # than the map's linear tiling (measured slower: profiles/flow_region_ab.txt)
-        small = lambda r, halo=None: (r is not None and not flow_region.is_full(r, hf, wf)
-                                      and 10 * tiles(halo, r) <= 9 * tiles(halo, None))
+        small = lambda r, kernel=None: (r is not None and not flow_region.is_full(r, hf, wf)
+                                        and 10 * tiles(kernel, r) <= 9 * tiles(kernel, None))
+        roi = lambda p: KERNELS[Kernel(p.halo)].roi              # (the kernel takes an output rectangle: woft_conv_params.roi_*)
 
         def restricted(p, r):
             q = ops.copy_params(p)
@@ -628,10 +626,10 @@ class _Plan:
                 lk = restricted(st.arg, rr[0])               # launched blocks: the gather's pixels (or, without one, the samples')
                 lk.smp_y0, lk.smp_x0, lk.smp_h, lk.smp_w = rr[-1]
                 new = Step("lookup", lk)
-            elif st.kind == "conv" and st.arg.halo in ROI_HALOS and small(rr[0], st.arg.halo):
+            elif st.kind == "conv" and roi(st.arg) and small(rr[0], Kernel(st.arg.halo)):
                 new = Step("conv", restricted(st.arg, rr[0]), tag + "@roi")
-            elif st.kind == "conv2" and st.arg[0].halo in ROI_HALOS and any(small(r, st.arg[0].halo) for r in rr):
-                new = Step("conv2", tuple(restricted(p, r) if small(r, p.halo) else p for p, r in zip(st.arg, rr)), tag + "@roi")
+            elif st.kind == "conv2" and roi(st.arg[0]) and any(small(r, Kernel(st.arg[0].halo)) for r in rr):
+                new = Step("conv2", tuple(restricted(p, r) if small(r, Kernel(p.halo)) else p for p, r in zip(st.arg, rr)), tag + "@roi")
             if new is not None:
                 progs.setdefault(it, list(base[it]))[k] = new
         if not progs:
@@ -684,8 +682,7 @@ class _Plan:
             xin, in_norm, in_stats = x, 0, None
             if isinstance(x, list):
                 _, raw_x, mode, ms, mat = x
-                probe = self._cp(raw_x, pc, raw_x, in_norm=mode, in_stats=ms) if mat is None else None
-                if probe is not None and probe.in_norm:
+                if mat is None and ops.select_conv(raw_x, pc, in_norm=mode, precision=self.prec).in_norm:
                     xin, in_norm, in_stats = raw_x, mode, ms
                 else:
                     xin = materialise(x)

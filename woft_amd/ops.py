@@ -12,8 +12,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, conv_select
 from ._lib import ConvParams, LookupOtfParams, LookupParams, check, ptr, stream_ptr
+from .conv_select import KERNELS, PRECISION, Kernel, pair_ok  # noqa: F401  (PRECISION, pair_ok: part of this module's interface)
 
 DEV = "cuda"
 
@@ -205,9 +206,10 @@ def fold_bn(weight, bias, bn_w, bn_b, mean, var, eps=1e-5):
     return w, b
 
 
-# "f16mx8" (round 4): fp16 main term + two block-scaled fp8 cross terms -- an fp32-emulating product in two matrix-pipe passes instead
-# of bf16x3's three (woft_conv_params.wgt_mx); layers whose kernel has no such instance run in bf16x3
-PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2, "fp16": 3, "f16mx8": 4}
+# PRECISION (conv_select's).  "f16mx8" (round 4): fp16 main term + two block-scaled fp8 cross terms -- an fp32-emulating product in two
+# matrix-pipe passes instead of bf16x3's three (woft_conv_params.wgt_mx); layers whose kernel has no such instance run in bf16x3
+#
+# Developer switches of the kernel selection (conv_select.Switches): module attributes, gathered by _switches() at every call.
 # which layers precision "f16mx8" actually runs in two passes: "auto" (default) = where it measured faster than bf16x3; "all" = every
 # multi-tap layer of the register-streamed kernel (the kernel tests use it)
 MX_LAYERS = os.environ.get("WOFT_MX_LAYERS", "auto")
@@ -217,36 +219,44 @@ USE_REGB = os.environ.get("WOFT_REGB", "1") != "0"
 REGB_TY4 = os.environ.get("WOFT_REGB_TY4", "1") != "0"
 USE_STEM = os.environ.get("WOFT_STEM", "1") != "0"        # 7x7 / stride-2 first layer on conv_stem.hip (0: gather kernel)
 USE_1X1 = os.environ.get("WOFT_1X1", "1") != "0"          # wide 1x1 layers on conv_1x1.hip (0: gather kernel)
-HALO_TILES = {1: (8, 16, 1), 2: (9, 9, 1), 4: (4, 16, 1), 7: (8, 16, 1), 8: (8, 16, 1), 12: (4, 16, 1)}     # (TY, TX, images per workgroup)
 HALO_MIN_BLOCKS = int(os.environ.get("WOFT_HALO_MIN_BLOCKS", "400"))
 WH_HALO = int(os.environ.get("WOFT_WH_HALO", "2"))
-
-
 TILE_MIN_BLOCKS = int(os.environ.get("WOFT_TILE_MIN_BLOCKS", "400"))
+assert conv_select.EPI_FLOWHEAD == _lib.EPI_FLOWHEAD
 
 
-def pick_tiles(m, cout_pad):
-    """Block tile: 128-wide in N when the padded cout allows; 128 rows in M when that still yields
-    at least TILE_MIN_BLOCKS workgroups (256 CUs), else 64."""
-    tn = 128 if cout_pad % 128 == 0 else 64
-    blocks128 = math.ceil(m / 128) * (cout_pad // tn)
-    tm = 128 if blocks128 >= TILE_MIN_BLOCKS else 64
-    return tm, tn
+def _switches():
+    return conv_select.Switches(USE_HALO, USE_REGB, REGB_TY4, USE_STEM, USE_1X1, WH_HALO, HALO_MIN_BLOCKS, TILE_MIN_BLOCKS,
+                                MX_LAYERS, os.environ.get("WOFT_MX_ZR", "12"))
 
 
 # ------------------------------------------------------------------------------------------
 # kernels
 # ------------------------------------------------------------------------------------------
+def select_conv(x, pc, epi=_lib.EPI_LINEAR, x2=None, stats=None, ho=None, wo=None, tiles=None, cout=None, precision=0, halo=None,
+                in_norm=0, bias_map=None, wh0=None, **_):
+    """conv_select.select() for the layer conv_params(x, pc, out, ...) would build, from the same arguments (the others are ignored)."""
+    if ho is None or wo is None:
+        ho, wo = pc.out_hw(x.h, x.w)
+    layer = conv_select.Layer(x.n, x.h, x.w, ho, wo, pc.taps_y, pc.taps_x, pc.stride, pc.pad_y, pc.pad_x, pc.cin_pad,
+                              cout or pc.cout, pc.cout_pad, pc.flat, x.cs, x2 is not None, stats is not None, int(in_norm or 0),
+                              bias_map is not None, wh0 is not None, epi)
+    return conv_select.select(layer, PRECISION.get(precision, precision), _switches(), tiles, halo)
+
+
 def conv_params(x, pc, out, co_off=0, epi=_lib.EPI_LINEAR, x2=None, c_split=0, e0=None, e1=None, out1=None,
                 split=0, alpha=1.0, stats=None, ho=None, wo=None, tiles=None, cout=None, precision=0, halo=None,
                 in_norm=0, in_stats=None, bias_map=None, x2_off=0, wh0=None):
-    """Build (and keep alive) a woft_conv_params for `out[:, co_off:co_off+cout] = epi(conv(x))`.
-    in_norm = 1 / 2 with in_stats = (mean, rstd): x is a RAW conv output, InstanceNorm (2: + ReLU) applied while
-    loading -- LDS-halo kernel only (check p.halo on the result; the caller falls back to woft_inorm_apply).
-    wh0 = (lookup Act, mean, fragments (pack_wh0_frags), bias, index | None): the weight head's first conv is
-    evaluated inside this launch from the lookup windows and x is not read (whole-window kernel only: p.halo == 2)."""
+    """Build (and keep alive) a woft_conv_params for `out[:, co_off:co_off+cout] = epi(conv(x))` on the kernel instance that
+    conv_select.select() picks (tiles, halo: its overrides).
+    in_norm = 1 / 2 with in_stats = (mean, rstd): x is a RAW conv output, InstanceNorm (2: + ReLU) applied while loading where
+    the kernel can (p.in_norm on the result; else the caller falls back to woft_inorm_apply).
+    wh0 = (lookup Act, mean, fragments (pack_wh0_frags), bias, index | None): the weight head's first conv is evaluated inside
+    this launch from the lookup windows and x is not read."""
     if ho is None or wo is None:
         ho, wo = pc.out_hw(x.h, x.w)
+    sel = select_conv(x, pc, epi=epi, x2=x2, stats=stats, ho=ho, wo=wo, tiles=tiles, cout=cout, precision=precision, halo=halo,
+                      in_norm=in_norm, bias_map=bias_map, wh0=wh0)
     p = ConvParams()
     p.in0, p.cs0 = ptr(x.t), x.cs
     if x2 is not None:                  # (x2_off: first channel of x2 used as the second source)
@@ -257,161 +267,36 @@ def conv_params(x, pc, out, co_off=0, epi=_lib.EPI_LINEAR, x2=None, c_split=0, e
     p.taps_y, p.taps_x, p.stride, p.pad_y, p.pad_x = pc.taps_y, pc.taps_x, pc.stride, pc.pad_y, pc.pad_x
     p.cin_pad, p.flat = pc.cin_pad, pc.flat
     p.wgt, p.bias, p.alpha = ptr(pc.wgt), ptr(pc.bias), alpha
-    p.wgt_hi, p.wgt_lo, p.precision = ptr(pc.wgt_hi), ptr(pc.wgt_lo), PRECISION.get(precision, precision)
-    if p.precision == 3:                # fp16 operands: the weight plane holds fp16 values
+    p.wgt_hi, p.wgt_lo, p.precision = ptr(pc.wgt_hi), ptr(pc.wgt_lo), sel.precision
+    if PRECISION.get(precision, precision) == conv_select.FP16:    # fp16 operands: the weight plane holds fp16 values
         p.wgt_hi, p.wgt_lo = ptr(pc.wgt_f16()), None
-    p.cout, p.cout_pad = (cout or pc.cout), pc.cout_pad
+    p.wgt_frag = p.wgt_mx = None
+    if KERNELS[sel.kernel].weights == conv_select.FRAG:  # weights in MFMA-fragment order (conv_regb.hip, conv_1x1.hip)
+        p.wgt_frag = ptr(pc.frag(2 if sel.precision == conv_select.BF16X3 else 1,
+                                 f16=sel.precision in (conv_select.FP16, conv_select.F16MX8)))
+        if sel.precision == conv_select.F16MX8:
+            p.wgt_mx = ptr(pc.frag_mx())
+    p.cout, p.cout_pad = (cout or pc.cout), sel.cout_pad
     p.out, p.ldo, p.co_off = ptr(out.t), out.cs, co_off
     p.out_w, p.out_pitch = (-12346 if SLOW_GATES else 0), 0
     p.epi, p.split = epi, split
     p.e0, p.lde0 = (ptr(e0.t), e0.cs) if e0 is not None else (None, 0)
     p.e1, p.lde1 = (ptr(e1.t), e1.cs) if e1 is not None else (None, 0)
     p.out1, p.ldo1 = (ptr(out1.t), out1.cs) if out1 is not None else (None, 0)
-    m = x.n * ho * wo
-    tm, tn = tiles or pick_tiles(m, pc.cout_pad)
-    if tiles is None and p.precision == 0 and tm == 128 and math.ceil(m / 128) * (pc.cout_pad // tn) < 2048:
-        tm = 64                         # fp32 kernel: 64-row tiles up to ~2000 workgroups (3-15 % per layer, gather_sweep.py fp32)
-    if tiles is None and p.precision != 0 and (pc.flat or pc.taps_y * pc.taps_x == 1):
-        tm, tn = 64, 64                 # short-K gather layers (1x1, flat 7x7): 64 x 64 tiles measured 5-35 % faster
-                                        # than 128-wide ones at every resolution of a 1080p frame (tools/gather_sweep.py)
-    if tiles is None and tn == 128 and stats is None and _round_up(p.cout, 64) < pc.cout_pad:
-        tn = 64                         # the last 64 columns of the 128-padded weight matrix are padding (cout 192, 576)
-    if tn == 64 and stats is None:
-        p.cout_pad = _round_up(p.cout, 64)              # column tiles actually launched (convc2: 3 instead of 4 x 64)
-    p.tile_m, p.tile_n = tm, tn
-    # LDS-halo kernel for the split-bf16 precisions on stride-1 multi-tap convs (see conv.hip)
-    auto_halo = halo is None
-    if halo is None:
-        halo = 0
-        if USE_HALO and p.precision != 0 and not pc.flat and pc.stride == 1 and pc.taps_y * pc.taps_x > 1 \
-                and (ho, wo) == (x.h, x.w) and (pc.taps_y, pc.taps_x) in ((3, 3), (1, 5), (5, 1)):
-            nt = pc.cout_pad // tn
-            if (x.h, x.w) == (9, 9) and tn == 128:
-                halo = WH_HALO if x.n >= 4 * 256 else 2
-            elif x.h >= 8 and x.w >= 16:
-                # Tile choice, measured on MI355X with tools/tile_sweep.py (1080p layer shapes).  Many independent
-                # workgroups beat larger tiles (16x16 / multi-patch workgroups run at 1 block per CU and lose to
-                # 8x16 by 1.5-3x): take the 8x16 pixel tile only while it still yields ~2 workgroups per CU, else 4x16.
-                b816 = x.n * math.ceil(ho / 8) * math.ceil(wo / 16)
-                auto = tiles is None
-                if auto and p.precision in (PRECISION["bf16"], PRECISION["fp16"]):
-                    # plain bf16 (one LDS plane, fewer registers): 64-channel column tiles win throughout --
-                    # 8x16 x 64 for the 256-wide layers (~1000 workgroups), 4x16 x 64 for the narrower ones
-                    tn = 64
-                    if stats is None:
-                        p.cout_pad = _round_up(p.cout, 64)
-                    halo = 1 if 4 * b816 * (p.cout_pad // 64) >= 7 * HALO_MIN_BLOCKS else 4   # (>= 700 workgroups)
-                else:
-                    # bf16x3: 64-channel column tiles (three workgroups per CU) unless their grid lands just over
-                    # one round of the 768 resident slots while the 128-wide tiles (two per CU) still fit in one
-                    # round -- the 256-wide layers at 1/8 of 1080p; 4x16 pixel tiles when 8x16 gives too few workgroups
-                    if auto:
-                        w64 = b816 * math.ceil(p.cout / 64)
-                        wide_ok = pc.cout_pad % 128 == 0 and b816 * (pc.cout_pad // 128) <= 512
-                        if tn == 128 and not (wide_ok and 768 < w64 < 1536):
-                            tn = 64
-                        if tn == 64 and stats is None:   # (with statistics the rows keep the padded width)
-                            p.cout_pad = _round_up(p.cout, 64)
-                    halo = 1 if b816 * (p.cout_pad // tn) >= HALO_MIN_BLOCKS else 4
-                p.tile_n = tn
-    # the encoders' first layer (7x7, stride 2, 3 -> 64 on the NHWC4 image, flat packing): its own kernel (conv_stem.hip, halo 7)
-    # -- bit-identical to the gather kernel, 8x16-pixel tiles (the statistics rows follow them)
-    if USE_STEM and auto_halo and halo == 0 and tiles is None and p.precision != 0 and pc.flat and x.cs == 4 and x2 is None \
-            and (pc.taps_y, pc.taps_x, pc.stride, pc.pad_y, pc.pad_x, pc.cin_pad) == (7, 1, 2, 3, 3, 32) \
-            and pc.cout_pad % 64 == 0 and not in_norm and bias_map is None and wh0 is None \
-            and (ho, wo) == ((x.h - 1) // 2 + 1, (x.w - 1) // 2 + 1):
-        halo = 7
-        p.tile_n = tn = 64
-    # stride-1 multi-tap layers without InstanceNorm plumbing: the kernel that streams the weights global -> registers
-    # (conv_regb.hip, halo 8) -- bit-identical, 1-8 % faster per layer on the update block's shapes (tools/regb_check.py)
-    if USE_REGB and auto_halo and halo in (1, 4) and tiles is None and stats is None and not in_norm and p.precision != 0:
-        p.tile_n = tn = (p.tile_n if halo == 1 else 64)
-        halo = 8
-    # the GRU q convs (1x5 / 5x1, 128 columns) on 4x16-pixel x 128-column tiles instead of 8x16 x 64: same workgroup count and
-    # per-wave work (64 rows x 32 columns), but the four waves are four column bands -- the weight fragments are fetched once
-    # per workgroup instead of by both row halves.  Alone -6...8 % per layer at 1/8 of 1080p; inside a frame +-0 at 1080p
-    # and 4K, +1.5 % frames/s at 720p.  (convm the same alone, nothing in a frame: left on 8x16 x 64; a layer that would pad
-    # to 128 columns -- convc2, 192 -> 256 -- loses 19 %.)  WOFT_REGB_TY4=0: off
-    if REGB_TY4 and auto_halo and halo == 8 and p.tile_n == 64 and pc.cout_pad % 128 == 0 and _round_up(p.cout, 64) == pc.cout_pad \
-            and (pc.taps_y, pc.taps_x) in ((1, 5), (5, 1)):
-        halo, p.tile_n = 12, 128
-    # wide 1x1 / stride-1 layers (convc1: 324 -> 256; the encoders' closing 128 -> 256): the streamed GEMM kernel (conv_1x1.hip, halo
-    # 16) -- 64 pixels x all 256 columns per workgroup, activations read and converted once per layer; bit-identical to the gather kernel
-    if USE_1X1 and auto_halo and halo == 0 and tiles is None and stats is None and not in_norm and wh0 is None and p.precision != 0 \
-            and not pc.flat and (pc.taps_y, pc.taps_x, pc.stride, pc.pad_y, pc.pad_x) == (1, 1, 1, 0, 0) and (ho, wo) == (x.h, x.w) \
-            and pc.cout_pad % 256 == 0 and _round_up(p.cout, 256) == pc.cout_pad:
-        # (layers that only fill 128-column tiles gain nothing: mask head conv2 256 -> 576 61.5 vs 59.9 us, 128 -> 128 13.8 vs 14.0)
-        halo = 16
-        p.tile_m, p.tile_n, p.cout_pad = 64, 256, pc.cout_pad
-        tm = 64
-    # ... and the flat-packed 7x7 conv on the flow (convf1, update.py:91) on the same kernel (128 columns per workgroup, K chunks = tap
-    # rows), so that it keeps sharing convc1's launch (pair_ok)
-    if USE_1X1 and auto_halo and halo == 0 and tiles is None and stats is None and not in_norm and wh0 is None and p.precision != 0 \
-            and pc.flat and x2 is None and (pc.taps_x, pc.stride, pc.cin_pad) == (1, 1, 32) and 2 * pc.pad_y + 1 == pc.taps_y \
-            and (ho, wo) == (x.h, x.w) and pc.cout_pad % 128 == 0 and _round_up(p.cout, 128) == pc.cout_pad:
-        halo = 16
-        p.tile_m, p.tile_n, p.cout_pad = 64, 128, pc.cout_pad
-        tm = 64
-    p.halo = halo
-    p.wgt_frag = None
-    p.wgt_mx = None
-    if p.precision == 4 and not (halo in (8, 12) and pc.taps_y * pc.taps_x > 1 and not in_norm):
-        p.precision = 1                 # f16mx8 exists on the register-streamed kernel's multi-tap instances: elsewhere bf16x3
-    if p.precision == 4 and MX_LAYERS == "auto":
-        # measured per layer at 1080p (profiles/r04_layer_times_f16mx8*.txt against ..._bf16x3.txt): the 3x3 layers are 8-10 % faster in
-        # f16mx8 than in bf16x3 (motion encoder, flow head, context encoder); the GRU's 1x5 / 5x1 z|r layers are 4-7 % slower (four row
-        # tiles per wave do not fit the 256 registers: half-size workgroups), the q layers equal, and the 128-column instance with a
-        # full-width store epilogue (mask head conv: spills) 75 vs 55 us -> those stay bf16x3
-        tn_mx = p.tile_n if p.tile_n in (64, 128) else (128 if pc.cout_pad % 128 == 0 else 64)
-        if (pc.taps_y, pc.taps_x) != (3, 3) or (tn_mx == 128 and pc.cout_pad % 128 == 0 and epi != _lib.EPI_FLOWHEAD):
-            p.precision = 1
-    if p.precision == 4 and halo == 8 and tiles is None and p.tile_n == 128:
-        # two row tiles per wave have the registers for the deep fragment pipeline; four (8 x 16 pixels x 128 columns) spill:
-        # 1x5 / 5x1 layers take the 4 x 16-pixel x 128-column layout (WOFT_MX_ZR = 12; 64: 64-column tiles; 128: keep)
-        # (3x3 layers keep their 128-column choice: that instance spills 40 bytes and still beats 64 columns, 52.7 vs 58.8 us on fh1)
-        if (pc.taps_y, pc.taps_x) in ((1, 5), (5, 1)) and pc.cout_pad % 128 == 0 and _round_up(p.cout, 128) == pc.cout_pad \
-                and os.environ.get("WOFT_MX_ZR", "12") == "12":
-            halo = p.halo = 12
-        elif (pc.taps_y, pc.taps_x) != (3, 3) and os.environ.get("WOFT_MX_ZR", "12") == "64":
-            p.tile_n = 64
-    if halo in (8, 12):                 # weights streamed to registers in MFMA-fragment order (conv_regb.hip)
-        assert p.precision != 0 and not pc.flat and pc.stride == 1 and not in_norm
-        assert (pc.taps_y, pc.taps_x) in ((3, 3), (1, 5), (5, 1)) and (ho, wo) == (x.h, x.w)
-        frag = pc.frag(2 if p.precision == 1 else 1, f16=p.precision in (3, 4))
-        p.wgt_frag = ptr(frag)
-        if p.precision == 4:
-            p.wgt_mx = ptr(pc.frag_mx())
-        if tiles is None and p.tile_n not in (64, 128):
-            p.tile_n = 128 if pc.cout_pad % 128 == 0 else 64
-        if halo == 12:
-            assert pc.cout_pad % 128 == 0 and pc.taps_y * pc.taps_x > 1
-            p.tile_n = 128
-        if p.tile_n == 128 and pc.cout_pad % 128 != 0:
-            p.tile_n = 64
-        p.cout_pad = pc.cout_pad if stats is not None else _round_up(p.cout, p.tile_n)
-    if halo == 16:
-        p.wgt_frag = ptr(pc.frag(2 if p.precision == 1 else 1, f16=p.precision == 3))
+    p.tile_m, p.tile_n, p.halo = sel.tile_m, sel.tile_n, sel.kernel
     p.bias_map, p.ld_bias_map = (ptr(bias_map.t), bias_map.cs) if bias_map is not None else (None, 0)
-    p.in_norm, p.in_mean, p.in_rstd = 0, None, None
-    if in_norm and halo in (1, 4) and (pc.taps_y, pc.taps_x) == (3, 3):   # (instantiated for the 3x3 pixel tiles)
-        p.in_norm, p.in_mean, p.in_rstd = int(in_norm), ptr(in_stats[0]), ptr(in_stats[1])
-    p._m_tiles = math.ceil(m / tm)
-    if halo in HALO_TILES:
-        ty, tx, g = HALO_TILES[halo]
-        p._m_tiles = math.ceil(x.n / g) * math.ceil(ho / ty) * math.ceil(wo / tx)
+    p.in_norm, p.in_mean, p.in_rstd = (sel.in_norm, ptr(in_stats[0]), ptr(in_stats[1])) if sel.in_norm else (0, None, None)
     if stats is not None:
-        rows = 2 * p._m_tiles
-        assert stats[0].numel() >= rows * pc.cout_pad
+        assert stats[0].numel() >= 2 * sel.m_tiles * pc.cout_pad
         p.stat_sum, p.stat_sq = ptr(stats[0]), ptr(stats[1])
     else:
         p.stat_sum, p.stat_sq = None, None
     if wh0 is not None:
         lk, mean, frag, b0, index = wh0
-        assert halo == 2 and p.precision != 0 and pc.cin_pad == 128, "fused first layer: 9x9 whole-window kernel only"
         p.wh0_lookup, p.wh0_ld, p.wh0_mean = ptr(lk.t), lk.cs, ptr(mean)
         p.wh0_w, p.wh0_bias, p.wh0_index = ptr(frag), ptr(b0), (ptr(index) if index is not None else None)
     p._keep = (x, x2, pc, out, e0, e1, out1, stats, in_stats, bias_map, wh0, p.wgt_frag and pc._frag)
-    p._m = m
+    p._m, p._m_tiles = x.n * ho * wo, sel.m_tiles
     return p
 
 
@@ -445,9 +330,9 @@ def pack_flowhead_frags(w2, planes, f16=False):
 
 def flowhead_params(x, pc, part, frags, **kw):
     """conv_params for FlowHead.conv1 with the second conv folded into its epilogue (WOFT_EPI_FLOWHEAD), or None when the
-    layer does not run on the register-streamed kernel (halo 8) here.  part: (planes * n_pix, >= 20) fp32."""
+    layer does not run on the register-streamed kernel (8 x 16 pixel tiles) here.  part: (planes * n_pix, >= 20) fp32."""
     p = conv_params(x, pc, Act(part, 1, x.h, x.w, 18), epi=_lib.EPI_FLOWHEAD, **kw)
-    if p.halo != 8 or pc.cout % 32 != 0:
+    if Kernel(p.halo) is not Kernel.REGB_8X16 or pc.cout % 32 != 0:
         return None
     n_planes = p.cout_pad // p.tile_n
     assert part.shape[0] >= n_planes * x.n_pix and part.shape[1] >= 20 and x.n == 1
@@ -461,23 +346,6 @@ def flow_head_gather(part, n_planes, h, w, bias2, delta, coords, flow4=None, flo
     check(_lib.load().woft_flow_head_gather(ptr(part), n_planes, part.shape[1], h, w, ptr(bias2), ptr(delta.t), delta.cs,
                                             ptr(coords), ptr(flow4), ptr(flow_cat), ld_cat, stream_ptr()),
           "woft_flow_head_gather")
-
-
-def pair_ok(a, b):
-    """True when woft_conv2d_pair takes the two layers in one launch (they select the same kernel instance)."""
-    if a.precision == 0 or a.precision != b.precision or a.halo != b.halo:
-        return False
-    if a.halo == 16:                                          # (conv_1x1.hip: a kernel whose workgroups pick their layer's tile form)
-        return not (a.stat_sum or b.stat_sum)
-    if a.tile_n != b.tile_n:
-        return False
-    if a.halo == 0 and a.tile_m != b.tile_m:                  # (the pixel-tile kernels ignore tile_m)
-        return False
-    if a.stat_sum or b.stat_sum or a.in_norm or b.in_norm:
-        return False
-    if a.halo == 0:
-        return True
-    return a.halo in (8, 12) and (a.taps_y, a.taps_x) == (b.taps_y, b.taps_x) and a.taps_y * a.taps_x > 1
 
 
 def run_conv_pair(a, b):
@@ -622,6 +490,7 @@ def corr_volume(f1, f2_rows, n_q, out, alpha, precision=0, f2_hi=None, f2_lo=Non
     p.out_w, p.out_pitch = 0, 0
     p.epi = _lib.EPI_LINEAR
     p.tile_m, p.tile_n = (128, 128) if f2_rows.shape[0] % 128 == 0 else (128, 64)
+    p.halo = Kernel.GATHER
     p._keep = (f1, f2_rows, out, f2_hi, f2_lo)
     return p
 

@@ -341,6 +341,40 @@ int woft_coords_init_flow(float* coords1, const float* flow_init, int32_t hf, in
  * -1 (before any launch) on a NULL pointer, flow == out, hf, wf <= 0 or hf*wf > 2^30. */
 int woft_forward_interpolate(const float* flow, int32_t hf, int32_t wf, float* out, void* stream);
 
+/* Flow sampling, chaining and the forward-backward check (csrc/flow_chain.hip; utils/interpolation.py).  DESIGN.md section 16.
+ * All planes contiguous fp32, [c][h][w]; flows [2][h][w], x plane first; grid coordinates x = column, y = row
+ * (utils/misc.py: torch_get_featuremap_coords).  One point / pixel per lane, no LDS, no atomics, no workspace.  Every integer
+ * index is formed from a float already clamped into the plane: no coordinate, finite or not, addresses outside it.
+ * h, w <= 2^24 (so that w - 1, h - 1 are exact in fp32).
+ *
+ * woft_sample_bilinear: bilinear_interpolate_torch (interpolation.py:92-133) in fp32, operation for operation.
+ *   x0 = floor(x), x1 = x0 + 1, both then clamped to [0, w-1] (y alike); the weights (x1-x)*(y1-y), (x1-x)*(y-y0),
+ *   (x-x0)*(y1-y), (x-x0)*(y-y0) from the CLAMPED corners as floats; out[ch][i] = ((wa*a + wb*b) + wc*c) + wd*d with
+ *   a = data[ch][y0][x0], b = [y1][x0], c = [y0][x1], d = [y1][x1], every product and sum rounded on its own (no FMA).
+ *   So, as in the reference: a point on or beyond the last row / column, or left of / above the first, samples 0 (weights
+ *   of equal corners cancel or vanish); a NaN or infinite coordinate gives NaN.  Bit-equal to the reference's CPU fp32
+ *   result for finite coordinates |v| <= 1e9 (beyond int64 the reference's float -> integer conversion is unspecified).
+ *   out: [c][n].  n == 0: nothing is launched.  -1 on a NULL pointer, c <= 0, n < 0, h or w <= 0 or > 2^24.
+ *
+ * The other two use this project's EDGE-EXACT sampler s(f, q) (the reference sampler's zeros on the last row / column would
+ * be wrong in a chain): q = ((float)x + fab_x, (float)y + fab_y) in fp32; q is valid iff 0 <= qx <= w-1 and 0 <= qy <= h-1
+ * (a NaN is not); x0 = floor(qx), x1 = min(x0+1, w-1), ax = qx - x0 (y alike);
+ * s = (1-ay)*((1-ax)*d00 + ax*d01) + ay*((1-ax)*d10 + ax*d11) per plane.
+ *
+ * woft_flow_chain: chain_flow (interpolation.py:9-23, unfinished there) as its docstring says: fac = fab + s(fbc, q); an
+ *   invalid q gives NaN in both planes (the fill_value of the reference's FlowInterpolator).  fac may not alias fbc.
+ *   -1 on a NULL pointer, h or w <= 0 or > 2^24.
+ *
+ * woft_flow_fb: forward-backward consistency.  b = s(fba, q); e2 = |fab + b|^2; bound = alpha*(|fab|^2 + |b|^2) + beta;
+ *   err[h][w] = sqrt(e2); ok[h][w] = 1.0f iff q is valid and e2 <= bound, else 0.0f.  An invalid q: err = +inf, ok = 0; a
+ *   NaN anywhere in the compare: ok = 0.  Either of err / ok may be NULL, not both.
+ *   -1 on a NULL flow, both outputs NULL, h or w <= 0 or > 2^24, alpha or beta negative, NaN or infinite. */
+int woft_sample_bilinear(const float* data, int32_t c, int32_t h, int32_t w, const float* x, const float* y, int64_t n,
+                         float* out, void* stream);
+int woft_flow_chain(const float* fab, const float* fbc, int32_t h, int32_t w, float* fac, void* stream);
+int woft_flow_fb(const float* fab, const float* fba, int32_t h, int32_t w, float alpha, float beta, float* err, float* ok,
+                 void* stream);
+
 /* Weight-head glue (weighted_raft.py:258-279, 347-384).
  * woft_colsum: total[c] = sum_q f[q][c] in fp64 (ws: [n_part][c] doubles).
  * woft_wh_pack: mean[p] = alpha * <f1[p], total>  (= mean_q vol[p,q], weighted_raft.py:358-361, in its

@@ -3,4 +3,7 @@ def __getattr__(name):
     if name == "forward_interpolate":
         from .warm import forward_interpolate
         return forward_interpolate
+    if name in ("chain_flow", "fb_consistency"):
+        from .interpolation import chain_flow, fb_consistency
+        return chain_flow if name == "chain_flow" else fb_consistency
     raise AttributeError(f"module 'woft_amd' has no attribute {name!r}")

@@ -83,7 +83,10 @@ _SIGS = {
     "woft_coords_init": (i32, [vp, i32, i32, vp, vp, i32, vp]),
     "woft_coords_init_flow": (i32, [vp, vp, i32, i32, vp, vp, i32, vp]),
     "woft_forward_interpolate": (i32, [vp, i32, i32, vp, vp]),
-    "woft_colsum": (i32, [vp, i64, i32, vp, i32, vp, vp]),
+    "woft_sample_bilinear": (i32, [vp, i32, i32, i32, vp, vp, i64, vp, vp]),
+    "woft_flow_chain": (i32, [vp, vp, i32, i32, vp, vp]),
+    "woft_flow_fb": (i32, [vp, vp, i32, i32, f32, f32, vp, vp, vp]),
+    "woft_colsum":(i32, [vp, i64, i32, vp, i32, vp, vp]),
     "woft_wh_pack": (i32, [vp, i32, vp, i32, vp, f32, i64, i32, vp, vp, vp]),
     "woft_wh_conv0": (i32, [vp, i32, vp, i64, i32, vp, vp, vp, vp, vp]),
     "woft_wh_reduce": (i32, [vp, i32, i32, vp, f32, i64, vp, vp]),

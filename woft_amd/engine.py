@@ -891,7 +891,7 @@ class _Plan:
         return self.flow4.t[:, :2].t().reshape(2, self.hf, self.wf).contiguous()
 
     def flow(self, iters, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False, trace=None, defer_wh=False,
-             mout=None, mask_sigmoid=False, flow_init=None):
+             mout=None, mask_sigmoid=False, flow_init=None, skip_wh=False):
         """Target features -> volume -> `iters` refinements -> full-resolution outputs.
         defer_wh (full weighted model with a weight region set): stop before the weight head -- flow_up / dst are final,
         wout is NOT written -- and let finish_weights() evaluate the head where the caller then says it reads the weights.
@@ -899,6 +899,8 @@ class _Plan:
         passed through a sigmoid); the head runs after the weight head whether or not mout is given.
         mask_sigmoid (the tracker's visibility request only): mout receives the sigmoid of those logits instead -- the do_sigmoid
         flag the upsampling kernels already have for the weight channel.
+        skip_wh (a caller that reads the flow only, e.g. the reverse flow of a forward-backward check): the weight head (and the
+        mask head) are not evaluated and wout / mout are not written; flow_up / dst do not depend on either head.
         flow_init (weighted_raft.py:184,223-224: coords1 = coords1 + flow_init): None = start from zero flow; a (2, hf, wf)
         tensor = copied into the plan's buffer first (set_flow_init); True = the buffer as it stands.  The first iteration's
         motion encoder reads it as the flow, the later coordinate updates write coords1 - coords0 as ever.  With a trace, the
@@ -934,6 +936,9 @@ class _Plan:
             ops.run_conv(p)
         if defer_wh:
             assert e.weighted and not sp.small and self.wh_region is not None and not e.mask_head
+            self._upsample(None, crop, h, w, flow_up=flow_up, dst=dst, wout=None, do_sigmoid=do_sigmoid)
+            return
+        if skip_wh:
             self._upsample(None, crop, h, w, flow_up=flow_up, dst=dst, wout=None, do_sigmoid=do_sigmoid)
             return
         if e.weighted:

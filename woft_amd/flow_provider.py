@@ -196,7 +196,7 @@ class RAFTWrapper:
             self._all_pixels.pop(key, None)
 
     def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True, mask_sigmoid=False,
-                  has_init=False):
+                  has_init=False, skip_wh=False):
         """plan.flow() eagerly, or -- use_graph -- as ONE hipGraph launch (captured at the second call with the same
         arguments; the per-launch event hooks of bench.py force the eager path).
         has_init: start from the plan's flow_init buffer (filled by the caller BEFORE this call: a replayed graph reads the
@@ -205,14 +205,14 @@ class RAFTWrapper:
             # (mode "TC" hands out dst = grid + flow only: the (2, H, W) flow map is then not written at all)
             plan.flow(iters, crop, oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"], wout=o["w"] if weighted else None,
                       do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"), mask_sigmoid=mask_sigmoid,
-                      flow_init=True if has_init else None)
+                      flow_init=True if has_init else None, skip_wh=skip_wh)
         if not self.use_graph or plan.lookup_events is not None or plan.wh_events is not None or plan.conv_events is not None:
             return eager()
         region = plan.wh_region
         fregion = plan.flow_region if not has_init else None     # (restricted iterations are other launches: other graphs)
         key = (iters, crop, oh, ow, weighted, do_sigmoid, want_flow, bool(defer_wh), o["flow"].data_ptr(),
                region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid), bool(has_init),
-               fregion["key"] if fregion is not None else None)
+               fregion["key"] if fregion is not None else None, bool(skip_wh))
         g = plan._graphs.get(key)
         if g is None:
             eager()                                        # this call's results; also the warm-up the capture needs
@@ -395,9 +395,37 @@ class RAFTWrapper:
             raise RuntimeError("flow_low(): no flow has been computed yet")
         return plan.flow_low() if copy else plan.flow4.t[:, :2].t().reshape(2, plan.hf, plan.wf)
 
+    def flow_map(self):
+        """After a computed compute_flow(mode='flow') or compute_flow(mode='TC', keep_flow=True): the (2, H, W) flow map of that
+        call -- the provider's own buffer, valid until the next call at the same output size."""
+        m = getattr(self, "_flow_map", None)
+        if m is None:
+            raise RuntimeError("flow_map(): the last flow wrote no flow map (mode 'TC' without keep_flow, or no flow yet)")
+        return m
+
+    def compute_flow_fb(self, src_img, dst_img, alpha=0.01, beta=0.5, numpy_out=False):
+        """Both flows of an image pair and their forward-backward consistency (no counterpart in raft.py)
+        -> (flow_fwd (2, H, W), flow_bwd (2, H, W), err (1, H, W), ok (1, H, W)) as tensors of the caller's own (numpy_out: arrays).
+        Two ordinary flows -- flow_fwd has the bits of compute_flow(src_img, dst_img, mode='flow'), flow_bwd those of
+        compute_flow(dst_img, src_img, mode='flow') -- and one woft_flow_fb launch: with b = flow_bwd sampled at pixel + flow_fwd,
+        err = |flow_fwd + b| and ok = 1.0 where that point is inside the frame and err^2 <= alpha * (|flow_fwd|^2 + |b|^2) + beta
+        (else 0.0; outside the frame err = +inf).  Every raft_type and every padding_mode the provider has; the flow cache is not
+        consulted.  Neither flow's weights are returned, so the weight head is skipped where the network allows it.
+        Like any other call it replaces the state the previous call left (borrowed buffers, deferred weights, flow_low())."""
+        alpha, beta = float(alpha), float(beta)
+        if not (0.0 <= alpha < float("inf")) or not (0.0 <= beta < float("inf")):
+            raise ValueError(f"compute_flow_fb: alpha and beta must be finite and >= 0, got {alpha!r}, {beta!r}")
+        # (each flow is cloned out of the per-size output buffers before the next one overwrites them)
+        fwd = self.compute_flow(src_img, dst_img, mode="flow", skip_weights=True)[0]
+        bwd = self.compute_flow(dst_img, src_img, mode="flow", skip_weights=True)[0]
+        err, ok = ops.flow_fb(fwd, bwd, alpha, beta)
+        out = (fwd, bwd, err[None], ok[None])
+        return tuple(t.cpu().numpy() for t in out) if numpy_out else out
+
     def compute_flow(self, src_img, dst_img, mode="TC", vis=False, src_img_identifier=None,
                      numpy_out=False, do_sigmoid=False, borrow=False, defer_weights=False, weight_region=False,
-                     src_is_previous_dst=False, visibility=False, flow_init=None, iters=None, flow_region=False):
+                     src_is_previous_dst=False, visibility=False, flow_init=None, iters=None, flow_region=False,
+                     keep_flow=False, skip_weights=False):
         """src_img / dst_img: (H, W, 3) uint8 BGR (numpy, or CUDA tensors already on the device).
         mode 'TC' -> (src_coords (2,HW) int64, dst_coords (2,HW) f32, weights (1,HW) f32 | None)
         mode 'flow' -> (flow (2,H,W), weights (1,H,W) | None).
@@ -424,11 +452,17 @@ class RAFTWrapper:
         flow_region (extension, default off): the caller reads flow, correspondences and weights only inside the region declared
         with pin_flow_region() (flows from the pinned source, no flow_init, no visibility mask, no weights_postprocessing_fn; config
         key `flow_region` = False / env WOFT_FLOW_REGION=0 switch it off): identical values there, unspecified but finite ones
-        elsewhere.  Without it every call computes the whole map, as the reference does."""
+        elsewhere.  Without it every call computes the whole map, as the reference does.
+        keep_flow (extension, default off): mode 'TC' writes the (2, H, W) flow map as well (the same upsampling launch; the
+        correspondences are unchanged) and flow_map() hands it out, for a caller that needs both forms of one flow.
+        skip_weights (extension, default off; ignored on a flow-cache hit): the caller reads the flow only -- weights come back as
+        None and the weight head is not evaluated (the flow does not depend on it: bit-identical).  A 'weighted_masked' network
+        evaluates both heads regardless (its mask output stays valid)."""
         if visibility and not self.masked:
             raise ValueError("compute_flow(visibility=True) needs raft_type 'weighted_masked': no other type has a mask output")
         assert mode in ["flow", "TC"]
         assert src_img.shape == dst_img.shape
+        self._flow_map = None
         if src_img_identifier is not None and self.masked:
             # (deviation: the flow cache holds no mask -- utils/caching.py:53-59 -- and the reference raises UnboundLocalError on a
             #  cache hit with 'weighted_masked' (raft.py:171,202); here the cache is skipped and the flow computed, with its mask)
@@ -505,7 +539,7 @@ class RAFTWrapper:
         plan.load_image(1, d, top, left)
         self._last_dst[id(plan)] = (id(dst_img), key)         # (what this buffer set's target features will belong to after this call)
         o = self._outputs(oh, ow)
-        weighted = self.C.raft_type in ("weighted", "weighted_masked")
+        weighted = self.C.raft_type in ("weighted", "weighted_masked") and not skip_weights
         # (defer_weights = the number of pixels the caller will name: worth it only if their 3x3 supports cannot cover most
         # of the region anyway -- measured with 500 pixels: +0.7 % at 720p (3 900 windows), +6 % at 1080p, +11 % at 4K)
         # (weighted_masked: the mask head has 3x3 cross-pixel terms and runs on every pixel after the weight head -- not deferred)
@@ -517,8 +551,10 @@ class RAFTWrapper:
         if flow_init is not None:
             plan.set_flow_init(flow_init)                   # (outside any graph: see _run_flow)
         self._run_flow(plan, n_iters, (top, left), oh, ow, o, weighted, bool(do_sigmoid) and not post,
-                       defer_wh=self.weights_deferred, want_flow=(mode == "flow"), mask_sigmoid=bool(visibility),
-                       has_init=flow_init is not None)
+                       defer_wh=self.weights_deferred, want_flow=(mode == "flow" or bool(keep_flow)),
+                       mask_sigmoid=bool(visibility), has_init=flow_init is not None,
+                       skip_wh=bool(skip_weights) and not self.masked)
+        self._flow_map = o["flow"] if (mode == "flow" or keep_flow) else None
         self._low_plan, self.last_flow_key = plan, (slot,) + key
         if self.weights_deferred:
             return self._deliver(o, None, mode, oh, ow, numpy_out, borrow)

@@ -568,6 +568,52 @@ def forward_interpolate(flow, out=None):
     return out
 
 
+def _f32c(t, *shape):
+    return t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda and (not shape or tuple(t.shape) == shape)
+
+
+def sample_bilinear(data, x, y, out=None):
+    """bilinear_interpolate_torch (utils/interpolation.py:92-133) of a contiguous (C, H, W) fp32 device tensor at the N points
+    (x, y) -> (C, N): woft_sample_bilinear -- the reference's fp32 result bit for bit, its zeros on and beyond the last row /
+    column included."""
+    assert data.dim() == 3 and _f32c(data) and x.dim() == 1 and _f32c(x) and _f32c(y, *x.shape)
+    c, h, w = data.shape
+    n = x.shape[0]
+    if out is None:
+        out = torch.empty((c, n), dtype=torch.float32, device=data.device)
+    assert _f32c(out, c, n)
+    check(_lib.load().woft_sample_bilinear(ptr(data), c, h, w, ptr(x), ptr(y), n, ptr(out), stream_ptr()), "woft_sample_bilinear")
+    return out
+
+
+def flow_chain(flow_ab, flow_bc, out=None):
+    """flow_ab + flow_bc sampled at pixel + flow_ab (edge-exact bilinear; NaN where that point leaves the frame) of two contiguous
+    (2, H, W) fp32 device tensors -> `out` (a new tensor by default; not flow_bc): woft_flow_chain."""
+    assert flow_ab.dim() == 3 and flow_ab.shape[0] == 2 and _f32c(flow_ab) and _f32c(flow_bc, *flow_ab.shape)
+    if out is None:
+        out = torch.empty_like(flow_ab)
+    assert _f32c(out, *flow_ab.shape) and out.data_ptr() != flow_bc.data_ptr()
+    check(_lib.load().woft_flow_chain(ptr(flow_ab), ptr(flow_bc), flow_ab.shape[1], flow_ab.shape[2], ptr(out), stream_ptr()),
+          "woft_flow_chain")
+    return out
+
+
+def flow_fb(flow_ab, flow_ba, alpha=0.01, beta=0.5, err=None, ok=None, want_err=True, want_ok=True):
+    """Forward-backward check of two contiguous (2, H, W) fp32 device tensors -> (err (H, W) | None, ok (H, W) 0/1 floats | None):
+    woft_flow_fb.  err = |flow_ab + flow_ba(pixel + flow_ab)|, ok = err^2 <= alpha * (|flow_ab|^2 + |flow_ba(..)|^2) + beta;
+    a pixel whose flow leaves the frame: err = +inf, ok = 0."""
+    assert flow_ab.dim() == 3 and flow_ab.shape[0] == 2 and _f32c(flow_ab) and _f32c(flow_ba, *flow_ab.shape)
+    h, w = flow_ab.shape[1:]
+    if err is None and want_err:
+        err = torch.empty((h, w), dtype=torch.float32, device=flow_ab.device)
+    if ok is None and want_ok:
+        ok = torch.empty((h, w), dtype=torch.float32, device=flow_ab.device)
+    assert (err is None or (_f32c(err) and err.numel() == h * w)) and (ok is None or (_f32c(ok) and ok.numel() == h * w))
+    check(_lib.load().woft_flow_fb(ptr(flow_ab), ptr(flow_ba), h, w, float(alpha), float(beta), ptr(err), ptr(ok), stream_ptr()),
+          "woft_flow_fb")
+    return err, ok
+
+
 def coords_update(coords, delta, ld_delta, wf, flow4=None, flow_cat=None, ld_cat=0):
     check(_lib.load().woft_coords_update(ptr(coords), ptr(delta), ld_delta, wf, coords.shape[0], ptr(flow4),
                                          ptr(flow_cat), ld_cat, stream_ptr()), "woft_coords_update")

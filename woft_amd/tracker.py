@@ -22,6 +22,10 @@ Visibility (this project's own, no counterpart in TRK; DESIGN.md "Visibility mas
 prunes ('gate': p > `visibility_thr`) or scales ('weight': w * p) the correspondences inside the same select kernels, in both stages
 and both back ends.
 
+Forward-backward check (this project's own, no counterpart in TRK): with the config key `fb_check` = 'gate'
+both stages also run the REVERSE flow, compare the two (woft_flow_fb, keys `fb_alpha` / `fb_beta`) and hand the 0/1 verdict to the
+solver in the visibility slot as a gate -- a reliability signal for networks that have none (raft_type 'orig').
+
 Warm start (this project's own, no counterpart in TRK; DESIGN.md "Warm start"): with the config key `warm_start_local` the
 frame t-1 -> t flow of the second and later frames of a run of lost frames starts from the forward-interpolated 1/8-resolution
 flow of the previous one (RAFT's video warm start, raft_core/utils/utils.py:28-56) instead of from zero; `warm_start_iters`
@@ -159,6 +163,35 @@ class YAOFTrackerSingleControl:
             raise ValueError(f"visibility_thr {thr!r}: not a float in (0, 1)")
         return mode, float(np.float32(thr))                  # rounded to fp32 once, here
 
+    FB_MODES = ("gate",)
+
+    def _fb_config(self):
+        """-> (mode | None, alpha, beta).  Config keys `fb_check` (absent / falsy: off; 'gate' is the only mode) and `fb_alpha` /
+        `fb_beta` (finite floats >= 0, defaults 0.01 and 0.5): a correspondence survives iff its flow lands inside the frame and
+        |f + b|^2 <= fb_alpha * (|f|^2 + |b|^2) + fb_beta, b the reverse flow sampled where f lands."""
+        C = self.C
+        mode = C.fb_check
+        if isinstance(mode, type(C)) or not mode:           # (key absent: an empty, falsy Config)
+            return None, 0.01, 0.5
+        if mode not in self.FB_MODES:
+            raise ValueError(f"fb_check {mode!r}: not one of {self.FB_MODES} (or absent / None: no forward-backward check)")
+        vm = C.visibility_mode
+        if not isinstance(vm, type(C)) and vm:
+            raise ValueError(f"fb_check {mode!r} and visibility_mode {vm!r} are both set: the solver has one visibility slot, "
+                             "choose one of the two")
+        vals = []
+        for key, default in (("fb_alpha", 0.01), ("fb_beta", 0.5)):
+            v = getattr(C, key)
+            v = default if (isinstance(v, type(C)) or v is None) else v
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{key} {v!r}: not a finite float >= 0") from None
+            if not 0.0 <= v < float("inf"):                  # (NaN fails both compares)
+                raise ValueError(f"{key} {v!r}: not a finite float >= 0")
+            vals.append(v)
+        return mode, vals[0], vals[1]
+
     def _warm_start_config(self):
         """-> (on, iterations of a warm-started flow | None = the flow config's).  Config keys `warm_start_local` (absent / falsy:
         off) and `warm_start_iters` (an integer >= 1; absent / None: the flow config's `iters`)."""
@@ -177,7 +210,11 @@ class YAOFTrackerSingleControl:
         self.warm_start_local, self.warm_start_iters = self._warm_start_config()
         self.local_warm_started = False   # whether the last frame t-1 -> t flow started from a carried flow
         self._warm = None                 # (flow_low of the last frame t-1 -> t flow, its provider flow key): the carried flow
+        self.fb_check, self.fb_alpha, self.fb_beta = self._fb_config()
         self.visibility_mode, self.visibility_thr = self._visibility_config()
+        # what the solver's visibility slot carries: the MaskHead's probability under a visibility mode, the forward-backward
+        # verdict (0 / 1, gated at 0.5) under fb_check -- never both (_fb_config)
+        self._vis_mode, self._vis_thr = (("gate", 0.5) if self.fb_check else (self.visibility_mode, self.visibility_thr))
         if config.flow_config.raft_type == "weighted_masked" and self.visibility_mode is None:
             # the tracker unpacks (src, dst, weights) from compute_flow (TRK:101,181); a 'weighted_masked' provider returns a fourth
             # value, the visibility mask, which the tracker consumes only under a `visibility_mode`: refused here rather than at the first frame
@@ -187,6 +224,9 @@ class YAOFTrackerSingleControl:
         if self.C.subsampler_fn:
             self.C.subsampler_fn = make_forward_compatible(self.C.subsampler_fn)
         self.flower = config.flow_config.of_class(config.flow_config)
+        if self.fb_check and not (hasattr(self.flower, "flow_map") and hasattr(self.flower, "pin_source")):
+            raise NotImplementedError("fb_check needs this project's flow provider (compute_flow(..., keep_flow=True) and "
+                                      f"flow_map()); {type(self.flower).__name__} has neither")
         self.device = self.DEVICE
         self._fused = self._fused_specs()
         self._sparse_weights = False
@@ -209,6 +249,9 @@ class YAOFTrackerSingleControl:
         if self.visibility_mode is not None:
             self.solver_decision += (f"; visibility {self.visibility_mode}"
                                      + (f" (p > {self.visibility_thr:.9g})" if self.visibility_mode == "gate" else " (w * p)"))
+        if self.fb_check:
+            self.solver_decision += (f"; forward-backward check {self.fb_check} (|f + b|^2 <= {self.fb_alpha:.9g} * (|f|^2 + |b|^2) "
+                                     f"+ {self.fb_beta:.9g})")
         return spec
 
     def _fused_specs_plain(self):
@@ -303,7 +346,8 @@ class YAOFTrackerSingleControl:
             # (a visibility mode: the mask head runs on every pixel after the weight head and the provider defers nothing for a
             #  'weighted_masked' network -- the non-deferred path)
             self._sparse_weights = bool(on and self._fused is not None and self._fused["n_draw"] and self._mask_weight_head()
-                                        and hasattr(self.flower, "finish_weights") and self.visibility_mode is None)
+                                        and hasattr(self.flower, "finish_weights") and self.visibility_mode is None
+                                        and not self.fb_check)
         self._set_pose(_EYE.copy(), good=True)
         self.prev_img, self.prev_img_identifier = img, img_identifier
         self.lost, self.N_lost = False, 0
@@ -351,7 +395,7 @@ class YAOFTrackerSingleControl:
 
         prewarp_H = self.last_good_H2init
         fit = self._global_stage(frame, prewarp_H)
-        if self.visibility_mode is not None:
+        if self._vis_mode is not None:
             meta.n_kept = self.n_kept                                # kept by the masks and the gate, template -> frame flow
         H_global = compose_H(prewarp_H, fit.H)
         meta.H_global_cur2init = H_global.copy()
@@ -366,7 +410,7 @@ class YAOFTrackerSingleControl:
             if not self.C.no_local_H:
                 H_cur2init = meta.H_local_cur2init = self._local_stage(frame)
                 meta.local_warm_started = self.local_warm_started    # (False without `warm_start_local`)
-                if self.visibility_mode is not None:
+                if self._vis_mode is not None:
                     meta.n_kept_local = self.n_kept                  # ... frame t-1 -> t flow (None: no flow ran)
         if debug:
             logger.debug("debug visualisation (TRK:210-264) needs the OpenCV GUI and is not part of the HIP path")
@@ -381,6 +425,8 @@ class YAOFTrackerSingleControl:
             meta.solver_decision = self.solver_decision
             if self.visibility_mode is not None:      # (like n_kept: the field exists only with a mode)
                 meta.visibility_mode = self.visibility_mode
+            if self.fb_check:
+                meta.fb_check = self.fb_check
         k = self.C.downscale_inputs
         if k:                                                        # TRK:280-283
             H_cur2init = compose_H(np.diag([1.0 / k, 1.0 / k, 1.0]), H_cur2init, np.diag([float(k), float(k), 1.0]))
@@ -395,7 +441,7 @@ class YAOFTrackerSingleControl:
         return bool(v)
 
     def _flow_region_on(self):
-        return bool(self._mask_weight_head() and self.visibility_mode is None and not self.warm_start_local)
+        return bool(self._mask_weight_head() and self.visibility_mode is None and not self.warm_start_local and not self.fb_check)
 
     def _set_pose(self, H, good):
         self.prev_H2init = H
@@ -428,11 +474,28 @@ class YAOFTrackerSingleControl:
             # mask's upsampling call) -- compute_flow called by anybody else returns the logits, as the reference's does
             src_xy, dst_xy, w, p = self.flower.compute_flow(src, dst, mode="TC", vis=False, src_img_identifier=None,
                                                             do_sigmoid=True, visibility=True, **kw)
+        elif self.fb_check:
+            src_xy, dst_xy, w, p = self._flow_fb(src, dst, kw)
         else:
             src_xy, dst_xy, w = self.flower.compute_flow(src, dst, mode="TC", vis=False, src_img_identifier=None,
                                                          do_sigmoid=True, **kw)
         s = getattr(self.flower, "last_flow_shape", None)
         return src_xy, dst_xy, w, p, ((s["H"], s["W"]) if s else None)
+
+    def _flow_fb(self, src, dst, kw):
+        """The flow src -> dst as _flow asks for it, the reverse flow dst -> src, and their forward-backward verdict on the flow
+        grid: -> (src_xy, dst_xy, w, ok (1, n) 0/1 floats).  The forward call is the one a tracker without fb_check makes (same
+        correspondences and weights, bit for bit) plus the flow map of the same upsampling launch; its results are copied before
+        the reverse flow overwrites the provider's per-size output buffers.  The reverse flow reads no weights."""
+        f = self.flower
+        src_xy, dst_xy, w = f.compute_flow(src, dst, mode="TC", vis=False, src_img_identifier=None, do_sigmoid=True,
+                                           keep_flow=True, **kw)
+        fwd, dst_xy, w = f.flow_map().clone(), dst_xy.clone(), (None if w is None else w.clone())
+        # (the warm start carries the FORWARD flow: read before the reverse flow replaces the provider's last-flow state)
+        self._fb_low = (f.flow_low(), f.last_flow_key) if self.warm_start_local else None
+        bwd = f.compute_flow(dst, src, mode="flow", vis=False, src_img_identifier=None, borrow=True, skip_weights=True)[0]
+        _, ok = ops.flow_fb(fwd, bwd, self.fb_alpha, self.fb_beta, want_err=False)
+        return src_xy, dst_xy, w, ok.reshape(1, -1)
 
     def _global_stage(self, frame, prewarp_H):
         """Template -> frame pre-warped by the last good homography (TRK:85-162).  Kept: correspondences that start
@@ -478,7 +541,7 @@ class YAOFTrackerSingleControl:
                                                 iters=self.warm_start_iters)
         self._local_chain = (frame, self._n_tracked)
         if self.warm_start_local:
-            self._warm = (self.flower.flow_low(), self.flower.last_flow_key)
+            self._warm = self._fb_low if self.fb_check else (self.flower.flow_low(), self.flower.last_flow_key)
         if np.array_equal(self.prev_H2init, _EYE):
             prev_mask = self._template_mask_u8
         else:
@@ -509,9 +572,10 @@ class YAOFTrackerSingleControl:
             # behaviour: the global stage lets it out of track(), the local stage keeps the previous pose.  A gate is MEANT to empty
             # the set under occlusion: the global stage then reports a failed re-detection (H = identity: the pre-warp's pose) and
             # the frame is lost, as any other frame whose global fit is rejected.
-            if self.visibility_mode is None or not judge or self.n_kept is None or self.n_kept >= 4:
+            if self._vis_mode is None or not judge or self.n_kept is None or self.n_kept >= 4:
                 raise
-            logger.debug(f"global stage: {self.n_kept} correspondences after the visibility {self.visibility_mode}: no fit")
+            logger.debug(f"global stage: {self.n_kept} correspondences after the "
+                         + (f"forward-backward {self.fb_check}" if self.fb_check else f"visibility {self.visibility_mode}") + ": no fit")
             return _Fit(H=_EYE.copy(), success=False)
 
     def _solve_device(self, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, vis=None):
@@ -522,9 +586,9 @@ class YAOFTrackerSingleControl:
         if vis is not None:
             # (an unweighted estimator under 'weight': the output weight is p itself and the fit is called weighted)
             ops.tc_select_vis(dst_xy, w if weighted else None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds,
-                              F["sobol_u"], vis, self.visibility_mode, self.visibility_thr, b["ws"], b["pa"], b["pb"], b["w"],
+                              F["sobol_u"], vis, self._vis_mode, self._vis_thr, b["ws"], b["pa"], b["pb"], b["w"],
                               ires[12:14], grid=grid)
-            weighted = weighted or self.visibility_mode == "weight"
+            weighted = weighted or self._vis_mode == "weight"
         elif w is None and getattr(self.flower, "weights_deferred", False):
             # The correspondences the fit will read are decided by the flow alone (masks, bounds, Sobol draw): select them
             # first, then let the provider evaluate the weight head on the windows under THEIR upsampling support only and
@@ -578,14 +642,14 @@ class YAOFTrackerSingleControl:
                                 grid=grid)
         else:
             keep = ops.tc_flags_vis(dst_xy if bounds else None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds,
-                                    vis, self.visibility_mode, self.visibility_thr, grid=grid)
+                                    vis, self._vis_mode, self._vis_thr, grid=grid)
         pick = lambda t: None if t is None else t[:, keep]
         src_xy, dst_xy, w, post = pick(src_xy), pick(dst_xy), pick(w), pick(post)
         if vis is not None:
             self.n_kept = int(src_xy.shape[1])
             if self.n_kept == 0:                                     # (nothing to hand to the config's callables)
                 raise AssertionError(torch.Size([1, 0, 2]))
-            if self.visibility_mode == "weight":                     # w * p in fp32 on the compacted set; p alone without weights
+            if self._vis_mode == "weight":                           # w * p in fp32 on the compacted set; p alone without weights
                 pk = vis.reshape(1, -1)[:, keep]
                 w = pk if w is None else w * pk
         if judge:
@@ -620,6 +684,11 @@ class WOFTWindow(YAOFTrackerSingleControl):
     MIN_FLOW_SIDE = 16                # a local window cut smaller than this by the frame edge: no flow, previous pose kept
 
     def __init__(self, config):
+        v = config.fb_check
+        if not isinstance(v, type(config)) and v:
+            # (not built: the window stages have their own _flow call sites and per-window plans)
+            raise NotImplementedError("fb_check is not provided by the search-window tracker: only YAOFTrackerSingleControl runs "
+                                      "the reverse flow")
         v = config.warm_start_local
         if not isinstance(v, type(config)) and v:
             # (the local windows move with the object: the flow of one window is not on the grid of the next)

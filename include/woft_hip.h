@@ -429,6 +429,43 @@ int woft_convex_upsample(const float* coords1, const float* wlow, const float* m
 int woft_convex_weights_at(const float* pts, const int32_t* count, int32_t n_max, const float* wlow, const float* mask,
                            int32_t ld_mask, int32_t hf, int32_t wf, int32_t crop_top, int32_t crop_left,
                            int32_t do_sigmoid, float* wsel, void* stream);
+/* ---- Training of the weight head (weighted_raft.py:318-384) ------------------------------------------
+ * The standard head -- three 3x3 convs to 128 channels, a ReLU after each, a closing 1x1 conv, the mean over the 9x9 window --
+ * on a compacted list of n_win <= WOFT_WH_TRAIN_MAX_WIN windows, forward layers that keep their activations and the backward
+ * of every stage.  Exact fp32 (v_mfma_f32_32x32x2_f32 products = a k-ordered fmaf chain); every sum is deterministic: no
+ * floating-point atomics, split sums are written as partials per WOFT_WH_TRAIN_CHUNK windows and added in chunk order.
+ * Activations: [window][81 positions][128 channels] fp32; the first layer's input: [window][81][8], woft_wh_pack's x8 rows.
+ *
+ * woft_convex_weights_at_bwd: adjoint of woft_convex_weights_at with respect to wlow.  g_wsel [n_max]: the gradient of wsel
+ *   (rows at and beyond min(count[0], n_max) are never read, nor are those rows of pts).  g_wlow [hf * wf] is written as zeros
+ *   first; then the cell of every listed window (index [n_win]: 1/8-resolution cell ids, each at most once; NULL = every cell,
+ *   n_win = hf * wf) receives the sum, in point order, of what the points whose 3x3 support holds it send back: the softmaxed
+ *   mask coefficient, the 8 * ... / 8 pair and, with do_sigmoid, the sigmoid's derivative (wlow is then read; else it may be
+ *   NULL).  Neighbours outside the map receive nothing (zero padding).  A gather: points that share a cell need no atomics.
+ * woft_wh_reduce_bwd: adjoint of woft_wh_reduce (nwin2 = 81, c = 128) on the listed windows:
+ *   g = g_wlow[index[p]] / 81 (index NULL: g_wlow[p]);  g_act[p][t][c] = g * w6[c] * (act[p][t][c] > 0);
+ *   g_w6[c] = sum_{p,t} g * act[p][t][c];  g_b6[0] = sum_p g_wlow[index[p]].  ws: (n_chunks) * 129 doubles.
+ * woft_wh_train_conv: one 3x3 layer cin -> 128 (cin = 128, or 8 for the first layer's x8 rows) on 9x9 windows, each window
+ *   zero-padded on its own:  y[p][t][co] = sum_{tap,ci} x[p][t + tap][ci] * wt[tap][ci][co]  (wt: [9][cin][128], tap = ky*3+kx),
+ *   then with bias: relu(y + bias[co]) -- a forward layer --, or with gate ([n_win][81][128]): y where gate > 0, else 0 -- the
+ *   data gradient of a layer when wt holds its transposed, flipped filter and gate the activation below it.  Not both.
+ * woft_wh_wgrad: parameter gradient of such a layer:  gw[co][ci][ky][kx] = sum_{p,t} gy[p][t][co] * x[p][t + tap][ci] for
+ *   ci < cin_out (gw: [128][cin_out][3][3], the state dict's layout; cin_out = 5 with cin = 8), gb[co] = sum_{p,t} gy[p][t][co].
+ *   ws: woft_wh_wgrad_ws_bytes(n_win, cin) bytes of partial sums.
+ * All return WOFT_EINVAL before any launch on a NULL required pointer or a size outside the stated range. */
+#define WOFT_WH_TRAIN_CHUNK 16
+#define WOFT_WH_TRAIN_MAX_WIN (9 * 2048)
+int woft_convex_weights_at_bwd(const float* pts, const int32_t* count, int32_t n_max, const float* g_wsel, const float* wlow,
+                               const float* mask, int32_t ld_mask, int32_t hf, int32_t wf, int32_t crop_top,
+                               int32_t crop_left, int32_t do_sigmoid, const int32_t* index, int32_t n_win, float* g_wlow,
+                               void* stream);
+int woft_wh_reduce_bwd(const float* act, const float* w6, const float* g_wlow, const int32_t* index, int32_t n_win,
+                       float* g_act, double* ws, float* g_w6, float* g_b6, void* stream);
+int woft_wh_train_conv(const float* x, int32_t cin, const float* wt, const float* bias, const float* gate, int32_t n_win,
+                       float* y, void* stream);
+int64_t woft_wh_wgrad_ws_bytes(int32_t n_win, int32_t cin);
+int woft_wh_wgrad(const float* gy, const float* x, int32_t cin, int32_t cin_out, int32_t n_win, float* ws, float* gw,
+                  float* gb, void* stream);
 /* Pre-computed flow read from the reference's cache files (utils/caching.py:53-59; raft.py:93-106) to the same
  * outputs: dst[2][h*w] = pixel grid + flow[2][h*w] (may be NULL), wout[h*w] = weights or sigmoid(weights)
  * (weights / wout may be NULL). */

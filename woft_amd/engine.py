@@ -27,7 +27,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib, conv_select, flow_region, ops
+from . import _lib, conv_select, flow_region, ops, wh_train
 from .conv_select import KERNELS, Kernel
 from .ops import Act, new_act
 
@@ -245,12 +245,7 @@ class RaftEngine:
         self.wh_std = shapes == [(128, 5, 3, 3), (128, 128, 3, 3), (128, 128, 3, 3), (1, 128, 1, 1)]
         last = idx[-1]
         if self.wh_std:
-            self.wh0 = ops.pack_conv(sd[w + "0.weight"], sd[w + "0.bias"], flat_cs=8)
-            self.wh2 = ops.pack_conv(sd[w + "2.weight"], sd[w + "2.bias"])
-            self.wh4 = ops.pack_conv(sd[w + "4.weight"], sd[w + "4.bias"])
-            # first conv as MFMA fragments for the fused two-layer launch (split-bf16 precisions, 9x9 windows)
-            self.wh0_frag = (ops.pack_wh0_frags(sd[w + "0.weight"], 2 if self.prec_wh == "bf16x3" else 1)
-                             if precision != "fp32" and sp.nwin == 9 else None)
+            self.wh0, self.wh2, self.wh4, self.wh0_frag = self._wh_std_packed(sd)
         else:
             # generic head: the first layer reads the 5-channel patches -- "flat" packing (8 floats per window position)
             # while kernel * 8 <= 32, else 32-channel rows; the other layers are ordinary convs on (windows, n, n, C)
@@ -263,6 +258,38 @@ class RaftEngine:
         self.wh6_w[:self.wh6_c] = sd[f"{w}{last}.weight"].reshape(-1)
         self.wh6_w = self.wh6_w.contiguous().cuda()
         self.wh6_b = float(sd[f"{w}{last}.bias"].item())
+
+    def _wh_std_packed(self, sd):
+        """The three 3x3 layers of the standard head packed for the conv kernels -> (wh0, wh2, wh4, wh0_frag)."""
+        w = "weight_head.net."
+        wh0 = ops.pack_conv(sd[w + "0.weight"], sd[w + "0.bias"], flat_cs=8)
+        wh2 = ops.pack_conv(sd[w + "2.weight"], sd[w + "2.bias"])
+        wh4 = ops.pack_conv(sd[w + "4.weight"], sd[w + "4.bias"])
+        # first conv as MFMA fragments for the fused two-layer launch (split-bf16 precisions, 9x9 windows)
+        wh0_frag = (ops.pack_wh0_frags(sd[w + "0.weight"], 2 if self.prec_wh == "bf16x3" else 1)
+                    if self.precision != "fp32" and self.spec.nwin == 9 else None)
+        return wh0, wh2, wh4, wh0_frag
+
+    def repack_weight_head(self, sd):
+        """Re-pack the standard head from `sd` (its eight weight_head.net.* tensors) IN PLACE into every device buffer the
+        inference path reads head parameters from -- the engine's packed layers and fragments, the closing conv's weights and
+        bias, and in every plan wh0_t, the bias tensor and the padded closing weights -- and drop every captured graph (a captured
+        launch bakes the closing bias in as an argument).  The next flow then has the bits of an engine built from `sd`."""
+        assert self.weighted and self.wh_std
+        sd = {k: v.detach().float().cpu() for k, v in sd.items() if k.startswith("weight_head.net.")}
+        wh0, wh2, wh4, frag = self._wh_std_packed(sd)
+        for old, new in ((self.wh0, wh0), (self.wh2, wh2), (self.wh4, wh4)):
+            ops.repack_conv_(old, new)
+        if self.wh0_frag is not None:
+            self.wh0_frag.copy_(frag)
+        self.wh6_w[:self.wh6_c].copy_(sd["weight_head.net.6.weight"].reshape(-1))
+        self.wh6_b = float(sd["weight_head.net.6.bias"].item())
+        for plan in self._plans.values():
+            plan.wh0_t.copy_(self.wh0.wgt[:128].t())
+            plan.wh6_b.fill_(self.wh6_b)
+            if plan._wh6_pad is not None:
+                plan._wh6_pad[:self.wh6_c].copy_(self.wh6_w[:self.wh6_c])
+            plan._graphs.clear()
 
     def _pack_mask_head(self, sd):
         sp = self.spec
@@ -319,6 +346,7 @@ class _Plan:
         self.flow_region, self._flow_regions = None, {}        # None = every launch on the whole map (set_flow_region)
         self.wh_region, self._wh_regions = None, {}            # None = every source pixel (set_weight_region)
         self._wh_dyn = {}                                      # per region: (dynamic window list, its programs, scratch)
+        self._wh_train = None                                  # buffers of wh_train_forward / wh_train_backward (first use)
         self._plan_features()
         self._plan_update_block()
         if eng.weighted:
@@ -1026,3 +1054,79 @@ class _Plan:
         if not self.wh_fused:
             last = self.a1 if e.wh_std else self.wh_last
             ops.wh_reduce(last, n * n, self._wh6_padded(last.cs), e.wh6_b, self.P, self.wlow)
+
+    # ---- training of the weight head (woft_amd/wh_train.py) ------------------------------------------
+    def _wh_train_buffers(self, n_max):
+        """Buffers of the training path, sized by 9 * n_max windows (the 3x3 upsampling support of n_max points), allocated at
+        the first use and again when a larger n_max arrives.  None of them is read by flow() / finish_weights()."""
+        cap = 9 * n_max
+        t = self._wh_train
+        if t is None or t["cap"] < cap:
+            z, P = self._z, self.P
+            i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device="cuda")
+            t = dict(cap=cap, x8=z(cap, 81, 8), act=[z(cap, 81, 128) for _ in range(3)], g=[z(cap, 81, 128) for _ in range(2)],
+                     out=z(cap), wlow=z(P), g_wlow=z(P), bitmap=i32(P), dyn=i32(P),
+                     all=torch.arange(P, dtype=torch.int32, device="cuda"),
+                     ws=z(ops.wh_wgrad_ws_floats(cap, 128)), ws64=z(-(-cap // ops.WH_TRAIN_CHUNK) * 129, dtype=torch.float64),
+                     gen=0 if t is None else t["gen"])
+            self._wh_train = t
+        return t
+
+    def wh_train_forward(self, params, pts, count, n_max, pad, crop, do_sigmoid=False):
+        """The weight of the last flow() at the (count) pixels pts (n_max, 2) = (x, y), by an un-fused exact-fp32 forward of the
+        standard head that keeps its three activations: the windows the points need (woft_wh_needed) compacted into a list,
+        the final lookup on their 8x8 blocks, mean response, the packed patches, three woft_wh_train_conv layers, the closing
+        conv + window mean, woft_convex_weights_at.  params: the eight tensors of the head in state-dict order (net.0.weight,
+        net.0.bias, ... net.6.bias), fp32 on the device, read as they are now.
+        -> (wsel (n_max,) with exact zeros at and beyond count, state for wh_train_backward)."""
+        sp, n = self.eng.spec, self.eng.spec.nwin
+        assert self.eng.weighted and self.eng.wh_std and not sp.small and n == 9 and 0 < n_max <= ops.HFIT_SINGLE_MAX
+        t = self._wh_train_buffers(n_max)
+        t["gen"] += 1
+        w0, b0, w2, b2, w4, b4, w6, b6 = (p.detach() for p in params)
+        wsel = torch.zeros(n_max, dtype=torch.float32, device="cuda")
+        ops.wh_needed(pts, count, n_max, pad[0], pad[1], self.hf, self.wf, t["all"], t["bitmap"], t["dyn"])
+        index = t["dyn"][t["dyn"] >= 0].contiguous()     # (reads its length back: training has no per-frame latency budget)
+        n_win = int(index.numel())
+        if n_win == 0:
+            return wsel, None
+        if self.otf:                                     # final lookup, weighted_raft.py:266, on the blocks that hold a wanted window
+            self.lookup.need = _lib.ptr(t["bitmap"])
+        self._lookup(self.lookup)
+        if self.otf:
+            self.lookup.need = None
+        ops.colsum(self.f2act[0].t, self.P, sp.fdim, self.cs_ws, self.cs_tot)
+        ops.wh_pack(self.corr, self.f1, self.cs_tot, 1.0 / (math.sqrt(float(sp.fdim)) * self.P), n, self.wmean, None)
+        li = index.long()
+        x8 = t["x8"][:n_win]                             # woft_wh_pack's rows of the listed windows (channels 5..7 stay zero)
+        x8[:, :, :4] = self.corr.t[li, :4 * n * n].view(n_win, n * n, 4)
+        x8[:, :, 4] = self.wmean[li][:, None]
+        wh_train.head_forward(x8, n_win, (w0, b0, w2, b2, w4, b4, w6), t["act"], t["out"])
+        t["wlow"].zero_()
+        t["wlow"][li] = t["out"][:n_win] + b6.reshape(())
+        ops.convex_weights_at(pts, count, n_max, t["wlow"], self.mask.t, self.hf, self.wf, crop, wsel, do_sigmoid=do_sigmoid)
+        return wsel, dict(gen=t["gen"], index=index, n_win=n_win, pts=pts, count=count, n_max=n_max, crop=crop,
+                          do_sigmoid=bool(do_sigmoid), w2=w2.clone(), w4=w4.clone(), w6=w6.reshape(-1).clone())
+
+    def wh_train_backward(self, state, g_wsel):
+        """Gradients of the eight head parameters for the gradient g_wsel (n_max,) of wh_train_forward's result: upsampling
+        adjoint -> closing conv + mean -> per layer the weight gradient (woft_wh_wgrad) and, above the first layer, the data
+        gradient (woft_wh_train_conv with the transposed, flipped filter and the ReLU gate).  Reads the activations the forward
+        left in the plan's training buffers and the plan's upsampling mask: it must run before the next wh_train_forward or
+        flow() of this plan.  Deterministic: two calls return equal bytes."""
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device="cuda")
+        gw0, gb0, gw2, gb2, gw4, gb4, gw6, gb6 = z(128, 5, 3, 3), z(128), z(128, 128, 3, 3), z(128), z(128, 128, 3, 3), z(128), \
+            z(1, 128, 1, 1), z(1)
+        grads = (gw0, gb0, gw2, gb2, gw4, gb4, gw6, gb6)
+        if state is None:
+            return grads
+        t = self._wh_train
+        if t is None or t["gen"] != state["gen"]:
+            raise RuntimeError("weights_at(): backward after a later flow or weights_at() in the same flow plan -- the activations "
+                               "and the upsampling mask it reads are gone")
+        n_win, index = state["n_win"], state["index"]
+        ops.convex_weights_at_bwd(state["pts"], state["count"], state["n_max"], g_wsel, t["wlow"], self.mask.t, self.hf, self.wf,
+                                  state["crop"], t["g_wlow"], index=index, do_sigmoid=state["do_sigmoid"])
+        wh_train.head_backward(t["x8"], n_win, (state["w2"], state["w4"], state["w6"]), t["act"], t["g_wlow"], index, t["g"],
+                               t["ws"], t["ws64"], grads)
+        return grads

@@ -12,7 +12,7 @@ from timeit import default_timer as timer
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, wh_train
 from .engine import RaftEngine
 
 logger = logging.getLogger(__name__)
@@ -153,6 +153,10 @@ class RAFTWrapper:
         # flow config key `volume_storage` ("fp32" | "bf16"): element type of the correlation volume (corr = "volume")
         self.engine = RaftEngine(state_dict, small=small, weighted=weighted, precision=self.precision, corr=self.corr,
                                  volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked)
+        # training of the weight head (weight_head_parameters / weights_at / sync_weight_head): the head's tensors as loaded, the
+        # Parameters made of them at the first request, and the plan + crop of the last COMPUTED flow (None: none, or a cache hit)
+        self._wh_loaded = {k: v for k, v in state_dict.items() if k.startswith("weight_head.net.")}
+        self._wh_params, self._wh_flow = None, None
         # restricted refinement iterations for callers that declare where they read the flow (pin_flow_region + flow_region=True)
         v = getattr(self.C, "flow_region", None)
         self.flow_region_on = (os.environ.get("WOFT_FLOW_REGION", "1") != "0") if (v is None or isinstance(v, type(self.C))) else bool(v)
@@ -201,6 +205,10 @@ class RAFTWrapper:
         arguments; the per-launch event hooks of bench.py force the eager path).
         has_init: start from the plan's flow_init buffer (filled by the caller BEFORE this call: a replayed graph reads the
         buffer's fixed address, the copy into it is not part of the graph)."""
+        self._wh_flow = (plan, crop)                       # (what weights_at() evaluates the head on)
+        if plan._wh_train is not None:                     # (a weights_at() graph of an earlier flow in this plan is stale now: its
+            plan._wh_train["gen"] += 1                     #  backward would read this flow's upsampling mask -- it raises instead)
+
         def eager():
             # (mode "TC" hands out dst = grid + flow only: the (2, H, W) flow map is then not written at all)
             plan.flow(iters, crop, oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"], wout=o["w"] if weighted else None,
@@ -236,6 +244,57 @@ class RAFTWrapper:
         plan.finish_weights(pts, count, n_max, crop, crop, oh, ow, flow_up=o["flow"], dst=o["dst"], wout=o["w"],
                             do_sigmoid=do_sigmoid, w_points=out)
         return o["w"] if out is None else out
+
+    # ---- training of the weight head (woft_amd/wh_train.py) ----
+    def _wh_trainable(self):
+        """NotImplementedError, naming the reason, unless this provider is the one case the training path covers."""
+        eng = self.engine
+        why = (f"raft_type '{self.C.raft_type}' (only 'weighted' is covered)" if self.C.raft_type != "weighted" else
+               "the small model (its head reads 7x7 windows of another lookup)" if eng.small else
+               "a weight_head_structure other than [(128, 3), (128, 3), (128, 3)]" if not eng.wh_std else
+               "a weights_postprocessing_fn between the head and the weights" if self.C.weights_postprocessing_fn else None)
+        if why:
+            raise NotImplementedError(f"training of the weight head is not provided for {why}")
+
+    def weight_head_parameters(self):
+        """The weight head's parameters as an OrderedDict of fp32 device torch.nn.Parameter (requires_grad=True) under the
+        reference's state-dict names weight_head.net.{0,2,4,6}.{weight,bias}, initialised from the loaded checkpoint; the same
+        objects at every call.  weights_at() reads their current values; the inference path (compute_flow) reads its own packed
+        copies, which sync_weight_head() refreshes.  torch.optim takes list(d.values()); dict(d) saves as a state dict."""
+        self._wh_trainable()
+        if self._wh_params is None:
+            self._wh_params = wh_train.make_parameters(self._wh_loaded)
+        return self._wh_params
+
+    def weights_at(self, pts, count=None, do_sigmoid=False):
+        """After a computed compute_flow(src, dst, ...) of this provider (skip_weights=True is the cheap way; not after a
+        flow-cache hit): the flow weight at the pixels pts (n_max, 2) float32 = (x, y) of the un-padded source image (n_max <=
+        2048), evaluated with the CURRENT values of weight_head_parameters() in exact fp32 -> (n_max,) float32, the logit or
+        (do_sigmoid) its sigmoid; rows at and beyond count (a device int32 scalar, optional) are exact zeros.  With grad enabled
+        and a parameter that requires grad the result carries a graph whose backward accumulates into the parameters' .grad
+        (once differentiable; deterministic); nothing else receives a gradient -- RAFT stays frozen.  backward() must run before
+        the next compute_flow / weights_at of this provider: it reads the plan's buffers."""
+        self._wh_trainable()
+        if self._wh_flow is None:
+            raise RuntimeError("weights_at(): no computed flow to evaluate the head on (none yet, or the last one came from the "
+                               "flow cache)")
+        if not (isinstance(pts, torch.Tensor) and pts.is_cuda and pts.dtype == torch.float32 and pts.dim() == 2
+                and pts.shape[1] == 2 and pts.shape[0] >= 1):
+            raise TypeError("weights_at(): pts must be a (n_max, 2) float32 device tensor of (x, y) pixels")
+        if pts.shape[0] > ops.HFIT_SINGLE_MAX:
+            raise ValueError(f"weights_at(): at most {ops.HFIT_SINGLE_MAX} points per call, got {pts.shape[0]}")
+        if count is not None and not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32
+                                      and count.numel() == 1):
+            raise TypeError("weights_at(): count must be a device int32 scalar")
+        plan, crop = self._wh_flow
+        params = self.weight_head_parameters().values()
+        return wh_train.weights_at(plan, params, pts.detach().contiguous(), count, int(pts.shape[0]), crop, do_sigmoid)
+
+    def sync_weight_head(self):
+        """Push the current values of weight_head_parameters() into the inference path: every packed buffer the engine and its
+        plans read head parameters from is rewritten in place and every captured graph is dropped.  Afterwards compute_flow
+        returns the bits of a fresh provider built from the original state dict with dict(weight_head_parameters()) merged in."""
+        self.engine.repack_weight_head({k: v.detach() for k, v in self.weight_head_parameters().items()})
 
     # ---- template caching (results-identical: InstanceNorm is per sample, extractor.py:171-190) ----
     def pin_source(self, src_img):
@@ -316,6 +375,7 @@ class RAFTWrapper:
         'half_flow' (2,H,W) and 'half_weights' (1,H,W) (any float dtype, cast to fp32); then the same
         post-processing as a computed flow (raft.py:152-195)."""
         dataset_name, seq_name, frame_i = identifier
+        self._wh_flow = None                               # (a cache hit leaves the network's buffers at an older flow: weights_at() refuses)
         path = Path(self.C.flow_cache_dir) / dataset_name / seq_name / f"{frame_i}-{frame_i + 1}.npz"
         data = np.load(path, allow_pickle=False)           # plain float arrays: nothing to unpickle
         flow = np.ascontiguousarray(data["half_flow"].astype(np.float32))

@@ -198,6 +198,21 @@ def pack_conv(weight, bias, stride=1, padding=None, cin_layout=None, flat_cs=0, 
                       cin_pad, kh, kw, padding[0], padding[1], stride, 0, 0, kh, kw)
 
 
+def repack_conv_(pc, new):
+    """Copy the packed layer `new` (pack_conv of other values of the same layer) into the device tensors of `pc`, IN PLACE:
+    parameter structs and captured launches that hold pc's addresses then read the new values.  Every form pc has built so far
+    (fp32 rows, the bf16 split, fragment orders, the fp16 plane) is rewritten."""
+    assert pc.wgt.shape == new.wgt.shape and pc.bias.shape == new.bias.shape
+    pc.wgt.copy_(new.wgt)
+    pc.bias.copy_(new.bias)
+    pc.wgt_hi.copy_(new.wgt_hi)
+    pc.wgt_lo.copy_(new.wgt_lo)
+    for key, t in (pc._frag or {}).items():
+        t.copy_(new.frag_mx() if key == "mx" else new.frag(1, f16=True) if key == "f16" else new.frag(key))
+    if pc._f16 is not None:
+        pc._f16.copy_(new.wgt_f16())
+
+
 def fold_bn(weight, bias, bn_w, bn_b, mean, var, eps=1e-5):
     """Eval-mode BatchNorm folded into the preceding conv (extractor.py:22-26)."""
     s = (bn_w.double() / torch.sqrt(var.double() + eps))
@@ -676,6 +691,56 @@ def convex_weights_at(pts, count, n_max, wlow, mask, hf, wf, crop, wsel, do_sigm
     check(_lib.load().woft_convex_weights_at(ptr(pts), ptr(count), n_max, ptr(wlow), ptr(mask), mask.shape[1], hf, wf,
                                              crop[0], crop[1], int(do_sigmoid), ptr(wsel), stream_ptr()),
           "woft_convex_weights_at")
+
+
+# ---- training of the weight head (csrc/wh_train.hip) ----
+WH_TRAIN_CHUNK = 16                     # WOFT_WH_TRAIN_CHUNK: windows per partial sum of the parameter gradients
+WH_TRAIN_MAX_WIN = 9 * 2048             # WOFT_WH_TRAIN_MAX_WIN
+
+
+def convex_weights_at_bwd(pts, count, n_max, g_wsel, wlow, mask, hf, wf, crop, g_wlow, index=None, do_sigmoid=False):
+    """g_wlow (hf * wf floats, zeroed first) = the gradient of convex_weights_at's wsel with respect to wlow, at the cells listed
+    in `index` (int32, None = every cell): woft_convex_weights_at_bwd."""
+    assert _f32c(g_wsel) and g_wsel.numel() >= n_max and _f32c(g_wlow) and g_wlow.numel() == hf * wf
+    n_win = hf * wf if index is None else index.numel()
+    check(_lib.load().woft_convex_weights_at_bwd(ptr(pts), ptr(count), n_max, ptr(g_wsel), ptr(wlow), ptr(mask), mask.shape[1],
+                                                 hf, wf, crop[0], crop[1], int(do_sigmoid), ptr(index), n_win, ptr(g_wlow),
+                                                 stream_ptr()), "woft_convex_weights_at_bwd")
+
+
+def wh_reduce_bwd(act, w6, g_wlow, index, n_win, g_act, ws, g_w6, g_b6):
+    """Backward of the closing 1x1 conv + window mean on n_win windows of (n_win, 81, 128) activations: g_act, g_w6 (128),
+    g_b6 (1); ws: at least ceil(n_win / WH_TRAIN_CHUNK) * 129 doubles (woft_wh_reduce_bwd)."""
+    assert _f32c(act) and _f32c(g_act) and act.numel() >= n_win * 81 * 128 and g_act.numel() >= n_win * 81 * 128
+    assert ws.dtype == torch.float64 and ws.numel() >= -(-n_win // WH_TRAIN_CHUNK) * 129
+    assert _f32c(w6) and w6.numel() >= 128 and _f32c(g_w6) and g_w6.numel() >= 128 and _f32c(g_b6)
+    assert index is None or (index.dtype == torch.int32 and index.numel() >= n_win)
+    check(_lib.load().woft_wh_reduce_bwd(ptr(act), ptr(w6), ptr(g_wlow), ptr(index), n_win, ptr(g_act), ptr(ws), ptr(g_w6),
+                                         ptr(g_b6), stream_ptr()), "woft_wh_reduce_bwd")
+
+
+def wh_train_conv(x, cin, wt, n_win, y, bias=None, gate=None):
+    """One 3x3 layer cin -> 128 on n_win 9x9 windows, exact fp32 (woft_wh_train_conv): x (n_win, 81, cin), wt (9, cin, 128),
+    y (n_win, 81, 128); with bias: relu(conv + bias); with gate (n_win, 81, 128): conv where gate > 0, else 0."""
+    assert _f32c(x) and x.numel() >= n_win * 81 * cin and _f32c(wt, 9, cin, 128) and _f32c(y) and y.numel() >= n_win * 81 * 128
+    assert bias is None or (_f32c(bias) and bias.numel() == 128)
+    assert gate is None or (_f32c(gate) and gate.numel() >= n_win * 81 * 128)
+    check(_lib.load().woft_wh_train_conv(ptr(x), cin, ptr(wt), ptr(bias), ptr(gate), n_win, ptr(y), stream_ptr()),
+          "woft_wh_train_conv")
+
+
+def wh_wgrad_ws_floats(n_win, cin):
+    return int(_lib.load().woft_wh_wgrad_ws_bytes(n_win, cin)) // 4
+
+
+def wh_wgrad(gy, x, cin, n_win, ws, gw, gb):
+    """Parameter gradient of a 3x3 layer cin -> 128 on n_win windows (woft_wh_wgrad): gy (n_win, 81, 128), x (n_win, 81, cin) ->
+    gw (128, cin_out, 3, 3) with cin_out = gw.shape[1] <= cin, gb (128); ws: wh_wgrad_ws_floats(n_win, cin) floats."""
+    assert _f32c(gy) and gy.numel() >= n_win * 81 * 128 and _f32c(x) and x.numel() >= n_win * 81 * cin
+    assert _f32c(gw) and gw.shape[0] == 128 and tuple(gw.shape[2:]) == (3, 3) and _f32c(gb, 128)
+    assert _f32c(ws) and ws.numel() >= wh_wgrad_ws_floats(n_win, cin)
+    check(_lib.load().woft_wh_wgrad(ptr(gy), ptr(x), cin, gw.shape[1], n_win, ptr(ws), ptr(gw), ptr(gb), stream_ptr()),
+          "woft_wh_wgrad")
 
 
 def upflow8(coords, wlow, hf, wf, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False):

@@ -375,6 +375,37 @@ int woft_flow_chain(const float* fab, const float* fbc, int32_t h, int32_t w, fl
 int woft_flow_fb(const float* fab, const float* fba, int32_t h, int32_t w, float alpha, float beta, float* err, float* ok,
                  void* stream);
 
+/* Multi-delta chaining (csrc/flow_multi.hip).  DESIGN.md section 18.  One candidate chain template -> s -> t is folded into a
+ * running per-pixel best; a tracker calls it once per temporal stride and keeps, per pixel, the most reliable chain.
+ * All planes contiguous fp32 [h][w], flows [2][h][w], best_sel an int32 plane; h, w <= 2^24.  The sampler s(f, q), its validity
+ * rule and its address rule are those of woft_flow_chain above.  One pixel per lane, no LDS, no atomics, no workspace.
+ *
+ * Candidate k: prev_flow / prev_cost / prev_vis = the stored result template -> s (all three NULL: s is the template itself --
+ * flow 0, cost 0, vis 1, nothing is read; any other mix of NULLs is an error); step_flow = the flow s -> t (required);
+ * step_wlogit = its reliability logit (NULL: the step costs the scalar unit_cost >= 0); step_mlogit = its visibility logit
+ * (NULL: the step's visibility is 1).  Per template pixel p = (x, y):
+ *   q    = p + prev_flow(p) in fp32                                 (p for the NULL prev)
+ *   flow = prev_flow(p) + s(step_flow, q)
+ *   cost = prev_cost(p) + softplus(-s(step_wlogit, q))              (the logit is interpolated, then converted;
+ *                                                                    log1pf(expf(-l)), for l < 0 as -l + log1pf(expf(l)))
+ *   vis  = prev_vis(p) * sigmoid(s(step_mlogit, q))
+ *   valid    = q inside [0, w-1] x [0, h-1], and flow, cost, vis and both interpolated logits finite (a NaN anywhere, or an
+ *              infinite logit under a tap, makes the candidate invalid)
+ *   occluded = vis < vis_thr                                        (vis_thr in [0, 1])
+ * The candidates are ordered by the key (occluded, cost), lexicographically.  A valid candidate replaces the running best iff
+ * the best is empty (first != 0, or best_sel < 0), or the best is occluded and the candidate is not, or both have the same
+ * occlusion state and cost < best_cost strictly: an equal key keeps the earlier fold.  An invalid candidate replaces nothing.
+ * A replaced pixel gets flow, cost, vis and best_sel = k (k in [0, 127]).  With first != 0 the running best is not read, and
+ * the pixel of an invalid candidate is written as flow NaN (both planes), cost +inf, vis 0, sel -1.  The occlusion state of
+ * the running best is best_vis < vis_thr with this call's vis_thr.
+ * best_* may share no byte with an input plane or with each other.
+ * -1 (before any launch) on a NULL step_flow or best_*, a partly-NULL prev triple, an overlap of best_* with a plane of this
+ * call, h or w <= 0 or > 2^24, k outside [0, 127], unit_cost negative or NaN, vis_thr outside [0, 1] or NaN. */
+int woft_flow_chain_fold(const float* prev_flow, const float* prev_cost, const float* prev_vis, const float* step_flow,
+                         const float* step_wlogit, const float* step_mlogit, int32_t h, int32_t w, float unit_cost,
+                         float vis_thr, int32_t k, int32_t first, float* best_flow, float* best_cost, float* best_vis,
+                         int32_t* best_sel, void* stream);
+
 /* Weight-head glue (weighted_raft.py:258-279, 347-384).
  * woft_colsum: total[c] = sum_q f[q][c] in fp64 (ws: [n_part][c] doubles).
  * woft_wh_pack: mean[p] = alpha * <f1[p], total>  (= mean_q vol[p,q], weighted_raft.py:358-361, in its

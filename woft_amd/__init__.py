@@ -6,4 +6,7 @@ def __getattr__(name):
     if name in ("chain_flow", "fb_consistency"):
         from .interpolation import chain_flow, fb_consistency
         return chain_flow if name == "chain_flow" else fb_consistency
+    if name in ("chain_fold", "MultiFlowTracker"):
+        from .multiflow import MultiFlowTracker, chain_fold
+        return chain_fold if name == "chain_fold" else MultiFlowTracker
     raise AttributeError(f"module 'woft_amd' has no attribute {name!r}")

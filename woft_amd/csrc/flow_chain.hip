@@ -7,26 +7,11 @@
 // because woft_sample_bilinear stands in for that function.  The EDGE-EXACT sampler of the chain and the check interpolates on
 // the closed rectangle [0, w-1] x [0, h-1] (the last row / column return the data there) and calls everything else invalid.
 //
-// Addresses: every integer index is converted from a float that was first forced into [0, w-1] (or [0, h-1]) by two ordered
-// compares that a NaN fails into the lower bound; w - 1 and h - 1 are exact in fp32 (w, h <= 2^24 is checked by the entry
-// points).  No coordinate, finite or not, can produce an address outside the plane.
-#include <math.h>
-
-#include "common.h"
+// It lives in flow_sample.h (shared with flow_multi.hip), where the address rule is stated: no coordinate, finite or not, can
+// produce an address outside the plane.
+#include "flow_sample.h"
 
 namespace {
-
-constexpr int FC_T = 256;
-// the two per-pixel kernels: a workgroup is FC_TY rows of FC_TX pixels (one wave per row segment: coalesced reads of fab and
-// writes), rows beyond 65535 * FC_TY by a grid-stride loop -- the pixel's (x, y) comes from the launch geometry, no division
-constexpr int FC_TX = 64, FC_TY = 4;
-constexpr int32_t FC_MAX_SIDE = 1 << 24;          // (float)(side - 1) is exact up to here
-
-// v forced into [0, hi]; NaN -> 0, +inf -> hi, -inf -> 0
-__device__ __forceinline__ float clamp_plane(float v, float hi) {
-    const float lo = v >= 0.f ? v : 0.f;
-    return lo <= hi ? lo : hi;
-}
 
 // ---- interpolation.py:92-133, operation for operation in fp32 (every product and sum rounded on its own) ---------------
 __global__ __launch_bounds__(FC_T) void sample_bilinear_kernel(const float* __restrict__ data, int c, int h, int w,
@@ -54,29 +39,6 @@ __global__ __launch_bounds__(FC_T) void sample_bilinear_kernel(const float* __re
         r = __fadd_rn(r, __fmul_rn(wd, p[id]));
         out[ch * n + i] = r;
     }
-}
-
-// ---- the edge-exact sampler of a [2][h][w] flow at q = pixel + fab(pixel) ---------------------------------------------
-struct Tap {
-    bool valid;
-    float sx, sy;
-};
-
-__device__ __forceinline__ Tap sample_flow(const float* __restrict__ f, int h, int w, int64_t plane, float qx, float qy) {
-    const float wm = (float)(w - 1), hm = (float)(h - 1);
-    Tap t;
-    t.valid = qx >= 0.f && qx <= wm && qy >= 0.f && qy <= hm;              // (a NaN fails)
-    const float x0f = clamp_plane(floorf(qx), wm), y0f = clamp_plane(floorf(qy), hm);   // (valid: floor(q) itself)
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
-    const float ax = qx - x0f, ay = qy - y0f;
-    const float bx = 1.f - ax, by = 1.f - ay;
-    const int64_t i00 = (int64_t)y0 * w + x0, i01 = (int64_t)y0 * w + x1, i10 = (int64_t)y1 * w + x0,
-                  i11 = (int64_t)y1 * w + x1;
-    const float* g = f + plane;
-    t.sx = by * (bx * f[i00] + ax * f[i01]) + ay * (bx * f[i10] + ax * f[i11]);
-    t.sy = by * (bx * g[i00] + ax * g[i01]) + ay * (bx * g[i10] + ax * g[i11]);
-    return t;
 }
 
 __global__ __launch_bounds__(FC_T) void flow_chain_kernel(const float* __restrict__ fab, const float* __restrict__ fbc, int h,
@@ -112,13 +74,6 @@ __global__ __launch_bounds__(FC_T) void flow_fb_kernel(const float* __restrict__
         if (ok != nullptr) ok[i] = (t.valid && e2 <= bound) ? 1.f : 0.f;  // (a NaN e2 or bound fails the compare)
     }
 }
-
-inline dim3 pixel_grid(int32_t h, int32_t w) {
-    const int64_t gy = ceil_div64(h, FC_TY);
-    return dim3((unsigned)ceil_div64(w, FC_TX), (unsigned)(gy < 65535 ? gy : 65535));
-}
-
-inline bool bad_side(int32_t h, int32_t w) { return h <= 0 || w <= 0 || h > FC_MAX_SIDE || w > FC_MAX_SIDE; }
 
 }  // namespace
 

@@ -629,6 +629,40 @@ def flow_fb(flow_ab, flow_ba, alpha=0.01, beta=0.5, err=None, ok=None, want_err=
     return err, ok
 
 
+def flow_chain_fold(best, prev, step_flow, step_wlogit=None, step_mlogit=None, k=0, vis_thr=0.5, unit_cost=1.0, first=False):
+    """One candidate chain folded into the running per-pixel best (woft_flow_chain_fold).
+    best = (flow (2, H, W), cost, vis (H*W fp32 each), sel (H*W int32)): contiguous device tensors, updated in place and returned;
+    None allocates them (then `first` must be set).  prev = (flow, cost, vis) of the stored result template -> s, or None for
+    the template itself.  step_flow (2, H, W) = the flow s -> t, step_wlogit / step_mlogit (H*W elements each, optional) its
+    reliability and visibility logits.  The candidate's key is (vis < vis_thr, cost); it replaces the best where its key is
+    strictly smaller, sel then holds k.  first: the best is empty and is not read."""
+    assert step_flow.dim() == 3 and step_flow.shape[0] == 2 and _f32c(step_flow)
+    h, w = step_flow.shape[1:]
+    n = h * w
+    plane = lambda t: t is None or (_f32c(t) and t.numel() == n)
+    assert plane(step_wlogit) and plane(step_mlogit)
+    if prev is not None:
+        assert len(prev) == 3 and _f32c(prev[0], 2, h, w) and _f32c(prev[1]) and prev[1].numel() == n and plane(prev[2]) \
+            and prev[2] is not None
+    k, vis_thr, unit_cost = int(k), float(vis_thr), float(unit_cost)
+    if not 0 <= k <= 127:
+        raise ValueError(f"flow_chain_fold: k must be in [0, 127], got {k}")
+    if not (0.0 <= vis_thr <= 1.0) or not (unit_cost >= 0.0):
+        raise ValueError(f"flow_chain_fold: vis_thr must be in [0, 1] and unit_cost >= 0, got {vis_thr!r}, {unit_cost!r}")
+    if best is None:
+        assert first, "flow_chain_fold: without a running best the fold must be the first"
+        new = lambda dtype: torch.empty((h, w), dtype=dtype, device=step_flow.device)
+        best = (torch.empty_like(step_flow), new(torch.float32), new(torch.float32), new(torch.int32))
+    bf, bc, bv, bs = best
+    assert _f32c(bf, 2, h, w) and plane(bc) and plane(bv) and bc is not None and bv is not None
+    assert bs.dtype == torch.int32 and bs.is_contiguous() and bs.is_cuda and bs.numel() == n
+    pf, pc, pv = prev if prev is not None else (None, None, None)
+    check(_lib.load().woft_flow_chain_fold(ptr(pf), ptr(pc), ptr(pv), ptr(step_flow), ptr(step_wlogit), ptr(step_mlogit), h, w,
+                                           unit_cost, vis_thr, k, int(bool(first)), ptr(bf), ptr(bc), ptr(bv), ptr(bs),
+                                           stream_ptr()), "woft_flow_chain_fold")
+    return best
+
+
 def coords_update(coords, delta, ld_delta, wf, flow4=None, flow_cat=None, ld_cat=0):
     check(_lib.load().woft_coords_update(ptr(coords), ptr(delta), ld_delta, wf, coords.shape[0], ptr(flow4),
                                          ptr(flow_cat), ld_cat, stream_ptr()), "woft_coords_update")

@@ -406,6 +406,29 @@ int woft_flow_chain_fold(const float* prev_flow, const float* prev_cost, const f
                          float vis_thr, int32_t k, int32_t first, float* best_flow, float* best_cost, float* best_vis,
                          int32_t* best_sel, void* stream);
 
+/* A fold result as correspondences for the planar fit (csrc/flow_multi.hip).  DESIGN.md section 19.  flow [2][gh][gw], cost, vis
+ * [gh][gw] fp32 and sel [gh][gw] int32 are what woft_flow_chain_fold leaves; tmask is the frame-sized template mask of
+ * woft_tc_select, uint8 [mh][mw] with gh <= mh, gw <= mw, pixel (x, y) of the grid at tmask[y * mw + x] (NULL: every pixel counts;
+ * mh, mw are then not read).  Per pixel i = y * gw + x, n = gh * gw:
+ *   valid  = 0 <= sel[i] <= 127 and flow_x, flow_y, cost, vis all finite       (the fold writes no sel above 127)
+ *   dst[i] = (float)x + flow_x, dst[n + i] = (float)y + flow_y, one fp32 add each; NaN in both where not valid.  The [2][n]
+ *            layout woft_tc_select* reads, whose bounds check drops NaN.
+ *   w[i]   = expf(-cost) where valid, else 0: the product of the chain's sigmoid(reliability logit).  w may be NULL: nothing is
+ *            computed or stored for it.
+ *   ok[i]  = 1.0f where valid and not (vis < vis_thr), else 0.0f: the fold's occlusion rule (vis == vis_thr is not occluded), to
+ *            be gated at 0.5 in the visibility slot of woft_tc_select_vis.
+ *   hist   (may be NULL) int32 [WOFT_CHAIN_HIST], over the pixels whose tmask byte is non-zero: hist[s] = pixels with ok = 1 and
+ *            sel = s, hist[128] = pixels that are not valid, hist[129] = valid but occluded pixels.  Zeroed by this call on the
+ *            stream; blocks count in LDS and add their non-zero counters with integer atomics: deterministic.  The counters are
+ *            int32: meaningful for fewer than 2^31 masked pixels.
+ * One pixel per lane in the fold's geometry, no workspace, no floating-point atomics.  No input value addresses anything but
+ * the range-checked sel, which indexes the LDS counters.
+ * -1 (before any launch) on a NULL flow / cost / vis / sel / dst / ok, gh or gw <= 0 or > 2^24, mh < gh or mw < gw with a tmask,
+ * vis_thr outside [0, 1] or NaN, an output that shares a byte with an input or with another output. */
+#define WOFT_CHAIN_HIST 130
+int woft_chain_tc(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask, int32_t gh,
+                  int32_t gw, int32_t mh, int32_t mw, float vis_thr, float* dst, float* w, float* ok, int32_t* hist, void* stream);
+
 /* Weight-head glue (weighted_raft.py:258-279, 347-384).
  * woft_colsum: total[c] = sum_q f[q][c] in fp64 (ws: [n_part][c] doubles).
  * woft_wh_pack: mean[p] = alpha * <f1[p], total>  (= mean_q vol[p,q], weighted_raft.py:358-361, in its

@@ -9,4 +9,7 @@ def __getattr__(name):
     if name in ("chain_fold", "MultiFlowTracker"):
         from .multiflow import MultiFlowTracker, chain_fold
         return chain_fold if name == "chain_fold" else MultiFlowTracker
+    if name in ("chain_correspondences", "WOFTChained"):
+        from .chained import WOFTChained, chain_correspondences
+        return chain_correspondences if name == "chain_correspondences" else WOFTChained
     raise AttributeError(f"module 'woft_amd' has no attribute {name!r}")

@@ -1,6 +1,8 @@
 // Multi-delta flow chaining: one candidate chain folded into a running per-pixel best (the combination step of a dense
 // long-term tracker that chains flows over several temporal strides and keeps, per pixel, the most reliable chain).
 // DESIGN.md section 18.  One streaming kernel with a local gather, one template pixel per lane: no LDS, no atomics, no workspace.
+// Below it, the step from a fold result to the planar fit's correspondences (woft_chain_tc): streaming, no
+// gather, the 130 integer counters of its histogram in LDS.
 //
 // The sampler, its address rule and the launch geometry are those of flow_chain.hip (flow_sample.h): every tap address derives
 // from a clamped float, so no input, finite or not, addresses outside a plane; the pixel's own planes are read at (x, y) of the
@@ -64,6 +66,60 @@ __global__ __launch_bounds__(FC_T) void flow_chain_fold_kernel(const float* __re
     }
 }
 
+constexpr unsigned CHAIN_TC_BLOCKS = 2048;        // blocks of a launch with a histogram: 256 CUs x 8 blocks of 4 waves
+
+// A fold result turned into what the planar fit reads: target coordinates, the fit weight exp(-cost), the
+// 0/1 occlusion gate and the histogram of winning candidates under the template mask.  The fold's geometry: the pixel's (x, y)
+// comes from the launch geometry and addresses everything; `sel` is the only input value used as an index, range-checked first,
+// and it indexes the LDS counters alone.  A wave is one row segment (FC_TX = 64 lanes), so y and the loop's trip count are
+// wave-uniform and every lane of a wave reaches the ballots below.
+__global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict__ flow, const float* __restrict__ cost,
+                                                        const float* __restrict__ vis, const int32_t* __restrict__ sel,
+                                                        const uint8_t* __restrict__ tmask, int gh, int gw, int mw, float vis_thr,
+                                                        float* __restrict__ dst, float* __restrict__ w, float* __restrict__ ok,
+                                                        int32_t* __restrict__ hist) {
+    __shared__ int32_t bins[WOFT_CHAIN_HIST];
+    const int tid = (int)threadIdx.y * FC_TX + (int)threadIdx.x;
+    if (hist != nullptr) {
+        if (tid < WOFT_CHAIN_HIST) bins[tid] = 0;
+        __syncthreads();
+    }
+    const int64_t plane = (int64_t)gh * gw;
+    const int x = (int)blockIdx.x * FC_TX + (int)threadIdx.x;
+    const bool in = x < gw;
+    for (int y = (int)blockIdx.y * FC_TY + (int)threadIdx.y; y < gh; y += (int)gridDim.y * FC_TY) {
+        int bin = -1;                                 // the counter this lane adds to (-1: none)
+        if (in) {
+            const int64_t i = (int64_t)y * gw + x;
+            const float fx = flow[i], fy = flow[plane + i], c = cost[i], v = vis[i];
+            const int32_t s = sel[i];
+            const bool valid = s >= 0 && s < WOFT_CHAIN_HIST - 2 && isfinite(fx) && isfinite(fy) && isfinite(c) && isfinite(v);
+            const bool seen = valid && !(v < vis_thr);                    // the fold's occlusion rule
+            dst[i] = valid ? (float)x + fx : NAN;
+            dst[plane + i] = valid ? (float)y + fy : NAN;
+            if (w != nullptr) w[i] = valid ? expf(-c) : 0.f;
+            ok[i] = seen ? 1.f : 0.f;
+            if (hist != nullptr && (tmask == nullptr || tmask[(int64_t)y * mw + x] != 0))
+                bin = !valid ? WOFT_CHAIN_HIST - 2 : (seen ? s : WOFT_CHAIN_HIST - 1);
+        }
+        if (hist != nullptr) {
+            // one LDS add per distinct counter of the wave (a frame's pixels mostly agree on it), by the first lane that holds it
+            uint64_t todo = __ballot(bin >= 0);
+            while (todo != 0) {
+                const int lead = __ffsll((unsigned long long)todo) - 1;
+                const int b = __shfl(bin, lead);
+                const uint64_t same = __ballot(bin == b);
+                if ((int)threadIdx.x == lead) atomicAdd(&bins[b], (int32_t)__popcll(same));
+                todo &= ~same;
+            }
+        }
+    }
+    if (hist != nullptr) {
+        __syncthreads();
+        if (tid < WOFT_CHAIN_HIST && bins[tid] != 0) atomicAdd(&hist[tid], bins[tid]);
+    }
+}
+
 // [a, a + na) and [b, b + nb) share a byte
 inline bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
     const uint64_t pa = (uint64_t)(uintptr_t)a, pb = (uint64_t)(uintptr_t)b;
@@ -94,5 +150,39 @@ extern "C" int woft_flow_chain_fold(const float* prev_flow, const float* prev_co
     hipLaunchKernelGGL(flow_chain_fold_kernel, pixel_grid(h, w), dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, prev_flow, prev_cost,
                        prev_vis, step_flow, step_wlogit, step_mlogit, h, w, unit_cost, vis_thr, k, first != 0, best_flow, best_cost,
                        best_vis, best_sel);
+    return woft_launch_status();
+}
+
+extern "C" int woft_chain_tc(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask,
+                             int32_t gh, int32_t gw, int32_t mh, int32_t mw, float vis_thr, float* dst, float* w, float* ok,
+                             int32_t* hist, void* stream) {
+    if (!flow || !cost || !vis || !sel || !dst || !ok || bad_side(gh, gw)) return WOFT_EINVAL;
+    if (tmask != nullptr && (mh < gh || mw < gw)) return WOFT_EINVAL;
+    if (!(vis_thr >= 0.f && vis_thr <= 1.f)) return WOFT_EINVAL;                                                  // (NaN fails)
+    // every pixel's outputs are written while other pixels' inputs are still unread: an output may share no byte with an input or
+    // with another output (overlap() lets a NULL through)
+    const uint64_t pb = (uint64_t)gh * (uint64_t)gw * 4u;
+    const void* outs[4] = {dst, w, ok, hist};
+    const uint64_t nout[4] = {2 * pb, pb, pb, WOFT_CHAIN_HIST * sizeof(int32_t)};
+    const void* ins[5] = {flow, cost, vis, sel, tmask};
+    const uint64_t nin[5] = {2 * pb, pb, pb, pb, tmask ? (uint64_t)mh * (uint64_t)mw : 0u};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = 0; b < 5; ++b)
+            if (overlap(outs[a], nout[a], ins[b], nin[b])) return WOFT_EINVAL;
+        for (int b = a + 1; b < 4; ++b)
+            if (overlap(outs[a], nout[a], outs[b], nout[b])) return WOFT_EINVAL;
+    }
+    if (hist != nullptr && hipMemsetAsync(hist, 0, WOFT_CHAIN_HIST * sizeof(int32_t), (hipStream_t)stream) != hipSuccess)
+        return WOFT_ELAUNCH;
+    // With a histogram every block ends in a few atomics on the same handful of counters, and those serialise: one block per
+    // 64 x 4 tile (8 100 at 1080p) spent more time there than streaming.  So the grid is cut to about one resident set of blocks
+    // and the row loop does the rest: same tiles, same addresses, a quarter of the atomics at 1080p.
+    dim3 grid = pixel_grid(gh, gw);
+    if (hist != nullptr) {
+        const unsigned rows = CHAIN_TC_BLOCKS / grid.x;
+        grid.y = grid.y < rows ? grid.y : (rows > 0 ? rows : 1u);
+    }
+    hipLaunchKernelGGL(chain_tc_kernel, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tmask, gh, gw,
+                       tmask ? mw : gw, vis_thr, dst, w, ok, hist);
     return woft_launch_status();
 }

@@ -663,6 +663,40 @@ def flow_chain_fold(best, prev, step_flow, step_wlogit=None, step_mlogit=None, k
     return best
 
 
+CHAIN_HIST = 130        # WOFT_CHAIN_HIST: one counter per candidate index 0..127, [128] invalid, [129] valid but occluded
+
+
+def chain_tc(flow, cost, vis, sel, tmask_u8, vis_thr, want_w=True, mask_hw=None, out=None):
+    """A fold result as correspondences for the planar fit (woft_chain_tc) -> (dst (2, n), w (1, n) | None,
+    ok (1, n), hist (130,) int32), n = H * W.  flow (2, H, W), cost, vis (n fp32 each), sel (n int32): contiguous device tensors,
+    what flow_chain_fold leaves.  tmask_u8: the template mask (uint8, mask_hw = (mh, mw) >= (H, W), default the grid's size), or
+    None: every pixel counts in hist.  dst = pixel + flow (NaN where the pixel has no valid chain), w = exp(-cost) (0 there;
+    want_w=False: not computed), ok = 1 where valid and not (vis < vis_thr), hist[s] = masked pixels with ok = 1 and sel = s,
+    hist[128] = masked invalid pixels, hist[129] = masked occluded ones.  out: the tuple of an earlier call at this size, reused."""
+    assert flow.dim() == 3 and flow.shape[0] == 2 and _f32c(flow)
+    h, w = flow.shape[1:]
+    n = h * w
+    assert all(_f32c(t) and t.numel() == n for t in (cost, vis))
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.is_cuda and sel.numel() == n
+    vis_thr = float(vis_thr)
+    if not (0.0 <= vis_thr <= 1.0):
+        raise ValueError(f"chain_tc: vis_thr must be in [0, 1], got {vis_thr!r}")
+    mh, mw = mask_hw or (h, w)
+    if tmask_u8 is not None:
+        assert tmask_u8.dtype == torch.uint8 and tmask_u8.is_contiguous() and tmask_u8.is_cuda and tmask_u8.numel() == mh * mw
+    if out is None:
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=flow.device)
+        out = (new(2, n), new(1, n) if want_w else None, new(1, n), torch.empty(CHAIN_HIST, dtype=torch.int32, device=flow.device))
+    dst, wout, ok, hist = out
+    if not want_w:
+        wout = None
+    assert _f32c(dst, 2, n) and _f32c(ok, 1, n) and (wout is None or _f32c(wout, 1, n))
+    assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda and hist.numel() == CHAIN_HIST)
+    check(_lib.load().woft_chain_tc(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tmask_u8), h, w, mh, mw, vis_thr, ptr(dst),
+                                    ptr(wout), ptr(ok), ptr(hist), stream_ptr()), "woft_chain_tc")
+    return dst, wout, ok, hist
+
+
 def coords_update(coords, delta, ld_delta, wf, flow4=None, flow_cat=None, ld_cat=0):
     check(_lib.load().woft_coords_update(ptr(coords), ptr(delta), ld_delta, wf, coords.shape[0], ptr(flow4),
                                          ptr(flow_cat), ld_cat, stream_ptr()), "woft_coords_update")

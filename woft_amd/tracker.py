@@ -140,6 +140,9 @@ class YAOFTrackerSingleControl:
     DEVICE = "cuda"                  # (a host-logic test may build the tracker around a stub flow provider on "cpu")
 
     VISIBILITY_MODES = ("gate", "weight")
+    # a 'weighted_masked' flow config is refused without a `visibility_mode` (nobody would read the mask); a subclass whose flows
+    # are consumed elsewhere (woft_amd.chained.WOFTChained: the fold reads the mask) says so here
+    MASK_NEEDS_VISIBILITY_MODE = True
 
     def _visibility_config(self):
         """-> (mode | None, threshold as the fp32 value the kernels compare with).  Config keys `visibility_mode` (absent / falsy:
@@ -215,7 +218,7 @@ class YAOFTrackerSingleControl:
         # what the solver's visibility slot carries: the MaskHead's probability under a visibility mode, the forward-backward
         # verdict (0 / 1, gated at 0.5) under fb_check -- never both (_fb_config)
         self._vis_mode, self._vis_thr = (("gate", 0.5) if self.fb_check else (self.visibility_mode, self.visibility_thr))
-        if config.flow_config.raft_type == "weighted_masked" and self.visibility_mode is None:
+        if config.flow_config.raft_type == "weighted_masked" and self.visibility_mode is None and self.MASK_NEEDS_VISIBILITY_MODE:
             # the tracker unpacks (src, dst, weights) from compute_flow (TRK:101,181); a 'weighted_masked' provider returns a fourth
             # value, the visibility mask, which the tracker consumes only under a `visibility_mode`: refused here rather than at the first frame
             raise ValueError("the tracker takes a flow config with raft_type 'orig' or 'weighted'; 'weighted_masked' (MaskHead "
@@ -265,7 +268,7 @@ class YAOFTrackerSingleControl:
             return None
         if not hasattr(self.flower, "pin_source"):
             return None
-        if self.flower.C.raft_type != ("weighted" if self.visibility_mode is None else "weighted_masked"):
+        if not self._device_solver_reads(self.flower.C.raft_type):
             return None
         from .probe import solver_spec
         spec, how = solver_spec(C.H_estimator, C.subsampler_fn or None, C.redet_success_fn, device=self.device)
@@ -284,6 +287,10 @@ class YAOFTrackerSingleControl:
         n_draw = spec["n_draw"]
         spec["sobol_u"] = torch.from_numpy(sobol_points(n_draw).astype(np.float32)).to(self.device) if n_draw else None
         return spec
+
+    def _device_solver_reads(self, raft_type):
+        """Whether the device back end can take its weights (and its visibility) from a provider of this raft_type."""
+        return raft_type == ("weighted" if self.visibility_mode is None else "weighted_masked")
 
     def _fused_buffers(self, n_grid):
         # (WOFTWindow._fused_buffers swaps `_fb_key` / `_fb` from its own per-size cache: keep these two names)

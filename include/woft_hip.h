@@ -429,6 +429,27 @@ int woft_flow_chain_fold(const float* prev_flow, const float* prev_cost, const f
 int woft_chain_tc(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask, int32_t gh,
                   int32_t gw, int32_t mh, int32_t mw, float vis_thr, float* dst, float* w, float* ok, int32_t* hist, void* stream);
 
+/* Frame-features record (csrc/features.hip).  DESIGN.md section 20.  What the encoders produce for one image at one padded
+ * geometry, P = (hp / 8) * (wp / 8) pixels, as one contiguous fp32 block: record = [P][fdim] fnet map | [P][hdim] net (after
+ * tanh) | [P][cdim] inp (after relu) -- 4 * P * (fdim + hdim + cdim) bytes.  Everything else a flow reads of an image (split
+ * operands, pyramid, volumes, gate biases) is derived from these.  Streaming copies, 16 bytes per lane and step, no atomics,
+ * no workspace; values are moved, never recomputed: every restored float has the bits that were packed.
+ * woft_features_pack: the rows of f1 (row stride ld_f1 floats), net (ld_net) and inp (ld_inp: the first cdim channels of the
+ *   GRU input buffer, whose rows are wider) -> record.
+ * woft_features_unpack, source role (net, xbuf and inp_c all given): record -> fmap rows (ld_fmap), net (ld_net), the first cdim
+ *   channels of xbuf's rows (ld_xbuf) and the same values in inp_c (ld_inp_c), in one launch; with fmap_split also the [hi | lo]
+ *   lines of the fnet map in the same pass, bit for bit what woft_split_bf16_lines makes of those P rows (needs ld_fmap ==
+ *   fdim and fdim % 32 == 0).  Target role (net, xbuf, inp_c and fmap_split all NULL): the fnet map alone -> fmap (ld_fmap).
+ *   Nothing outside the named maps is written: rows beyond P and channels beyond the map's count keep what they hold.
+ * WOFT_EINVAL before any launch on a NULL record or map (in the source role: any of net, xbuf, inp_c missing), P < 1, a
+ * channel count that is not a positive multiple of 4 (or above 4096), a row stride below the channel count or not a multiple
+ * of 4, fmap_split outside the conditions above, or a record of 2^31 or more float4s. */
+int woft_features_pack(const float* f1, int64_t ld_f1, const float* net, int64_t ld_net, const float* inp, int64_t ld_inp,
+                       int64_t P, int32_t fdim, int32_t hdim, int32_t cdim, float* record, void* stream);
+int woft_features_unpack(const float* record, int64_t P, int32_t fdim, int32_t hdim, int32_t cdim, float* fmap, int64_t ld_fmap,
+                         void* fmap_split, float* net, int64_t ld_net, float* xbuf, int64_t ld_xbuf, float* inp_c,
+                         int64_t ld_inp_c, void* stream);
+
 /* Weight-head glue (weighted_raft.py:258-279, 347-384).
  * woft_colsum: total[c] = sum_q f[q][c] in fp64 (ws: [n_part][c] doubles).
  * woft_wh_pack: mean[p] = alpha * <f1[p], total>  (= mean_q vol[p,q], weighted_raft.py:358-361, in its

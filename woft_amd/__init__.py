@@ -12,4 +12,7 @@ def __getattr__(name):
     if name in ("chain_correspondences", "WOFTChained"):
         from .chained import WOFTChained, chain_correspondences
         return chain_correspondences if name == "chain_correspondences" else WOFTChained
+    if name == "FrameFeatures":
+        from .flow_provider import FrameFeatures
+        return FrameFeatures
     raise AttributeError(f"module 'woft_amd' has no attribute {name!r}")

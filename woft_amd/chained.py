@@ -92,7 +92,8 @@ class WOFTChained(YAOFTrackerSingleControl):
 
     Config keys, all optional: chain_deltas (default (None, 1, 2, 4, 8, 16, 32)), chain_vis_thr (0.5), chain_unit_cost (1.0),
     chain_iters (None: the flow config's), chain_weights (True; False, or an unweighted estimator preset: exp(-cost) is not
-    computed and the fit is unweighted).  raft_type 'orig' chains on unit costs (w = exp(-chain_unit_cost * chain length)),
+    computed and the fit is unweighted), chain_share_features (False; True: every frame is encoded once and its flows run from the
+    record -- MultiFlowTracker(share_features=True), bit-identical, 66.4 MB more per stored 1080p frame).  raft_type 'orig' chains on unit costs (w = exp(-chain_unit_cost * chain length)),
     'weighted' on the reliability logit, 'weighted_masked' also on the visibility logit -- without a `visibility_mode`: the fold
     consumes the mask.  `pw_mask`, `no_prewarp_after_N`, `no_local_H` and `do_not_mask_TCs_by_prewarped` are not used.
 
@@ -123,13 +124,15 @@ class WOFTChained(YAOFTrackerSingleControl):
         self.chain_unit_cost = _get(config, "chain_unit_cost", 1.0)
         self.chain_iters = _get(config, "chain_iters", None)
         self.chain_weights = bool(_get(config, "chain_weights", True))
+        self.chain_share_features = bool(_get(config, "chain_share_features", False))
         super().__init__(config)
         if not hasattr(self.flower, "pin_source"):
             raise NotImplementedError("the chained tracker needs this project's flow provider (pin_source, compute_flow(mode='flow', "
                                       f"borrow=True)); {type(self.flower).__name__} has no pin_source")
         self.multi = self._new_multi()            # (validates the chain keys)
         self.chain_deltas = self.multi.deltas
-        self.solver_decision += (f"; chained deltas {self.chain_deltas}; pw_mask, no_prewarp_after_N, no_local_H and "
+        self.solver_decision += (f"; chained deltas {self.chain_deltas}; chain_share_features "
+                                 f"{'on: every frame encoded once' if self.chain_share_features else 'off'}; pw_mask, no_prewarp_after_N, no_local_H and "
                                  "do_not_mask_TCs_by_prewarped are not used")
         if self._fused is not None and not self.chain_weights:
             self._fused = dict(self._fused, weighted=False)
@@ -140,7 +143,7 @@ class WOFTChained(YAOFTrackerSingleControl):
 
     def _new_multi(self):
         return MultiFlowTracker(self.flower, deltas=self.chain_deltas, vis_thr=self.chain_vis_thr, unit_cost=self.chain_unit_cost,
-                                iters=self.chain_iters)
+                                iters=self.chain_iters, share_features=self.chain_share_features)
 
     def _device_solver_reads(self, raft_type):
         return True                               # (weights and gate come from chain_tc, whatever the network provides)

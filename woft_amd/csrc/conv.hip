@@ -30,6 +30,7 @@
 #include "conv_common.h"
 #include "dma.h"
 #include "halo_map.h"
+#include "split_lines.h"
 
 // Build parts (woft_amd/build.py): this file is compiled once per precision code of woft_conv_params -- -DWOFT_ONLY_PREC=1 (bf16x3:
 // the TERMS = 3 instances + the C ABI entry points), 2 (bf16: TERMS = 1 + the exact-fp32 kernel), 3 (fp16: TERMS = 16 + the
@@ -1200,11 +1201,7 @@ extern "C" int woft_set_tuning(int key, int value) {
 __global__ void split_bf16_lines_kernel(const float* __restrict__ x, int64_t n4, __bf16* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
-    const f32x4 vv = *(const f32x4*)(x + i * 4);
-    const bf16x4 h = __builtin_convertvector(vv, bf16x4);
-    __bf16* line = out + (i >> 3) * 64 + (i & 7) * 4;       // 32 inputs -> one 128-byte line [32 hi | 32 lo]
-    *(bf16x4*)line = h;
-    *(bf16x4*)(line + 32) = __builtin_convertvector(vv - __builtin_convertvector(h, f32x4), bf16x4);
+    split_bf16_lines_store(out, i, *(const f32x4*)(x + i * 4));     // 32 inputs -> one 128-byte line [32 hi | 32 lo]
 }
 
 extern "C" int woft_split_bf16_lines(const float* x, int64_t n, void* out, void* stream) {

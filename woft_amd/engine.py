@@ -905,6 +905,46 @@ class _Plan:
         self.run(self.prog_gate_bias)
         return reused
 
+    # ---- frame-features records: an image encoded once, restored as the source or target of any flow ----
+    @property
+    def record_dims(self):
+        sp = self.eng.spec
+        return sp.fdim, sp.hdim, sp.cdim
+
+    def new_record(self):
+        """An empty record for this plan's geometry: P * (fdim + hdim + cdim) floats of the caller's own."""
+        return torch.empty(ops.features_record_floats(self.P, *self.record_dims), dtype=torch.float32, device="cuda")
+
+    def encode_record(self, record):
+        """fnet and cnet on the image in img[0] (the launch programs of encode_source), then the fnet map, net and inp packed into
+        `record` (woft_features_pack).  Overwrites this plan's source maps: whatever source was resident here is gone, and the
+        reuse book-keeping is reset (target_valid, source_tag) -- the derived source state (split operand, gate biases) is NOT
+        brought up to date, restore_source() does that."""
+        self.source_tag, self.target_valid = None, False
+        self.run(self.prog_f_src)
+        self.run(self.prog_c_src)
+        ops.features_pack(self.f1rows, self.net0.t, self.xbuf.t, self.P, self.record_dims, record)
+
+    def restore_source(self, record):
+        """The state encode_source() leaves for the record's image, bit for bit, without an encoder pass: one unpack launch writes
+        the fnet rows, net, inp (GRU input buffer and inp_c) and, where the correlation operand is [hi | lo] lines, those in the
+        same pass (pad rows beyond P are never written: they stay zero); then the derived steps encode_source() runs -- the
+        split where it is not fused, the gate-bias convs."""
+        x3 = self.prec != "fp32" and self.prec_corr == "bf16x3"
+        self.source_tag = None
+        ops.features_unpack(record, self.P, self.record_dims, self.f1rows, self.f1s if x3 else None, self.net0.t, self.xbuf.t,
+                            self.inp_c.t)
+        if self.prec != "fp32" and not x3:
+            self._split(self.f1rows, self.f1s)
+        self.run(self.prog_gate_bias)
+
+    def restore_target(self, record):
+        """The record's fnet map -> the level-0 target map f2act[0]: flow(target_restored=True) then skips prog_f_dst and derives
+        the pyramid / volumes from it (prog_volume starts from f2act[0] in every corr mode).  Until that flow has run the level-0
+        operand is stale: target_valid is cleared, flow() sets it."""
+        self.target_valid = False
+        ops.features_unpack(record, self.P, self.record_dims, self.f2act[0].t)
+
     def set_flow_init(self, flow_init):
         """Copy the caller's initial flow -- (2, hf, wf), 1/8-resolution pixels of the padded image, any float dtype, either
         device -- into the plan's own buffer; flow(..., flow_init=True) then starts from it."""
@@ -919,7 +959,7 @@ class _Plan:
         return self.flow4.t[:, :2].t().reshape(2, self.hf, self.wf).contiguous()
 
     def flow(self, iters, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False, trace=None, defer_wh=False,
-             mout=None, mask_sigmoid=False, flow_init=None, skip_wh=False):
+             mout=None, mask_sigmoid=False, flow_init=None, skip_wh=False, target_restored=False):
         """Target features -> volume -> `iters` refinements -> full-resolution outputs.
         defer_wh (full weighted model with a weight region set): stop before the weight head -- flow_up / dst are final,
         wout is NOT written -- and let finish_weights() evaluate the head where the caller then says it reads the weights.
@@ -932,11 +972,13 @@ class _Plan:
         flow_init (weighted_raft.py:184,223-224: coords1 = coords1 + flow_init): None = start from zero flow; a (2, hf, wf)
         tensor = copied into the plan's buffer first (set_flow_init); True = the buffer as it stands.  The first iteration's
         motion encoder reads it as the flow, the later coordinate updates write coords1 - coords0 as ever.  With a trace, the
-        trace is also called once as trace(plan, -1) after the initialisation, before the first iteration."""
+        trace is also called once as trace(plan, -1) after the initialisation, before the first iteration.
+        target_restored: f2act[0] already holds the target's fnet map (restore_target): no encoder pass over img[1]."""
         e, sp = self.eng, self.eng.spec
         if iters < 1:
             raise ValueError("iters must be >= 1")
-        self.run(self.prog_f_dst)
+        if not target_restored:
+            self.run(self.prog_f_dst)
         self.run(self.prog_volume)
         self.target_valid = True                             # (level-0 target map + operand now belong to the image in img[1])
         if flow_init is None:

@@ -57,6 +57,30 @@ def _mask_head_shapes(structure, fdim):
     return shapes + [(1, cur, 1, 1)]
 
 
+class FrameFeatures:
+    """One frame, encoded: what RAFTWrapper.encode_frame() returns and compute_flow() accepts in place of
+    an image, as source or as target.  Owns its device record -- the fnet map, net and inp in fp32, `nbytes` = 4 * P * (fdim +
+    hdim + cdim): 66.4 MB for a 1080p frame on the full model -- never a view of a plan buffer; valid for the provider that made it,
+    at the padded geometry it was made at, for as long as it is referenced (sync_weight_head() does not touch it: the encoders
+    are frozen).
+    provider; geometry = (hp, wp, top, left) of the padded image; size = (H, W) of the un-padded image; shape = (H, W, 3)."""
+
+    def __init__(self, provider, record, geometry, size):
+        self.provider, self.record = provider, record
+        self.geometry, self.size = tuple(int(v) for v in geometry), tuple(int(v) for v in size)
+
+    @property
+    def shape(self):
+        return self.size + (3,)
+
+    @property
+    def nbytes(self):
+        return self.record.numel() * self.record.element_size()
+
+    def __repr__(self):
+        return f"FrameFeatures({self.size[0]} x {self.size[1]}, padded geometry {self.geometry}, {self.nbytes} bytes)"
+
+
 class _Recent:
     """Least-recently-used book-keeping of RAFTWrapper.bound_plans(): touch(key, keep) marks `key` as used now and returns the
     keys that fall out -- all but the `keep` most recent ones, never the protected key (the one last touched with protect=True)."""
@@ -200,11 +224,13 @@ class RAFTWrapper:
             self._all_pixels.pop(key, None)
 
     def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True, mask_sigmoid=False,
-                  has_init=False, skip_wh=False):
+                  has_init=False, skip_wh=False, target_restored=False):
         """plan.flow() eagerly, or -- use_graph -- as ONE hipGraph launch (captured at the second call with the same
         arguments; the per-launch event hooks of bench.py force the eager path).
         has_init: start from the plan's flow_init buffer (filled by the caller BEFORE this call: a replayed graph reads the
-        buffer's fixed address, the copy into it is not part of the graph)."""
+        buffer's fixed address, the copy into it is not part of the graph).
+        target_restored: the target's fnet map was restored from a record (also before this call, outside any graph) -- no target
+        encoder pass: other launches, another graph."""
         self._wh_flow = (plan, crop)                       # (what weights_at() evaluates the head on)
         if plan._wh_train is not None:                     # (a weights_at() graph of an earlier flow in this plan is stale now: its
             plan._wh_train["gen"] += 1                     #  backward would read this flow's upsampling mask -- it raises instead)
@@ -213,14 +239,14 @@ class RAFTWrapper:
             # (mode "TC" hands out dst = grid + flow only: the (2, H, W) flow map is then not written at all)
             plan.flow(iters, crop, oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"], wout=o["w"] if weighted else None,
                       do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"), mask_sigmoid=mask_sigmoid,
-                      flow_init=True if has_init else None, skip_wh=skip_wh)
+                      flow_init=True if has_init else None, skip_wh=skip_wh, target_restored=target_restored)
         if not self.use_graph or plan.lookup_events is not None or plan.wh_events is not None or plan.conv_events is not None:
             return eager()
         region = plan.wh_region
         fregion = plan.flow_region if not has_init else None     # (restricted iterations are other launches: other graphs)
         key = (iters, crop, oh, ow, weighted, do_sigmoid, want_flow, bool(defer_wh), o["flow"].data_ptr(),
                region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid), bool(has_init),
-               fregion["key"] if fregion is not None else None, bool(skip_wh))
+               fregion["key"] if fregion is not None else None, bool(skip_wh), bool(target_restored))
         g = plan._graphs.get(key)
         if g is None:
             eager()                                        # this call's results; also the warm-up the capture needs
@@ -463,7 +489,47 @@ class RAFTWrapper:
             raise RuntimeError("flow_map(): the last flow wrote no flow map (mode 'TC' without keep_flow, or no flow yet)")
         return m
 
-    def compute_flow_fb(self, src_img, dst_img, alpha=0.01, beta=0.5, numpy_out=False):
+    def _upload(self, a, H, W, lh, lw, what="compute_flow"):
+        """An image argument -> its (lh, lw, 3) uint8 tensor on the device."""
+        if isinstance(a, torch.Tensor):
+            t = a if a.is_cuda else a.cuda(non_blocking=True)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(a)).cuda(non_blocking=True)
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+            raise TypeError(f"{what} takes (H, W, 3) uint8 BGR images, got {tuple(t.shape)} {t.dtype}")
+        if (lh, lw) != (H, W):
+            t = t[:lh, :lw].contiguous()
+        return t.contiguous()
+
+    def _operand_geometry(self, a):
+        """(hp, wp, top, left, H, W) of an image or a FrameFeatures argument of compute_flow."""
+        if isinstance(a, FrameFeatures):
+            return a.geometry + a.size
+        h, w = int(a.shape[0]), int(a.shape[1])
+        return tuple(_pad_geometry(h, w, self.C.padding_mode)[:4]) + (h, w)
+
+    def encode_frame(self, img):
+        """Encode one frame once: img, (H, W, 3) uint8 BGR (numpy or a device tensor) -> FrameFeatures, which compute_flow() and
+        compute_flow_fb() accept in place of the image, as source or target, any number of times; the flows have the bits of
+        the flows from the image (InstanceNorm and eval-mode BatchNorm are per sample: the restored maps are the values the
+        encoder passes of those flows would produce).  One fnet pass, one cnet pass and one pack launch; the record is a new
+        device tensor of the caller's own (66.4 MB at 1080p on the full model).  Runs in the buffer set a flow from a non-pinned
+        source runs in -- the pinned source's resident state is not touched -- and resets that set's reuse book-keeping
+        (src_is_previous_dst finds nothing to reuse after it)."""
+        H, W = img.shape[:2]
+        hp, wp, top, left, oh, ow, lh, lw = _pad_geometry(H, W, self.C.padding_mode)
+        slot = 0 if self._pinned is None else 1
+        plan = self.engine.plan(hp, wp, slot)
+        self._touch_plan((hp, wp) if slot == 0 else (hp, wp, slot), (oh, ow), plan.P, False)
+        plan.load_image(0, self._upload(img, H, W, lh, lw, "encode_frame"), top, left)
+        self._last_dst.pop(id(plan), None)
+        if slot == 0:
+            self._pinned_key = None
+        record = plan.new_record()
+        plan.encode_record(record)
+        return FrameFeatures(self, record, (hp, wp, top, left), (H, W))
+
+    def compute_flow_fb(self, src_img, dst_img, alpha=0.01, beta=0.5, numpy_out=False, share_features=False):
         """Both flows of an image pair and their forward-backward consistency (no counterpart in raft.py)
         -> (flow_fwd (2, H, W), flow_bwd (2, H, W), err (1, H, W), ok (1, H, W)) as tensors of the caller's own (numpy_out: arrays).
         Two ordinary flows -- flow_fwd has the bits of compute_flow(src_img, dst_img, mode='flow'), flow_bwd those of
@@ -471,10 +537,14 @@ class RAFTWrapper:
         err = |flow_fwd + b| and ok = 1.0 where that point is inside the frame and err^2 <= alpha * (|flow_fwd|^2 + |b|^2) + beta
         (else 0.0; outside the frame err = +inf).  Every raft_type and every padding_mode the provider has; the flow cache is not
         consulted.  Neither flow's weights are returned, so the weight head is skipped where the network allows it.
-        Like any other call it replaces the state the previous call left (borrowed buffers, deferred weights, flow_low())."""
+        Like any other call it replaces the state the previous call left (borrowed buffers, deferred weights, flow_low()).
+        src_img / dst_img may be FrameFeatures.  share_features (default off): encode each image once (encode_frame) and run both
+        directions from the records -- four encoder passes instead of six, the same bits."""
         alpha, beta = float(alpha), float(beta)
         if not (0.0 <= alpha < float("inf")) or not (0.0 <= beta < float("inf")):
             raise ValueError(f"compute_flow_fb: alpha and beta must be finite and >= 0, got {alpha!r}, {beta!r}")
+        if share_features:
+            src_img, dst_img = (a if isinstance(a, FrameFeatures) else self.encode_frame(a) for a in (src_img, dst_img))
         # (each flow is cloned out of the per-size output buffers before the next one overwrites them)
         fwd = self.compute_flow(src_img, dst_img, mode="flow", skip_weights=True)[0]
         bwd = self.compute_flow(dst_img, src_img, mode="flow", skip_weights=True)[0]
@@ -486,7 +556,13 @@ class RAFTWrapper:
                      numpy_out=False, do_sigmoid=False, borrow=False, defer_weights=False, weight_region=False,
                      src_is_previous_dst=False, visibility=False, flow_init=None, iters=None, flow_region=False,
                      keep_flow=False, skip_weights=False):
-        """src_img / dst_img: (H, W, 3) uint8 BGR (numpy, or CUDA tensors already on the device).
+        """src_img / dst_img: (H, W, 3) uint8 BGR (numpy, or CUDA tensors already on the device), or -- either or both -- the
+        FrameFeatures that encode_frame() made of such an image: the flow then has the bits of the flow from the image, without
+        the encoder passes over it.  A record must be this provider's and of the other operand's padded geometry, and cannot be
+        combined with src_img_identifier (ValueError each).  A record as src is a non-pinned source: weight_region, defer_weights
+        and flow_region are honoured or ignored exactly as for any non-pinned source image (flow_region and a pinned weight
+        region: ignored; defer_weights with weight_region: honoured); src_is_previous_dst is ignored with it.  The pinned image as
+        src with a record as dst keeps the pinned fast path and all three.
         mode 'TC' -> (src_coords (2,HW) int64, dst_coords (2,HW) f32, weights (1,HW) f32 | None)
         mode 'flow' -> (flow (2,H,W), weights (1,H,W) | None).
         raft_type 'weighted_masked' (raft.py:181,216): one more value, the visibility-mask logits -- (1,H,W) in mode 'flow',
@@ -521,6 +597,18 @@ class RAFTWrapper:
         if visibility and not self.masked:
             raise ValueError("compute_flow(visibility=True) needs raft_type 'weighted_masked': no other type has a mask output")
         assert mode in ["flow", "TC"]
+        src_rec = src_img if isinstance(src_img, FrameFeatures) else None
+        dst_rec = dst_img if isinstance(dst_img, FrameFeatures) else None
+        if src_rec is not None or dst_rec is not None:
+            for rec in (src_rec, dst_rec):
+                if rec is not None and rec.provider is not self:
+                    raise ValueError("compute_flow: a FrameFeatures record of another provider (its encoders made other features)")
+            if src_img_identifier is not None:
+                raise ValueError("compute_flow: src_img_identifier (the flow cache) cannot be combined with a FrameFeatures record")
+            gs, gd = self._operand_geometry(src_img), self._operand_geometry(dst_img)
+            if gs != gd:
+                raise ValueError(f"compute_flow: the operands have different padded geometries (hp, wp, top, left, H, W): src {gs}, "
+                                 f"dst {gd} -- a FrameFeatures record serves only the geometry it was encoded at")
         assert src_img.shape == dst_img.shape
         self._flow_map = None
         if src_img_identifier is not None and self.masked:
@@ -554,20 +642,15 @@ class RAFTWrapper:
         self._touch_plan((hp, wp) if slot == 0 else (hp, wp, slot), (oh, ow), plan.P, pinned_here)
         start_time = timer()
 
-        def up(a):
-            if isinstance(a, torch.Tensor):
-                t = a if a.is_cuda else a.cuda(non_blocking=True)
-            else:
-                t = torch.from_numpy(np.ascontiguousarray(a)).cuda(non_blocking=True)
-            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
-                raise TypeError(f"compute_flow takes (H, W, 3) uint8 BGR images, got {tuple(t.shape)} {t.dtype}")
-            if (lh, lw) != (H, W):
-                t = t[:lh, :lw].contiguous()
-            return t.contiguous()
-
+        up = lambda a: self._upload(a, H, W, lh, lw)
         key = (hp, wp, top, left)
         if pinned_here and self._pinned_key == key and plan.source_tag is self:
             pass                                           # fmap1 / net / inp still resident in the plan
+        elif src_rec is not None:                          # the source state of an encode_source() of the record's image
+            plan.restore_source(src_rec.record)
+            self.source_features_reused = False
+            if slot == 0:
+                self._pinned_key = None
         else:
             s = up(src_img)
             plan.load_image(0, s, top, left)
@@ -595,9 +678,13 @@ class RAFTWrapper:
         if flow_region and self.flow_region_on and pinned_here and not post and flow_init is None and not self.masked:
             frect = self._flow_region(key, hp, wp, top, left, oh, ow)
         plan.set_flow_region(frect, n_iters)
-        d = up(dst_img)
-        plan.load_image(1, d, top, left)
-        self._last_dst[id(plan)] = (id(dst_img), key)         # (what this buffer set's target features will belong to after this call)
+        if dst_rec is not None:
+            plan.restore_target(dst_rec.record)
+            self._last_dst.pop(id(plan), None)             # (img[1] is not this target: nothing for src_is_previous_dst to reuse)
+        else:
+            d = up(dst_img)
+            plan.load_image(1, d, top, left)
+            self._last_dst[id(plan)] = (id(dst_img), key)     # (what this buffer set's target features will belong to after this call)
         o = self._outputs(oh, ow)
         weighted = self.C.raft_type in ("weighted", "weighted_masked") and not skip_weights
         # (defer_weights = the number of pixels the caller will name: worth it only if their 3x3 supports cannot cover most
@@ -613,7 +700,7 @@ class RAFTWrapper:
         self._run_flow(plan, n_iters, (top, left), oh, ow, o, weighted, bool(do_sigmoid) and not post,
                        defer_wh=self.weights_deferred, want_flow=(mode == "flow" or bool(keep_flow)),
                        mask_sigmoid=bool(visibility), has_init=flow_init is not None,
-                       skip_wh=bool(skip_weights) and not self.masked)
+                       skip_wh=bool(skip_weights) and not self.masked, target_restored=dst_rec is not None)
         self._flow_map = o["flow"] if (mode == "flow" or keep_flow) else None
         self._low_plan, self.last_flow_key = plan, (slot,) + key
         if self.weights_deferred:

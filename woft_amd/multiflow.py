@@ -96,10 +96,17 @@ class MultiFlowTracker:
     deltas:   the candidates of a frame, in fold order (ties go to the earlier one): None = the direct flow template -> t, an
               int d = the stored result of frame t - d chained with the flow (t - d) -> t.  Non-empty, unique, at most 8 entries,
               each int in [1, 127].
-    iters:    the refinement iterations of every flow (None: the flow config's)."""
+    iters:    the refinement iterations of every flow (None: the flow config's).
+    share_features: encode every frame once (provider.encode_frame) and run its flows from the record -- as the target of the
+              K flows of its own frame, and as the source of the chained flows of later frames -- instead of from the image:
+              one fnet and one cnet pass per frame, where the default runs K fnet passes over the frame and an fnet and a cnet
+              pass per chained flow over a stored one.  The results are bit-identical.  The records are kept beside the ring in
+              `_records` and dropped with their ring entries: 4 * P * (fdim + hdim + cdim) bytes per stored frame on top of
+              the frame and its result, P = (padded height / 8) * (padded width / 8) -- 66.4 MB at 1080p on the full model, 2.1 GB
+              for the 32 frames the default deltas keep.  The template's direct flow keeps the pinned source.  Default off."""
     DEVICE = "cuda"
 
-    def __init__(self, provider, deltas=(None, 1, 2, 4, 8, 16, 32), vis_thr=0.5, unit_cost=1.0, iters=None):
+    def __init__(self, provider, deltas=(None, 1, 2, 4, 8, 16, 32), vis_thr=0.5, unit_cost=1.0, iters=None, share_features=False):
         try:
             deltas = tuple(deltas)
         except TypeError:
@@ -118,6 +125,10 @@ class MultiFlowTracker:
         if getattr(getattr(provider, "C", None), "weights_postprocessing_fn", None):
             raise NotImplementedError("MultiFlowTracker: the chain cost is defined on the raw reliability logit; a flow config "
                                       "with a weights_postprocessing_fn is not supported")
+        self.share_features = bool(share_features)
+        if self.share_features and not hasattr(provider, "encode_frame"):
+            raise NotImplementedError("MultiFlowTracker(share_features=True) needs a flow provider with encode_frame() and "
+                                      f"compute_flow() on its records; {type(provider).__name__} has no encode_frame")
         self.provider, self.deltas, self.iters = provider, deltas, None if iters is None else int(iters)
         self.reach = max([d for d in deltas if d is not None], default=0)     # how far back a stored frame can still be needed
         self._fold = ops.flow_chain_fold
@@ -126,6 +137,7 @@ class MultiFlowTracker:
     def reset(self):
         """Forget the template and every stored frame."""
         self._template, self._ring, self.frame_index = None, {}, None
+        self._records = {}                                  # share_features: frame index -> its FrameFeatures, beside _ring
 
     def _upload(self, frame):
         """-> an (H, W, 3) uint8 tensor of the tracker's own on the device (never a view of the caller's or the provider's)."""
@@ -145,6 +157,8 @@ class MultiFlowTracker:
             h, w = self._out_size(self._template)
             z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.DEVICE)
             self._ring[0] = (self._template, (z(2, h, w), z(h, w), torch.ones(h, w, dtype=torch.float32, device=self.DEVICE)))
+            if self.share_features:                         # (a chained flow from frame 0 starts from its record, like any other)
+                self._records[0] = self.provider.encode_frame(self._template)
 
     def _out_size(self, img):
         """(H, W) of the provider's flow maps for this frame size (padding_mode 'crop' trims the frame to multiples of 8)."""
@@ -174,9 +188,14 @@ class MultiFlowTracker:
         img = self._upload(frame)
         extra = {} if self.iters is None else dict(iters=self.iters)
         best = None
-        for k, s, chained in self.schedule(t):
+        sched = self.schedule(t)
+        # share_features: the frame is encoded once, here (even where a single flow reads it: its record is a later frame's source)
+        rec = self.provider.encode_frame(img) if self.share_features and (sched or self.reach) else None
+        for k, s, chained in sched:
             src, prev = self._ring[s] if chained else (self._template, None)
-            out = self.provider.compute_flow(src, img, mode="flow", do_sigmoid=False, borrow=True, **extra)
+            if rec is not None and chained:
+                src = self._records[s]
+            out = self.provider.compute_flow(src, img if rec is None else rec, mode="flow", do_sigmoid=False, borrow=True, **extra)
             flow, wl, ml = out[0], out[1], (out[2] if len(out) > 2 else None)
             # (the borrowed buffers are consumed here, before the next flow overwrites them)
             best = self._fold(best, prev, flow, wl, ml, k=k, vis_thr=self.vis_thr, unit_cost=self.unit_cost, first=best is None)
@@ -187,7 +206,10 @@ class MultiFlowTracker:
         self.frame_index = t
         if self.reach:
             self._ring[t] = (img, (bf, bc, bv))
+            if rec is not None:
+                self._records[t] = rec
             for old in [i for i in self._ring if i < t + 1 - self.reach]:      # (frame t + 1 reaches back to t + 1 - reach)
                 del self._ring[old]
+                self._records.pop(old, None)
         return SimpleNamespace(flow=bf.clone(), cost=bc.reshape(1, h, w).clone(), vis=bv.reshape(1, h, w).clone(),
                                occluded=(bv < self.vis_thr).reshape(1, h, w), sel=bs.reshape(1, h, w), frame_index=t)

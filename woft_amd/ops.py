@@ -478,6 +478,33 @@ def split_bf16_lines(x, out):
     check(_lib.load().woft_split_bf16_lines(ptr(x), x.numel(), ptr(out), stream_ptr()), "woft_split_bf16_lines")
 
 
+def features_record_floats(n_pix, fdim, hdim, cdim):
+    """Floats of a frame-features record: [n_pix x fdim | n_pix x hdim | n_pix x cdim] (woft_features_pack)."""
+    return n_pix * (fdim + hdim + cdim)
+
+
+def features_pack(f1rows, net, xbuf, n_pix, dims, record):
+    """The first n_pix rows of f1rows (fnet map), of net and of the first dims[2] channels of xbuf -> record, one launch
+    (woft_features_pack).  dims = (fdim, hdim, cdim); the tensors are 2-D fp32 with contiguous rows."""
+    fdim, hdim, cdim = dims
+    assert record.dtype == torch.float32 and record.is_contiguous() and record.numel() == features_record_floats(n_pix, *dims)
+    assert f1rows.shape[0] >= n_pix and net.shape[0] >= n_pix and xbuf.shape[0] >= n_pix
+    check(_lib.load().woft_features_pack(ptr(f1rows), f1rows.stride(0), ptr(net), net.stride(0), ptr(xbuf), xbuf.stride(0),
+                                         n_pix, fdim, hdim, cdim, ptr(record), stream_ptr()), "woft_features_pack")
+
+
+def features_unpack(record, n_pix, dims, fmap, fmap_split=None, net=None, xbuf=None, inp_c=None):
+    """record -> the first n_pix rows of fmap; with net, xbuf and inp_c (the source role) also those and, with fmap_split, the
+    fnet map's [hi | lo] lines -- one launch (woft_features_unpack).  Without them (the target role) fmap alone."""
+    fdim, hdim, cdim = dims
+    assert record.dtype == torch.float32 and record.is_contiguous() and record.numel() == features_record_floats(n_pix, *dims)
+    assert fmap.shape[0] >= n_pix and all(t is None or t.shape[0] >= n_pix for t in (fmap_split, net, xbuf, inp_c))
+    ld = lambda t: 0 if t is None else t.stride(0)
+    check(_lib.load().woft_features_unpack(ptr(record), n_pix, fdim, hdim, cdim, ptr(fmap), ld(fmap), ptr(fmap_split), ptr(net),
+                                           ld(net), ptr(xbuf), ld(xbuf), ptr(inp_c), ld(inp_c), stream_ptr()),
+          "woft_features_unpack")
+
+
 def corr_gemm_bf16(a, b, m, n, alpha, out, terms):
     """out[:m, :n] = alpha * A B^T on pre-split bf16 operands (rows padded to 128); see woft_corr_gemm_bf16.
     out: float32, or bfloat16 for the bf16-storage volume."""

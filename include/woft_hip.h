@@ -26,7 +26,8 @@ extern "C" {
 
 /* ABI / build identification: returns 10000*major + 100*minor + patch. */
 int woft_abi_version(void);
-/* sizeof(woft_conv_params) (which = 0) / woft_lookup_params (1) / woft_lookup_otf_params (2): layout check for FFI mirrors. */
+/* sizeof(woft_conv_params) (which = 0) / woft_lookup_params (1) / woft_lookup_otf_params (2) / woft_lookup_band_params (3):
+   layout check for FFI mirrors. */
 int woft_sizeof(int which);
 /* developer knob for the micro-benchmarks in tools/ (ablation bits of the correlation GEMM, key 2); 0 in production. */
 int woft_set_tuning(int key, int value);
@@ -313,6 +314,38 @@ typedef struct woft_lookup_otf_params {
     int32_t smp_y0, smp_x0, smp_h, smp_w;
 } woft_lookup_otf_params;
 int woft_corr_lookup_otf(const woft_lookup_otf_params* p, void* stream);
+/* Correlation band: the correlations of the volume-free lookup around the identity, computed once per flow.
+ * For source pixel p = (x, y) (row y * wf + x) and level l the band holds alpha * <f1[p], f2_l[q]> for the cells
+ *     q = (floor(x / 2^l) - radius - m_l + bx,  floor(y / 2^l) - radius - m_l + by),   0 <= bx, by < W_l = 2 (radius + 1 + m_l),
+ * i.e. every cell of every (2 radius + 2)^2 window whose centre cell floor(coords / 2^l) lies within +-m_l cells of
+ * floor(p / 2^l); cells outside the level's map hold 0 (the lookup's zero padding).  m_0 = WOFT_BAND_M0 and
+ * m_l = ceil(m_0 / 2^l): a centre within [-m_0, m_0) cells of p at level 0 stays within +-m_l of floor(p / 2^l) at level l
+ * (floor((x + d) / 2^l) - floor(x / 2^l) lies in [-ceil(m_0 / 2^l), ceil(m_0 / 2^l)] for -m_0 <= d < m_0).
+ * Layout (floats): band[(pixel * rows + row_off_l + bx) * WOFT_BAND_LD + by], row_off_l = W_0 + ... + W_(l-1), rows = the sum
+ * over all levels: x-major rows of 64 bytes, entries by >= W_l are zero.  radius <= 4 (W_0 <= WOFT_BAND_LD).
+ * radius 4, 4 levels: W = 16, 14, 12, 12 -> 54 rows = 3456 bytes per source pixel. */
+#define WOFT_BAND_M0 3
+#define WOFT_BAND_LD 16
+#define WOFT_BAND_M(l) ((WOFT_BAND_M0 + (1 << (l)) - 1) >> (l))
+#define WOFT_BAND_W(radius, l) (2 * ((radius) + 1 + WOFT_BAND_M(l)))
+/* m[l], w[l], row_off[l] of `levels` levels (each may be NULL) -> rows per source pixel, or WOFT_EINVAL. */
+int woft_corr_band_geometry(int32_t radius, int32_t levels, int32_t* m, int32_t* w, int32_t* row_off);
+typedef struct woft_lookup_band_params {
+    woft_lookup_otf_params otf; /* as for woft_corr_lookup_otf (terms 1 or 3; ablate = 0)                          */
+    float* band;                /* [hf*wf][rows][WOFT_BAND_LD]                                                     */
+    int32_t* miss;              /* [hf*wf]: 1 where the pixel's 8 x 8 block was launched and missed the band, else 0 */
+    int32_t* miss_count;        /* [1]: + 1 per missed block                                                      */
+} woft_lookup_band_params;
+/* Fills the band from otf.f1 / otf.f2 (every value bit-identical to woft_corr_gemm_bf16's for that pair: the volume-free
+ * lookup's chunk loop on the band's bounding boxes); reads no coordinates, ignores need / fh_* / roi_* / smp_* / out. */
+int woft_corr_band_build(const woft_lookup_band_params* p, void* stream);
+/* The volume-free lookup with the correlations read from the band.  Prologue (need, roi_*, smp_*, folded flow-head gather)
+ * as woft_corr_lookup_otf, same operations in the same order.  An 8 x 8 block HITS when for every pixel of it inside the map
+ * and every level both coordinates of floor(coords / 2^l) lie within +-m_l of floor(p / 2^l): its samples are interpolated
+ * from the band (woft_corr_lookup's arithmetic) and its miss flags cleared.  Otherwise no sample is written, its flags are
+ * set and *miss_count grows by one: woft_corr_lookup_otf with need = miss, fh_part = NULL and the same rectangles then
+ * computes exactly the missed blocks.  Blocks skipped by need or smp_* are flagged 0. */
+int woft_corr_lookup_band(const woft_lookup_band_params* p, void* stream);
 /* NHWC map [h][w][c] -> its rows in 4x4-tile order [(ceil(h/4)*ceil(w/4)*16)][c], zero rows outside
  * the map: the B operand of the correlation GEMM that yields the tiled volume layout above. */
 int woft_tile_rows(const float* in, int32_t h, int32_t w, int32_t c, float* out, void* stream);

@@ -1,4 +1,7 @@
-"""Micro-benchmark of the volume-free lookup (woft_corr_lookup_otf) at 1080p feature size, smooth random flow."""
+"""Micro-benchmark of the volume-free lookup (woft_corr_lookup_otf) at 1080p feature size, smooth random flow.
+BAND=1: the correlation band instead -- its build, the band lookup and the fallback launch (the volume-free lookup on the miss
+flags), isolated, on the smooth field (residual flow 0.3 cells), and on fields scattered by +-3 px and +-8 px per pixel, with the
+blocks that missed; the plain volume-free lookup on the same field beside them."""
 import os
 import sys
 from pathlib import Path
@@ -33,6 +36,8 @@ def main():
     noise = (torch.rand(P, 2, device="cuda") * 2 - 1) * (flow if os.environ.get("SMOOTH", "1") == "0" else 0.3)
     coords = (base + flow + noise).contiguous()
     out = torch.zeros(P, 352, device="cuda")
+    if os.environ.get("BAND", "0") == "1":
+        return band(f1s, f2s, dims, hf, wf, c, base, out)
     lp = ops.make_lookup_otf_params(f1s, f2s, dims, hf, wf, c, coords, out, 4, 3)
     lp.ablate = int(os.environ.get("OTF_ABL", "0"))     # developer instances (csrc/lookup_otf.hip: 1, 2, 3, 8, 15, 16 = phase stamps, 64 = stamps in one chunk)
     ms = bench(lambda: ops.run_lookup_otf(lp), reps=20)
@@ -57,6 +62,36 @@ def main():
         for g in range(4):
             print(f"  group {g}: " + ", ".join(f"{n} {int(np.median(d[:, 5 * g + k]))}" for k, n in enumerate(names)))
         print(f"  chunk total (median cycles): {int(np.median((rows[:, 20] - rows[:, 0]) & 0xffffffff))}  ({len(rows)} workgroups)")
+
+
+def band(f1s, f2s, dims, hf, wf, c, base, out):
+    P = hf * wf
+    rows = ops.band_geometry(4, 4)[3]
+    buf = torch.zeros(P * rows * ops.BAND_LD, device="cuda")
+    miss, count = torch.zeros(P, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    g = torch.Generator(device="cuda").manual_seed(1)
+    rnd = lambda: torch.rand(P, 2, device="cuda", generator=g) * 2 - 1
+    fields = [("smooth 0.3 cells", base + 0.3 * rnd()), ("scattered +-3 px", base + 3.0 / 8 * rnd()),
+              ("scattered +-8 px", base + 8.0 / 8 * rnd()), ("scattered +-32 px", base + 32.0 / 8 * rnd())]
+    first = True
+    for name, coords in fields:
+        coords = coords.contiguous()
+        lp = ops.make_lookup_otf_params(f1s, f2s, dims, hf, wf, c, coords, out, 4, 3)
+        bp = ops.make_lookup_band_params(lp, buf, miss, count)
+        fb = ops.copy_params(lp)
+        fb.need = miss.data_ptr()
+        if first:
+            print(f"band build {hf}x{wf} ({buf.numel() * 4 / 2**20:.0f} MiB): {bench(lambda: ops.run_band_build(bp), reps=20) * 1e3:8.1f} us")
+            first = False
+        count.zero_()
+        ops.run_lookup_band(bp)
+        n_miss = int(count.item())
+        t_band = bench(lambda: ops.run_lookup_band(bp), reps=20)
+        t_fb = bench(lambda: ops.run_lookup_otf(fb), reps=20)
+        t_both = bench(lambda: (ops.run_lookup_band(bp), ops.run_lookup_otf(fb)), reps=20)
+        t_otf = bench(lambda: ops.run_lookup_otf(lp), reps=20)
+        print(f"{name:18s}: missed blocks {n_miss:4d} of {((hf + 7) // 8) * ((wf + 7) // 8)} | band lookup {t_band * 1e3:7.1f} us, fallback "
+              f"{t_fb * 1e3:7.1f} us, both {t_both * 1e3:7.1f} us | volume-free lookup {t_otf * 1e3:7.1f} us")
 
 
 if __name__ == "__main__":

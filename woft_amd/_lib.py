@@ -56,6 +56,12 @@ class LookupOtfParams(C.Structure):
     ]
 
 
+class LookupBandParams(C.Structure):
+    # woft_lookup_band_params: the embedded woft_lookup_otf_params spelled out field by field (the same layout; a flat mirror
+    # keeps every field a scalar, a pointer or an array of them)
+    _fields_ = LookupOtfParams._fields_ + [("band", vp), ("miss", vp), ("miss_count", vp)]
+
+
 _SIGS = {
     "woft_abi_version": (i32, []),
     "woft_sizeof": (i32, [i32]),
@@ -67,6 +73,9 @@ _SIGS = {
     "woft_split_bf16_lines": (i32, [vp, i64, vp, vp]),
     "woft_flow_to_tc": (i32, [vp, vp, i32, i32, vp, vp, i32, vp]),
     "woft_corr_lookup_otf": (i32, [C.POINTER(LookupOtfParams), vp]),
+    "woft_corr_band_geometry": (i32, [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "woft_corr_band_build": (i32, [C.POINTER(LookupBandParams), vp]),
+    "woft_corr_lookup_band": (i32, [C.POINTER(LookupBandParams), vp]),
     "woft_conv3x3_narrow": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i64, i32, vp]),
     "woft_flow_head_update": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     "woft_flow_head_gather": (i32, [vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, i32, vp]),
@@ -148,7 +157,7 @@ def load():
         fn = getattr(lib, name)           # AttributeError if a declared symbol is not exported
         fn.restype, fn.argtypes = res, args
     if lib.woft_sizeof(0) != C.sizeof(ConvParams) or lib.woft_sizeof(1) != C.sizeof(LookupParams) \
-            or lib.woft_sizeof(2) != C.sizeof(LookupOtfParams):
+            or lib.woft_sizeof(2) != C.sizeof(LookupOtfParams) or lib.woft_sizeof(3) != C.sizeof(LookupBandParams):
         raise WoftHipError("ctypes mirror of woft_conv_params / woft_lookup_params is out of sync with the library")
     _lib = lib
     return lib

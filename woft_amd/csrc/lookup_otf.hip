@@ -48,6 +48,7 @@
 
 #include "common.h"
 #include "dma.h"
+#include "lookup_blocks.h"
 
 namespace {
 
@@ -85,17 +86,11 @@ __device__ __forceinline__ void lds_dma16x2(const void* gbase, uint32_t o0_plus_
                  : "memory", "vcc");
 }
 
-// 8 x 8 blocks of a launch: first block and block counts per axis
-struct BlockRect {
-    int by0, bx0, ny, nx;
-};
-__host__ __device__ __forceinline__ BlockRect block_rect(const woft_lookup_otf_params& p) {
-    if ((p.roi_y0 | p.roi_x0 | p.roi_h | p.roi_w) == 0) return BlockRect{0, 0, (p.hf + 7) / 8, (p.wf + 7) / 8};
-    const int by0 = p.roi_y0 / 8, bx0 = p.roi_x0 / 8;
-    return BlockRect{by0, bx0, (p.roi_y0 + p.roi_h - 1) / 8 - by0 + 1, (p.roi_x0 + p.roi_w - 1) / 8 - bx0 + 1};
-}
-
-template <int TERMS, int R, int K, int ABL>
+// BAND (woft_corr_band_build): the same chunk loop on the bounding box of the block's BANDS instead of its lookup windows.  A
+// pixel's "window" of level l is its band, W_l x W_l cells at the fixed origin floor(p / 2^l) - R - m_l (no coordinates are
+// read), held in LDS in rows of WOFT_BAND_LD floats (64 KB of windows: one workgroup per CU); when the box is done the bands
+// are copied to p.out (the band buffer) in their memory layout instead of being sampled.  Values: this kernel's own, bit for bit.
+template <int TERMS, int R, int K, int ABL, bool BAND = false>
 __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_lookup_otf_params p) {
     constexpr int NPX = 64, NT = 256;
     constexpr int NW = 2 * R + 1, N2 = NW * NW;
@@ -106,7 +101,8 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
     constexpr int GS = 2, NGRP = 3, NST = GS * NGRP, DEPTH = NGRP - 1;
     static_assert(NK % GS == 0, "K steps per chunk must be a multiple of the steps per barrier");
     __shared__ __attribute__((aligned(16))) __bf16 stage[NST * 64 * 64];    // NST stages of 64 B rows, 128 B each
-    constexpr int WS = NW + 1, WLD = WS * WS + 2;       // a window: WS x WS cells, x-major (cell (cx, cy) at cx * WS + cy); even stride
+    // a window: WS x WS cells, x-major (cell (cx, cy) at cx * WST + cy); even stride
+    constexpr int WS = NW + 1, WST = BAND ? WOFT_BAND_LD : WS, WLD = BAND ? WOFT_BAND_LD * WOFT_BAND_LD + 4 : WS * WS + 2;
     __shared__ __attribute__((aligned(16))) float Wn[NPX * WLD];
     constexpr int MAXL = 4;
     __shared__ __attribute__((aligned(16))) int s_org[MAXL][NPX];    // window origin per level, clamped to 16 bits and packed (x | y << 16)
@@ -136,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
     // folded flow-head gather of their pixels
     const bool sampled = (p.smp_y0 | p.smp_x0 | p.smp_h | p.smp_w) == 0 ||
                          (py0 < p.smp_y0 + p.smp_h && py0 + 8 > p.smp_y0 && px0 < p.smp_x0 + p.smp_w && px0 + 8 > p.smp_x0);
-    if (p.need != nullptr) {      // nobody wants this block's samples (the weight head on a subset of the source pixels)
+    if (!BAND && p.need != nullptr) {      // nobody wants this block's samples (the weight head on a subset of the source pixels)
         int any = 0;
         if (tid < NPX) {
             const int y = py0 + (tid >> 3), x = px0 + (tid & 7);
@@ -146,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
     }
     // lookup centre of source pixel `tid` (wave 0), read once: requested BEFORE the A fragments (loads return in order)
     float cx = 0.f, cy = 0.f;
-    if (tid < NPX) {
+    if (!BAND && tid < NPX) {
         const int y = py0 + (tid >> 3), x = px0 + (tid & 7);
         if (y < p.hf && x < p.wf) {
             const int64_t i = (int64_t)y * p.wf + x;
@@ -187,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
             }
         }
     }
-    if (!sampled) return;                                // (block-uniform, before the first barrier)
+    if (!BAND && !sampled) return;                                // (block-uniform, before the first barrier)
     if (tid < NPX) {
         const int y = py0 + (tid >> 3), x = px0 + (tid & 7);
         // window origins, interpolation weights, drop-test operands and bounding boxes of ALL levels, while the other waves fetch
@@ -198,7 +194,10 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
             if (l < p.levels) {
                 int wx0 = 0, wy0 = 0;
                 float fx = 0.f, fy = 0.f;
-                if (cvalid) {
+                if (BAND) {                              // the band's origin: fixed by the pixel alone
+                    wx0 = (x >> l) - R - WOFT_BAND_M(l);
+                    wy0 = (y >> l) - R - WOFT_BAND_M(l);
+                } else if (cvalid) {
                     const float sc = 1.0f / (float)(1 << l);
                     const float xs = cx * sc, ys = cy * sc;
                     float flx = floorf(xs), fly = floorf(ys);
@@ -215,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
                 const int ox = wx0 < -16384 ? -16384 : (wx0 > 16384 ? 16384 : wx0);
                 const int oy = wy0 < -16384 ? -16384 : (wy0 > 16384 ? 16384 : wy0);
                 s_org[l][tid] = cvalid ? ((ox & 0xffff) | (oy << 16)) : 0x40004000;      // (pixels outside the grid: never inside)
-                s_pm[l][tid] = 4 * (tid * WLD - (ox * WS + oy));     // (BYTE offset: the drop adds its position's once per chunk)
+                s_pm[l][tid] = 4 * (tid * WLD - (ox * WST + oy));     // (BYTE offset: the drop adds its position's once per chunk)
                 const int b0 = wave_reduce_minmax<false>(cvalid ? wx0 : 0x3fffffff), b1 = wave_reduce_minmax<true>(cvalid ? wx0 : -0x3fffffff);
                 const int b2 = wave_reduce_minmax<false>(cvalid ? wy0 : 0x3fffffff), b3 = wave_reduce_minmax<true>(cvalid ? wy0 : -0x3fffffff);
                 if (tid == 0) { s_box[l][0] = b0; s_box[l][1] = b1; s_box[l][2] = b2; s_box[l][3] = b3; }
@@ -285,15 +284,16 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
     // the first rows arrive while the workgroup is busy with that
     auto start_level = [&](int l) __attribute__((always_inline)) {
         W = sel4(l, p.w[0], p.w[1], p.w[2], p.w[3]);
+        const int NWL = BAND ? WOFT_BAND_W(R, l) - 1 : NW;   // a window spans NWL + 1 cells
         const int H = sel4(l, p.h[0], p.h[1], p.h[2], p.h[3]);
         bx0 = __builtin_amdgcn_readfirstlane(s_box[l][0]);
         by0 = __builtin_amdgcn_readfirstlane(s_box[l][2]);
         int bx1 = __builtin_amdgcn_readfirstlane(s_box[l][1]), by1 = __builtin_amdgcn_readfirstlane(s_box[l][3]);
-        clipped = bx0 < 0 || by0 < 0 || bx1 + NW > W - 1 || by1 + NW > H - 1;
+        clipped = bx0 < 0 || by0 < 0 || bx1 + NWL > W - 1 || by1 + NWL > H - 1;
         bx0 = bx0 > 0 ? bx0 : 0;
         by0 = by0 > 0 ? by0 : 0;
-        bx1 = (bx1 + NW < W - 1) ? bx1 + NW : W - 1;         // windows span wx0 .. wx0 + 2R + 1
-        by1 = (by1 + NW < H - 1) ? by1 + NW : H - 1;
+        bx1 = (bx1 + NWL < W - 1) ? bx1 + NWL : W - 1;       // windows span wx0 .. wx0 + 2R + 1
+        by1 = (by1 + NWL < H - 1) ? by1 + NWL : H - 1;
         bw = bx1 - bx0 + 1;
         const int bh = by1 - by0 + 1;
         N = (bw > 0 && bh > 0) ? bw * bh : 0;
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
                 const int tx = bx0 + bx, ty = by0 + by;  // target pixel of this column
                 // (a column past the box end takes a position no window contains: 32767 - origin >= 16383 in both halves)
                 const int d_pos = pos < N ? ((tx & 0xffff) | (ty << 16)) : 0x7fff7fff;
-                const uint32_t d_q4 = lds_addr_of(Wn) + 4u * (uint32_t)(tx * WS + ty);
+                const uint32_t d_q4 = lds_addr_of(Wn) + 4u * (uint32_t)(tx * WST + ty);
                 const uint32_t trash = lds_addr_of(s_trash) + 4u * (uint32_t)lane;
                 i32x4 org[4], pm[4];
 #pragma unroll
@@ -403,7 +403,8 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
                     org[g4] = *(const i32x4*)&s_org[l][wm * 32 + 4 * hh + 8 * g4];
                     pm[g4] = *(const i32x4*)&s_pm[l][wm * 32 + 4 * hh + 8 * g4];
                 }
-                const u16x2 lim = {(unsigned short)(WS - 1), (unsigned short)(WS - 1)};
+                const unsigned short lim1 = (unsigned short)(BAND ? WOFT_BAND_W(R, l) - 1 : WS - 1);
+                const u16x2 lim = {lim1, lim1};
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const u16x2 dd = __builtin_bit_cast(u16x2, d_pos) - __builtin_bit_cast(u16x2, (int)org[r >> 2][r & 3]);
@@ -422,7 +423,20 @@ __global__ __launch_bounds__(256, 2) void corr_lookup_otf_kernel(const woft_look
         __syncthreads();                                 // every wave's drops are in the windows; the ring is free
         if (l + 1 < p.levels) start_level(l + 1);
         // ---- bilinear samples from the pixel's own window: the arithmetic of corr_lookup_kernel, one window column per item ----
-        if (!(ABL & 8)) {
+        if constexpr (BAND) {
+            // ---- the bands of level l, in their memory layout: a row of 64 bytes as four 16-byte pieces (entries past W_l: zero) ----
+            const int wl = WOFT_BAND_W(R, l), roff = band_row_off(R, l), rows = band_row_off(R, p.levels);
+            for (int it = tid; it < NPX * WOFT_BAND_LD * 4; it += NT) {
+                const int pix = it >> 6, c = (it >> 2) & 15, q4 = it & 3;
+                const int gy = py0 + (pix >> 3), gx = px0 + (pix & 7);
+                if (c >= wl || gy >= p.hf || gx >= p.wf) continue;
+                f32x4 v = *(const f32x4*)(Wn + pix * WLD + c * WST + q4 * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (q4 * 4 + e >= wl) v[e] = 0.f;
+                *(f32x4*)(p.out + (((int64_t)gy * p.wf + gx) * rows + roff + c) * WOFT_BAND_LD + q4 * 4) = v;
+            }
+        } else if (!(ABL & 8)) {
             for (int it = tid; it < NPX * NW; it += NT) {
                 const int pix = it / NW, i = it - pix * NW;
                 const int gy = py0 + (pix >> 3), gx = px0 + (pix & 7);
@@ -497,5 +511,43 @@ extern "C" int woft_corr_lookup_otf(const woft_lookup_otf_params* pp, void* stre
     }
     else return WOFT_EINVAL;
 #undef OTF
+    return woft_launch_status();
+}
+
+extern "C" int woft_corr_band_geometry(int32_t radius, int32_t levels, int32_t* m, int32_t* w, int32_t* row_off) {
+    if (radius < 1 || levels < 1 || levels > 4 || WOFT_BAND_W(radius, 0) > WOFT_BAND_LD) return WOFT_EINVAL;
+    for (int l = 0; l < levels; ++l) {
+        if (m) m[l] = WOFT_BAND_M(l);
+        if (w) w[l] = WOFT_BAND_W(radius, l);
+        if (row_off) row_off[l] = band_row_off(radius, l);
+    }
+    return band_row_off(radius, levels);
+}
+
+extern "C" int woft_corr_band_build(const woft_lookup_band_params* bp, void* stream) {
+    if (!bp || !bp->band) return WOFT_EINVAL;
+    woft_lookup_otf_params p = bp->otf;
+    if (p.levels < 1 || p.levels > 4 || !p.f1 || p.hf <= 0 || p.wf <= 0 || p.ablate != 0) return WOFT_EINVAL;
+    if (p.terms != 1 && p.terms != 3) return WOFT_EINVAL;                                   // (exact fp32: no band)
+    if (!((p.k == 256 && p.radius == 4) || (p.k == 128 && p.radius == 3))) return WOFT_EINVAL;
+    const int64_t row_bytes = (int64_t)p.k * (p.terms == 1 ? 2 : 4);
+    if ((int64_t)p.hf * p.wf * row_bytes >= (1ll << 32)) return WOFT_EINVAL;
+    for (int l = 0; l < p.levels; ++l)
+        if (!p.f2[l] || p.h[l] <= 0 || p.w[l] <= 0 || p.h[l] > 16384 || p.w[l] > 16384 ||
+            (int64_t)p.h[l] * p.w[l] * row_bytes >= (1ll << 32) - 4096)
+            return WOFT_EINVAL;
+    p.out = bp->band;
+    p.coords = nullptr;
+    p.need = nullptr;
+    p.fh_part = nullptr;
+    p.roi_y0 = p.roi_x0 = p.roi_h = p.roi_w = 0;
+    p.smp_y0 = p.smp_x0 = p.smp_h = p.smp_w = 0;
+    hipStream_t s = (hipStream_t)stream;
+    const BlockRect br = block_rect(p);
+    dim3 grid((unsigned)(br.nx * br.ny));
+#define BANDK(T, RR, KK) woft_launch(0, corr_lookup_otf_kernel<T, RR, KK, 0, true>, grid, dim3(256), 0, s, p)
+    if (p.radius == 4) { if (p.terms == 3) BANDK(3, 4, 256); else BANDK(1, 4, 256); }
+    else               { if (p.terms == 3) BANDK(3, 3, 128); else BANDK(1, 3, 128); }
+#undef BANDK
     return woft_launch_status();
 }

@@ -44,6 +44,16 @@ PYRAMID_ONE_LAUNCH = os.environ.get("WOFT_PYRAMID", "1") != "0"    # target pyra
 # the flow-head gather of iteration k runs inside the lookup launch of iteration k + 1 (volume-free lookup; the last
 # iteration's as its own launch): one launch fewer per iteration, same operations in the same order (0: always its own launch)
 FOLD_GATHER = os.environ.get("WOFT_FOLD_GATHER", "1") != "0"
+# correlation band (include/woft_hip.h: woft_lookup_band_params): the correlations of the volume-free lookup
+# around the identity are computed once per flow (woft_corr_band_build) and every lookup samples from them
+# (woft_corr_lookup_band), the volume-free lookup itself computing the 8 x 8 blocks whose windows left the band.  Bit-identical
+# results.  RaftEngine(corr_band=): "auto" = flows of at least BAND_MIN_LOOKUPS lookups, True = every flow the band applies to,
+# False = none; WOFT_CORR_BAND=0 switches it off everywhere.
+CORR_BAND = os.environ.get("WOFT_CORR_BAND", "1") != "0"
+# lookups from which the once-per-flow build pays: build time / saving per lookup, rounded up -- 132.8 us / (69.4 - 30.6 us) = 3.4
+# -> 4 at 1080p (profiles/lookup_band_ab.txt) -- and never below 6: below that the gain is inside the run-to-run spread, and
+# short flows keep their launch programs
+BAND_MIN_LOOKUPS = 6
 
 
 def _ru(x, m):
@@ -145,7 +155,7 @@ class _Enc:
 
 class RaftEngine:
     def __init__(self, state_dict, small=False, weighted=True, precision="fp32", corr="volume", volume_storage=None,
-                 mask_head=False):
+                 mask_head=False, corr_band="auto"):
         """precision: "fp32" (exact fp32 MFMA), "bf16x3" (split-bf16, fp32-emulating), "bf16", or "fp16" = the reference's
         `mixed_precision` scoping (weighted_raft.py:204-219,233-234,258-290: autocast around fnet, cnet and the update block
         only): those convolutions on fp16 operands with fp32 accumulation, the correlation, the weight head and both
@@ -168,6 +178,9 @@ class RaftEngine:
         #  kernel, the correlation and the weight head run in bf16x3)
         self.prec_corr = self.prec_wh = "bf16x3" if precision in ("fp16", "f16mx8") else precision
         self.corr = corr
+        if corr_band not in ("auto", True, False):
+            raise ValueError("corr_band must be 'auto', True or False")
+        self.corr_band = corr_band
         self.volume_storage = volume_storage or ("bf16" if precision == "bf16" else "fp32")
         if self.volume_storage not in ("fp32", "bf16") or (self.volume_storage == "bf16" and precision == "fp32"):
             raise ValueError("volume_storage: 'fp32', or 'bf16' with the split-bf16 precisions (their GEMM packs it)")
@@ -335,6 +348,12 @@ class _Plan:
         self.wh_events = None      # bench hook: (start, end, windows) around the weight head's first 128->128 layer
         self.conv_events = None    # bench hook: {tag: [(start, end)]} for the tagged conv launches of the iteration program
         self._graphs = {}          # the flow provider's captured hipGraphs of this plan's flow(), by call signature
+        # correlation band: its buffers (first use), whether it holds the correlations of the current source / target operands,
+        # and the band variants of the lookup parameter structs (by the address of the volume-free struct they mirror)
+        self._band = None
+        self.band_valid = False
+        self._band_params = {}
+        self._graph_band = {}      # per captured graph: band_valid as that flow() leaves it (a replay does not run flow())
         # what only some plans have: the full model's upsampling mask, a merged last iteration, the folded programs, fh_part (flow
         # head folded into one conv launch: per-pixel partial products of its second conv), the two heads
         self.mk = self.mask = self.prog_iter_last = self.folded = self.fh_part = None
@@ -872,7 +891,63 @@ class _Plan:
                 raise ValueError(kind)
 
     def _lookup(self, params):
+        if self.band_valid:
+            _timed(self.lookup_events, self._lookup_band, params)
+            return
         _timed(self.lookup_events, ops.run_lookup_otf if self.otf else ops.run_lookup, params)
+
+    # ---- correlation band ------------------------------------------------------------------
+    def band_applies(self, lookups, flow_init=None):
+        """Whether a flow of `lookups` lookups (iterations, + 1 with a weight head) runs on the correlation band: volume-free
+        correlation in a split-bf16 mode, a (radius, k) the band kernels are built for, no warm start (the band is centred on
+        the identity), and -- corr_band = "auto" -- enough lookups for the build to pay."""
+        e, sp = self.eng, self.eng.spec
+        if not CORR_BAND or e.corr_band is False or not self.otf or self.prec == "fp32" or flow_init is not None:
+            return False
+        if (sp.radius, sp.fdim) not in ops.BAND_INSTANCES or sp.levels > 4:
+            return False
+        return e.corr_band is True or lookups >= BAND_MIN_LOOKUPS
+
+    def _band_buffers(self):
+        if self._band is None:
+            sp = self.eng.spec
+            rows = ops.band_geometry(sp.radius, sp.levels)[3]
+            i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")
+            self._band = (torch.zeros(self.P * rows * ops.BAND_LD, dtype=torch.float32, device="cuda"), i32(self.P), i32(1))
+        return self._band
+
+    def _band_build(self):
+        """The band of the current source and target operands (after the pyramid): one launch; resets the miss counter."""
+        band, miss, count = self._band_buffers()
+        count.zero_()
+        ops.run_band_build(self._band_variant(self.lookup))
+        self.band_valid = True
+
+    def _band_variant(self, params):
+        """The band lookup's struct for a volume-free lookup struct (kept per struct; its `need` is copied at every use), with the
+        fallback's: the same launch with need = the miss flags and no folded gather."""
+        key = id(params)
+        if key not in self._band_params:
+            band, miss, count = self._band_buffers()
+            fb = ops.copy_params(params)
+            fb.fh_part, fb.need = None, _lib.ptr(miss)
+            fb._keep = (getattr(params, "_keep", None), miss)
+            self._band_params[key] = (params, ops.make_lookup_band_params(params, band, miss, count), fb)
+        _, bp, fb = self._band_params[key]
+        bp.need = params.need
+        bp._fallback = fb
+        return bp
+
+    def _lookup_band(self, params):
+        """Band lookup, then the volume-free lookup on the blocks it flagged as missed (its other blocks return at once)."""
+        bp = self._band_variant(params)
+        ops.run_lookup_band(bp)
+        ops.run_lookup_otf(bp._fallback)
+
+    @property
+    def band_miss_blocks(self):
+        """8 x 8 blocks that missed the band since it was last built (reads the device counter: tools and tests only)."""
+        return 0 if self._band is None else int(self._band[2].item())
 
     def _split(self, rows, out):
         """fp32 rows -> the correlation GEMM's bf16 operand: [hi | lo] lines (bf16x3) or the bf16 plane (bf16)."""
@@ -892,6 +967,7 @@ class _Plan:
         the same launch program (bit-identical).  Volume-free correlation only (the volume mode keeps the target operand in
         4x4-tile order); -> whether the features were reused."""
         reused = bool(reuse_target) and self.otf and self.target_valid
+        self.band_valid = False
         if reused:
             self.f1rows[:self.P].copy_(self.f2act[0].t.view(self.P, -1))
             if self.prec != "fp32":
@@ -921,6 +997,7 @@ class _Plan:
         reuse book-keeping is reset (target_valid, source_tag) -- the derived source state (split operand, gate biases) is NOT
         brought up to date, restore_source() does that."""
         self.source_tag, self.target_valid = None, False
+        self.band_valid = False
         self.run(self.prog_f_src)
         self.run(self.prog_c_src)
         ops.features_pack(self.f1rows, self.net0.t, self.xbuf.t, self.P, self.record_dims, record)
@@ -932,6 +1009,7 @@ class _Plan:
         split where it is not fused, the gate-bias convs."""
         x3 = self.prec != "fp32" and self.prec_corr == "bf16x3"
         self.source_tag = None
+        self.band_valid = False
         ops.features_unpack(record, self.P, self.record_dims, self.f1rows, self.f1s if x3 else None, self.net0.t, self.xbuf.t,
                             self.inp_c.t)
         if self.prec != "fp32" and not x3:
@@ -943,6 +1021,7 @@ class _Plan:
         the pyramid / volumes from it (prog_volume starts from f2act[0] in every corr mode).  Until that flow has run the level-0
         operand is stale: target_valid is cleared, flow() sets it."""
         self.target_valid = False
+        self.band_valid = False
         ops.features_unpack(record, self.P, self.record_dims, self.f2act[0].t)
 
     def set_flow_init(self, flow_init):
@@ -977,10 +1056,13 @@ class _Plan:
         e, sp = self.eng, self.eng.spec
         if iters < 1:
             raise ValueError("iters must be >= 1")
+        self.band_valid = False
         if not target_restored:
             self.run(self.prog_f_dst)
         self.run(self.prog_volume)
         self.target_valid = True                             # (level-0 target map + operand now belong to the image in img[1])
+        if self.band_applies(iters + (1 if e.weighted and not skip_wh else 0), flow_init):
+            self._band_build()
         if flow_init is None:
             ops.coords_init(self.coords, self.hf, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
         else:

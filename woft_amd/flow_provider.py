@@ -175,8 +175,13 @@ class RAFTWrapper:
         # (exact fp32 included: the lookup's fp32-MFMA instantiation), "otf" is faster and needs no P x P buffer: the default.
         self.corr = os.environ.get("WOFT_CORR") or getattr(self.C, "corr", None) or "otf"
         # flow config key `volume_storage` ("fp32" | "bf16"): element type of the correlation volume (corr = "volume")
+        # flow config key `corr_band` ("auto" | True | False; env WOFT_CORR_BAND=0: off): the correlations around the identity
+        # computed once per flow, the lookups sampling from them (engine.py: CORR_BAND) -- "auto": flows long enough for it to pay
+        v = getattr(self.C, "corr_band", None)
+        self.corr_band = "auto" if (v is None or isinstance(v, type(self.C))) else (v if v == "auto" else bool(v))
         self.engine = RaftEngine(state_dict, small=small, weighted=weighted, precision=self.precision, corr=self.corr,
-                                 volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked)
+                                 volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked,
+                                 corr_band=self.corr_band)
         # training of the weight head (weight_head_parameters / weights_at / sync_weight_head): the head's tensors as loaded, the
         # Parameters made of them at the first request, and the plan + crop of the last COMPUTED flow (None: none, or a cache hit)
         self._wh_loaded = {k: v for k, v in state_dict.items() if k.startswith("weight_head.net.")}
@@ -255,8 +260,10 @@ class RAFTWrapper:
                 with torch.cuda.graph(g):
                     eager()
             plan._graphs[key] = g
+            plan._graph_band[key] = plan.band_valid
         else:
             g.replay()
+            plan.band_valid = plan._graph_band[key]          # (whether this flow rebuilt the correlation band for its operands)
 
     def finish_weights(self, pts, count, n_max, out=None):
         """After compute_flow(..., defer_weights=True) with `weights_deferred` set: evaluate the weight head for the

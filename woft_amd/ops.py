@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, conv_select
-from ._lib import ConvParams, LookupOtfParams, LookupParams, check, ptr, stream_ptr
+from ._lib import ConvParams, LookupBandParams, LookupOtfParams, LookupParams, check, ptr, stream_ptr
 from .conv_select import KERNELS, PRECISION, Kernel, pair_ok  # noqa: F401  (PRECISION, pair_ok: part of this module's interface)
 
 DEV = "cuda"
@@ -471,6 +471,53 @@ def make_lookup_otf_params(f1s, f2s, dims, hf, wf, k, coords, out, radius, terms
 
 def run_lookup_otf(p):
     check(_lib.load().woft_corr_lookup_otf(C.byref(p), stream_ptr()), "woft_corr_lookup_otf")
+
+
+# ---- correlation band (include/woft_hip.h: woft_lookup_band_params; mirrored here, checked against woft_corr_band_geometry) ----
+BAND_M0, BAND_LD = 3, 16
+BAND_INSTANCES = ((4, 256), (3, 128))        # (radius, k) pairs the band kernels are built for: the volume-free lookup's
+
+
+def band_m(l):
+    """m_l = ceil(m_0 / 2^l): how far floor(coords / 2^l) may lie from floor(p / 2^l), in cells, for a hit."""
+    return (BAND_M0 + (1 << l) - 1) >> l
+
+
+def band_geometry(radius, levels):
+    """-> (m, w, row_off, rows): per level the margin m_l, the band's width W_l = 2 (radius + 1 + m_l) and its first row; rows per
+    source pixel.  band[(pixel * rows + row_off[l] + bx) * BAND_LD + by] is the correlation of the pixel p = (x, y) with cell
+    (floor(x / 2^l) - radius - m_l + bx, floor(y / 2^l) - radius - m_l + by) of level l."""
+    m = [band_m(l) for l in range(levels)]
+    w = [2 * (radius + 1 + ml) for ml in m]
+    off = [sum(w[:l]) for l in range(levels)]
+    return m, w, off, sum(w)
+
+
+def band_hit(cx, cy, x, y, levels):
+    """The band lookup's per-pixel predicate (the kernel ANDs it over the valid pixels of an 8 x 8 block): floor(coords / 2^l)
+    within +-m_l of floor(p / 2^l) on both axes, at every level."""
+    for l in range(levels):
+        s = 1.0 / (1 << l)
+        if abs(math.floor(cx * s) - (x >> l)) > band_m(l) or abs(math.floor(cy * s) - (y >> l)) > band_m(l):
+            return False
+    return True
+
+
+def make_lookup_band_params(otf, band, miss, miss_count):
+    """woft_lookup_band_params around a copy of a volume-free lookup's struct (its need / fh_* / roi_* / smp_* included)."""
+    p = LookupBandParams()
+    C.memmove(C.byref(p), C.byref(otf), C.sizeof(LookupOtfParams))     # (the embedded struct comes first)
+    p.band, p.miss, p.miss_count = ptr(band), ptr(miss), ptr(miss_count)
+    p._keep = (getattr(otf, "_keep", None), band, miss, miss_count)
+    return p
+
+
+def run_band_build(p):
+    check(_lib.load().woft_corr_band_build(C.byref(p), stream_ptr()), "woft_corr_band_build")
+
+
+def run_lookup_band(p):
+    check(_lib.load().woft_corr_lookup_band(C.byref(p), stream_ptr()), "woft_corr_lookup_band")
 
 
 def split_bf16_lines(x, out):

@@ -171,7 +171,7 @@ def test_unpack_writes_only_the_named_maps_of_a_plan(small):
 
 
 # ---- 2. flows from records ------------------------------------------------------------------------------------------------------------
-def _config(raft_type="weighted", small=False, precision="bf16x3", corr="otf", iters=4, seed=7, graph=False):
+def _config(raft_type="weighted", small=False, precision="bf16x3", corr="otf", iters=4, seed=7, graph=False, corr_band=None):
     from woft_amd.config import Config
     from woft_amd.flow_provider import RAFTWrapper
     masked = raft_type == "weighted_masked"
@@ -190,6 +190,8 @@ def _config(raft_type="weighted", small=False, precision="bf16x3", corr="otf", i
     c.iters, c.padding_mode, c.precision, c.corr = iters, "RAFT", precision, corr
     if graph:
         c.graph = True
+    if corr_band is not None:
+        c.corr_band = corr_band
     return c
 
 
@@ -268,7 +270,7 @@ def test_graph_provider_alternating_images_and_records(pairs):
         assert same(prov.compute_flow(src, dst, mode="flow"), ref), k
     plan = prov.engine.plan(*SIZES[0])
     keys = [k for k, g in plan._graphs.items() if g is not None]
-    assert {k[-1] for k in keys} == {False, True}                     # a captured graph for the encoded and for the restored target
+    assert {k.target_restored for k in keys} == {False, True}         # a captured graph for the encoded and for the restored target
 
 
 # ---- 3. no stale state ----------------------------------------------------------------------------------------------------------------
@@ -331,6 +333,101 @@ def test_src_is_previous_dst_finds_nothing_stale_after_a_record_flow(pairs):
             prov.encode_frame(c)
         assert same(prov.compute_flow(b, c, mode="TC", src_is_previous_dst=True), ref), between
         assert not prov.source_features_reused, between
+
+
+def test_replayed_and_eager_calls_leave_the_same_state(pairs):
+    """A provider that replays hipGraphs and an eager one, driven through the same calls: after every call the same output bytes,
+    the same source_features_reused / weights_deferred, and in both buffer sets the same band_valid, target_valid and source
+    ownership -- a replay applies the state its flow() left.  3 iterations with corr_band=True: the band applies except under a
+    warm start."""
+    size = SIZES[0]
+    a, b, c = pairs[size]
+    eager, graph = _provider(iters=3, corr_band=True), _provider(iters=3, corr_band=True, graph=True)
+    assert graph.use_graph and not eager.use_graph
+    init = torch.randn(2, size[0] // 8, size[1] // 8, generator=torch.Generator().manual_seed(4)).cuda()
+    pts = torch.tensor([[5.0, 7.0], [100.0, 90.0], [159.0, 127.0], [0.0, 0.0]], device="cuda")
+    count = torch.tensor([4], dtype=torch.int32, device="cuda")
+    rec = {}
+
+    def encode(p):
+        rec[p] = p.encode_frame(c)
+        return rec[p].record
+
+    def deferred(p):
+        out = p.compute_flow(a, b, mode="TC", weight_region=True, defer_weights=4)
+        assert p.weights_deferred and out[2] is None
+        return out[:2] + (p.finish_weights(pts, count, 4, out=torch.zeros(4, device="cuda")),)
+
+    def sync(p):
+        p.weight_head_parameters()
+        p.sync_weight_head()
+
+    image = lambda p: p.compute_flow(a, b, mode="flow")
+    steps = [("image/image", image)] * 3                                  # (the third call with one key replays)
+    steps += [("sync_weight_head", sync)] + [("image/image after sync", image)] * 3        # (the graphs are dropped: captured again)
+    steps += [("encode_frame", encode), ("image/image after encode_frame", image),
+              ("src_is_previous_dst", lambda p: p.compute_flow(b, c, mode="TC", src_is_previous_dst=True)),
+              ("record target", lambda p: p.compute_flow(a, rec[p], mode="flow")),
+              ("record source", lambda p: p.compute_flow(rec[p], b, mode="flow"))]
+    steps += [("flow_init", lambda p: p.compute_flow(a, b, mode="flow", flow_init=init))] * 3
+    steps += [("deferred weights", deferred)] * 3
+    steps += [("pin_source", lambda p: p.pin_source(a))]
+    steps += [("pinned source", image), ("second buffer set", lambda p: p.compute_flow(b, c, mode="flow", skip_weights=True))] * 3
+    steps += [("pinned source, resident", lambda p: p.compute_flow(a, c, mode="TC"))]
+    for k, (name, call) in enumerate(steps):
+        got, want = call(graph), call(eager)
+        assert (got is None and want is None) or same(got, want), (k, name)
+        assert (graph.source_features_reused, graph.weights_deferred) == (eager.source_features_reused, eager.weights_deferred), (k, name)
+        for slot in (0, 1):
+            pg, pe = graph.engine.plan(*size, slot), eager.engine.plan(*size, slot)
+            state = lambda plan, p: (plan.band_valid, plan.target_valid, plan.source_tag is p)
+            assert state(pg, graph) == state(pe, eager), (k, name, slot)
+        if name == "src_is_previous_dst":                               # (the one intended change: True under a graph as it is eagerly)
+            assert eager.source_features_reused and graph.source_features_reused
+    captured = {key for slot in (0, 1) for key, g in graph.engine.plan(*size, slot)._graphs.items() if g is not None}
+    assert len(captured) >= 3 and not any(eager.engine.plan(*size, slot)._graphs for slot in (0, 1))
+
+
+def _reachable(root, found, seen):
+    """Every object reachable from `root` through dicts, sequences and the attributes of woft_amd's own objects -> found."""
+    if id(root) in seen or isinstance(root, (str, bytes, torch.Tensor, np.ndarray)):
+        return
+    seen.add(id(root))
+    found.append(root)
+    if isinstance(root, dict):
+        children = list(root.keys()) + list(root.values())
+    elif isinstance(root, (list, tuple, set, frozenset)):
+        children = list(root)
+    elif type(root).__module__.startswith("woft_amd") and hasattr(root, "__dict__"):
+        children = list(vars(root).values())
+    else:
+        return
+    for child in children:
+        _reachable(child, found, seen)
+
+
+def test_a_dropped_plan_leaves_nothing_behind():
+    """bound_plans(1) over three shapes and back to the first: whatever the provider holds outside its engine refers to no plan
+    the engine has dropped -- neither the plan nor its id() -- and every flow has the bytes of an unbounded provider's."""
+    from woft_amd.engine import _Plan
+    shapes = [(128, 160), (136, 200), (120, 152), (128, 160)]
+    prov, ref = _provider(iters=3), _provider(iters=3)
+    prov.bound_plans(1)
+    plans = []                                                          # (kept alive here, so that no id() is handed out twice)
+    for h, w in shapes:
+        big = synth.make_template(h + 32, w + 32, seq_id=9)
+        a, b, c = (np.ascontiguousarray(big[16 - t:16 - t + h, 16 + 2 * t:16 + 2 * t + w]) for t in (0, 1, 3))
+        got, want = ((p.compute_flow(a, b, mode="flow"), p.compute_flow(b, c, mode="TC", src_is_previous_dst=True)) for p in (prov, ref))
+        assert same(got[0], want[0]) and same(got[1], want[1]), (h, w)
+        assert prov.source_features_reused and ref.source_features_reused
+        plans.append(prov.engine.plan(h, w))
+    live = list(prov.engine._plans.values())
+    assert len(live) == 1 and live[0] is plans[3] and plans[3] is not plans[0] and len(ref.engine._plans) == 3
+    dropped = plans[:3]
+    held = []
+    _reachable({k: v for k, v in vars(prov).items() if k != "engine"}, held, set())
+    assert not [x for x in held if isinstance(x, _Plan) and x is not live[0]]
+    assert not [x for x in held if isinstance(x, int) and not isinstance(x, bool) and x in {id(p) for p in dropped}]
 
 
 # ---- 4. errors ------------------------------------------------------------------------------------------------------------------------

@@ -78,7 +78,7 @@ def test_flow_inside_the_mask_is_unchanged(scene, precision, graph):
     if graph:
         assert any(g is not None for g in plan._graphs.values()), "nothing was replayed"
         if got[6]:
-            assert any(k[-1] is not None and g is not None for k, g in plan._graphs.items()), "the restricted flow was not replayed"
+            assert any(k.flow_region is not None and g is not None for k, g in plan._graphs.items()), "the restricted flow was not replayed"
     for t in got[:6]:
         assert bool(torch.isfinite(t).all())
     assert torch.equal(got[0].reshape(2, -1)[:, sel], ref[0].reshape(2, -1)[:, sel])        # flow_up

@@ -20,6 +20,9 @@ when the caller pins the source image.
 Launch programs: lists of Step(kind, arg, tag) replayed by _Plan.run().  A refinement iteration has up to three (first / middle /
 merged last) and, with the flow-head gather folded into the next lookup, a second set (_Plan.folded): _Plan._iteration() alone
 picks among them.  The heads after the loop (prog_mask, prog_wh, prog_mh) are plain lists of conv parameter structs.
+
+A plan alone knows what its buffers hold (source_owner, target_owner, target_valid, band_valid: _source_changed / _target_changed)
+and owns the captured hipGraphs of its flow() (flow(graph=True), FlowKey); callers ask, they keep no copy of either.
 """
 import math
 import os
@@ -75,6 +78,31 @@ class _Folded(NamedTuple):
     prog_iter_last: list       # None where the plan has no merged last iteration
     gather: list
     lookup: object
+
+
+class FlowKey(NamedTuple):
+    """What makes two _Plan.flow() calls the same launches on the same addresses: the key of a plan's captured graphs."""
+    iters: int
+    crop: tuple
+    h: int
+    w: int
+    flow_up: int               # the outputs by address (None: not written)
+    dst: int
+    wout: int
+    mout: int
+    do_sigmoid: bool
+    mask_sigmoid: bool
+    defer_wh: bool
+    skip_wh: bool
+    has_init: bool             # a flow_init was given (its values are not part of the key: the graph reads the plan's buffer)
+    target_restored: bool
+    wh_region: int             # address of the weight region's window list (None: every source pixel)
+    flow_region: tuple         # (rectangle, iterations) of the restricted iterations that run (None: none)
+
+
+class _FlowGraph(torch.cuda.CUDAGraph):
+    """A captured _Plan.flow() + post: the (band_valid, target_valid) that flow leaves in the plan, which a replay must set."""
+    post = None
 
 
 def _timed(sink, launch, *args, extra=None):
@@ -286,8 +314,8 @@ class RaftEngine:
     def repack_weight_head(self, sd):
         """Re-pack the standard head from `sd` (its eight weight_head.net.* tensors) IN PLACE into every device buffer the
         inference path reads head parameters from -- the engine's packed layers and fragments, the closing conv's weights and
-        bias, and in every plan wh0_t, the bias tensor and the padded closing weights -- and drop every captured graph (a captured
-        launch bakes the closing bias in as an argument).  The next flow then has the bits of an engine built from `sd`."""
+        bias, and every plan's own copies (_Plan.refresh_weight_head, which also drops the plan's captured graphs).  The next flow
+        then has the bits of an engine built from `sd`."""
         assert self.weighted and self.wh_std
         sd = {k: v.detach().float().cpu() for k, v in sd.items() if k.startswith("weight_head.net.")}
         wh0, wh2, wh4, frag = self._wh_std_packed(sd)
@@ -298,11 +326,7 @@ class RaftEngine:
         self.wh6_w[:self.wh6_c].copy_(sd["weight_head.net.6.weight"].reshape(-1))
         self.wh6_b = float(sd["weight_head.net.6.bias"].item())
         for plan in self._plans.values():
-            plan.wh0_t.copy_(self.wh0.wgt[:128].t())
-            plan.wh6_b.fill_(self.wh6_b)
-            if plan._wh6_pad is not None:
-                plan._wh6_pad[:self.wh6_c].copy_(self.wh6_w[:self.wh6_c])
-            plan._graphs.clear()
+            plan.refresh_weight_head()
 
     def _pack_mask_head(self, sd):
         sp = self.spec
@@ -342,18 +366,19 @@ class _Plan:
         self.prec, self.prec_corr, self.prec_wh = eng.precision, eng.prec_corr, eng.prec_wh
         self.otf = eng.corr == "otf"
         self.hf, self.wf, self.P = hp // 8, wp // 8, (hp // 8) * (wp // 8)
-        self.source_tag = None
-        self.target_valid = False  # the level-0 target map + operand belong to the image in img[1] (set by flow())
+        # what the operand buffers hold (_source_changed / _target_changed): source_owner = the (tag, key) that claimed the source
+        # state at encode_source(); target_owner = the token the target image was loaded under; target_valid = the level-0 target
+        # map + operand are that image's (flow() sets it); band_valid = the band holds the current operands' correlations
+        self._source_changed()
+        self._target_changed()
         self.lookup_events = None  # bench hook: list collecting (start, end) HIP events per lookup launch
         self.wh_events = None      # bench hook: (start, end, windows) around the weight head's first 128->128 layer
         self.conv_events = None    # bench hook: {tag: [(start, end)]} for the tagged conv launches of the iteration program
-        self._graphs = {}          # the flow provider's captured hipGraphs of this plan's flow(), by call signature
-        # correlation band: its buffers (first use), whether it holds the correlations of the current source / target operands,
-        # and the band variants of the lookup parameter structs (by the address of the volume-free struct they mirror)
+        self._graphs = {}          # flow(graph=True): {FlowKey: its _FlowGraph, or None after the first sighting}
+        # correlation band: its buffers (first use) and the band variants of the lookup parameter structs (by the address of the
+        # volume-free struct they mirror)
         self._band = None
-        self.band_valid = False
         self._band_params = {}
-        self._graph_band = {}      # per captured graph: band_valid as that flow() leaves it (a replay does not run flow())
         # what only some plans have: the full model's upsampling mask, a merged last iteration, the folded programs, fh_part (flow
         # head folded into one conv launch: per-pixel partial products of its second conv), the two heads
         self.mk = self.mask = self.prog_iter_last = self.folded = self.fh_part = None
@@ -897,12 +922,12 @@ class _Plan:
         _timed(self.lookup_events, ops.run_lookup_otf if self.otf else ops.run_lookup, params)
 
     # ---- correlation band ------------------------------------------------------------------
-    def band_applies(self, lookups, flow_init=None):
+    def band_applies(self, lookups, has_init=False):
         """Whether a flow of `lookups` lookups (iterations, + 1 with a weight head) runs on the correlation band: volume-free
         correlation in a split-bf16 mode, a (radius, k) the band kernels are built for, no warm start (the band is centred on
         the identity), and -- corr_band = "auto" -- enough lookups for the build to pay."""
         e, sp = self.eng, self.eng.spec
-        if not CORR_BAND or e.corr_band is False or not self.otf or self.prec == "fp32" or flow_init is not None:
+        if not CORR_BAND or e.corr_band is False or not self.otf or self.prec == "fp32" or has_init:
             return False
         if (sp.radius, sp.fdim) not in ops.BAND_INSTANCES or sp.levels > 4:
             return False
@@ -956,18 +981,44 @@ class _Plan:
         else:
             ops.split_bf16(rows, out, None)
 
-    def load_image(self, slot, img_u8, pad_top, pad_left):
+    # ---- what the operand buffers hold ---------------------------------------------------------------
+    # (every method that overwrites operands says so through these two: nothing else writes the owners or clears band_valid)
+    def _source_changed(self, owner=None):
+        """img[0] / fmap1 and its correlation operand, net, inp, the gate biases are being overwritten: `owner`'s from now on."""
+        self.source_owner = owner
+        self._operands_changed()
+
+    def _target_changed(self, owner=None):
+        """img[1] / the target maps are being overwritten: the image is `owner`'s, the maps nobody's until flow() has run."""
+        self.target_owner, self.target_valid = owner, False
+        self._operands_changed()
+
+    def _operands_changed(self):
+        self.band_valid = False                              # (no band is the new operands')
+
+    @property
+    def source_tag(self):
+        return None if self.source_owner is None else self.source_owner[0]
+
+    def load_image(self, slot, img_u8, pad_top, pad_left, owner=None):
+        """img_u8 -> img[slot] (0: the source image, 1: the target image).  owner (target only): the caller's token for the
+        image -- after the flow() that encodes it, `target_valid and target_owner == owner` says the target features are its."""
+        if slot == 0:
+            self._source_changed()
+        else:
+            self._target_changed(owner)
         ops.preprocess(img_u8, self.img[slot], self.hp, self.wp, pad_top, pad_left)
 
-    def encode_source(self, reuse_target=False):
-        """fmap1, net, inp of the source image in img[0] (cacheable across frames).
+    def encode_source(self, reuse_target=False, owner=None):
+        """fmap1, net, inp of the source image in img[0] (cacheable across frames: `source_owner == owner` for as long as nothing
+        overwrote them; owner = (tag, key), None = nobody asks).
         reuse_target: the source image IS the target image of this plan's previous flow() (consecutive lost frames: frame t was the
         target of the t-1 -> t flow and is the source of the t -> t+1 flow, TRK:181-184) -- its feature map is this plan's level-0
         target map: copied (fp32 map + correlation operand, two device copies) instead of a second fnet pass over the same image by
         the same launch program (bit-identical).  Volume-free correlation only (the volume mode keeps the target operand in
         4x4-tile order); -> whether the features were reused."""
         reused = bool(reuse_target) and self.otf and self.target_valid
-        self.band_valid = False
+        self._source_changed(owner)
         if reused:
             self.f1rows[:self.P].copy_(self.f2act[0].t.view(self.P, -1))
             if self.prec != "fp32":
@@ -994,10 +1045,10 @@ class _Plan:
     def encode_record(self, record):
         """fnet and cnet on the image in img[0] (the launch programs of encode_source), then the fnet map, net and inp packed into
         `record` (woft_features_pack).  Overwrites this plan's source maps: whatever source was resident here is gone, and the
-        reuse book-keeping is reset (target_valid, source_tag) -- the derived source state (split operand, gate biases) is NOT
-        brought up to date, restore_source() does that."""
-        self.source_tag, self.target_valid = None, False
-        self.band_valid = False
+        reuse book-keeping is reset (source_owner, target_owner, target_valid) -- the derived source state (split operand, gate
+        biases) is NOT brought up to date, restore_source() does that."""
+        self._source_changed()
+        self._target_changed()
         self.run(self.prog_f_src)
         self.run(self.prog_c_src)
         ops.features_pack(self.f1rows, self.net0.t, self.xbuf.t, self.P, self.record_dims, record)
@@ -1008,8 +1059,7 @@ class _Plan:
         same pass (pad rows beyond P are never written: they stay zero); then the derived steps encode_source() runs -- the
         split where it is not fused, the gate-bias convs."""
         x3 = self.prec != "fp32" and self.prec_corr == "bf16x3"
-        self.source_tag = None
-        self.band_valid = False
+        self._source_changed()
         ops.features_unpack(record, self.P, self.record_dims, self.f1rows, self.f1s if x3 else None, self.net0.t, self.xbuf.t,
                             self.inp_c.t)
         if self.prec != "fp32" and not x3:
@@ -1020,8 +1070,7 @@ class _Plan:
         """The record's fnet map -> the level-0 target map f2act[0]: flow(target_restored=True) then skips prog_f_dst and derives
         the pyramid / volumes from it (prog_volume starts from f2act[0] in every corr mode).  Until that flow has run the level-0
         operand is stale: target_valid is cleared, flow() sets it."""
-        self.target_valid = False
-        self.band_valid = False
+        self._target_changed()
         ops.features_unpack(record, self.P, self.record_dims, self.f2act[0].t)
 
     def set_flow_init(self, flow_init):
@@ -1038,7 +1087,7 @@ class _Plan:
         return self.flow4.t[:, :2].t().reshape(2, self.hf, self.wf).contiguous()
 
     def flow(self, iters, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False, trace=None, defer_wh=False,
-             mout=None, mask_sigmoid=False, flow_init=None, skip_wh=False, target_restored=False):
+             mout=None, mask_sigmoid=False, flow_init=None, skip_wh=False, target_restored=False, graph=False):
         """Target features -> volume -> `iters` refinements -> full-resolution outputs.
         defer_wh (full weighted model with a weight region set): stop before the weight head -- flow_up / dst are final,
         wout is NOT written -- and let finish_weights() evaluate the head where the caller then says it reads the weights.
@@ -1052,30 +1101,58 @@ class _Plan:
         tensor = copied into the plan's buffer first (set_flow_init); True = the buffer as it stands.  The first iteration's
         motion encoder reads it as the flow, the later coordinate updates write coords1 - coords0 as ever.  With a trace, the
         trace is also called once as trace(plan, -1) after the initialisation, before the first iteration.
-        target_restored: f2act[0] already holds the target's fnet map (restore_target): no encoder pass over img[1]."""
-        e, sp = self.eng, self.eng.spec
+        target_restored: f2act[0] already holds the target's fnet map (restore_target): no encoder pass over img[1].
+        graph: the launches (a static list on fixed buffers) as ONE hipGraph launch -- eager at the first sighting of a FlowKey,
+        eager and then captured at the second, replayed from the third, leaving the plan's Python state as the captured flow
+        left it; always eager under a trace or a bench event hook."""
         if iters < 1:
             raise ValueError("iters must be >= 1")
-        self.band_valid = False
-        if not target_restored:
-            self.run(self.prog_f_dst)
-        self.run(self.prog_volume)
-        self.target_valid = True                             # (level-0 target map + operand now belong to the image in img[1])
-        if self.band_applies(iters + (1 if e.weighted and not skip_wh else 0), flow_init):
-            self._band_build()
-        if flow_init is None:
-            ops.coords_init(self.coords, self.hf, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
-        else:
-            if flow_init is not True:
-                self.set_flow_init(flow_init)
-            ops.coords_init_flow(self.coords, self.flow_init, self.hf, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
-            if trace is not None:
-                trace(self, -1)
-        folded = self.folded is not None and trace is None   # (a trace reads the coordinates after every iteration)
+        if self._wh_train is not None:                       # (a weights_at() graph of an earlier flow in this plan is stale now: its
+            self._wh_train["gen"] += 1                       #  backward would read this flow's upsampling mask -- it raises instead)
+        if flow_init is not None and flow_init is not True:
+            self.set_flow_init(flow_init)                    # (a captured graph reads the plan's buffer: the copy stays outside)
         # restricted iterations (set_flow_region): not under a trace (it reads whole maps) nor a warm start (flow_low is read everywhere)
         region = self.flow_region if (trace is None and flow_init is None) else None
         if region is not None and region["key"][1] != iters:
             region = None
+        launch = lambda: self._flow(iters, crop, h, w, flow_up, dst, wout, do_sigmoid, trace, defer_wh, mout, mask_sigmoid,
+                                    flow_init is not None, skip_wh, target_restored, region)
+        if not graph or trace is not None or any(ev is not None for ev in (self.lookup_events, self.wh_events, self.conv_events)):
+            return launch()
+        key = FlowKey(iters, crop, h, w, _lib.ptr(flow_up), _lib.ptr(dst), _lib.ptr(wout), _lib.ptr(mout), bool(do_sigmoid),
+                      bool(mask_sigmoid), bool(defer_wh), bool(skip_wh), flow_init is not None, bool(target_restored),
+                      _lib.ptr(self.wh_region[0]) if self.wh_region is not None else None, region["key"] if region is not None else None)
+        g = self._graphs.get(key)
+        if g is not None:
+            g.replay()
+            self.band_valid, self.target_valid = g.post
+            return
+        launch()                                             # this call's results; also the warm-up the capture needs
+        if key in self._graphs:                              # (second sighting: capture for the calls to come)
+            g = _FlowGraph()
+            with torch.cuda.graph(g):
+                launch()
+            g.post = (self.band_valid, self.target_valid)
+        self._graphs[key] = g
+
+    def _flow(self, iters, crop, h, w, flow_up, dst, wout, do_sigmoid, trace, defer_wh, mout, mask_sigmoid, has_init, skip_wh,
+              target_restored, region):
+        """The launches of flow() (has_init: from the plan's flow_init buffer; region: the restricted programs, or None)."""
+        e, sp = self.eng, self.eng.spec
+        self._target_changed(self.target_owner)              # (the maps become those of the image or record already put in place)
+        if not target_restored:
+            self.run(self.prog_f_dst)
+        self.run(self.prog_volume)
+        self.target_valid = True                             # (level-0 target map + operand now belong to the image in img[1])
+        if self.band_applies(iters + (1 if e.weighted and not skip_wh else 0), has_init):
+            self._band_build()
+        if not has_init:
+            ops.coords_init(self.coords, self.hf, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
+        else:
+            ops.coords_init_flow(self.coords, self.flow_init, self.hf, self.wf, self.flow4.t, self.flow_cat, self.xbuf.cs)
+            if trace is not None:
+                trace(self, -1)
+        folded = self.folded is not None and trace is None   # (a trace reads the coordinates after every iteration)
         for it in range(iters):
             prog = self._iteration(it, iters, folded)
             self.run(prog if region is None else region["iters"].get(it, prog))
@@ -1086,16 +1163,13 @@ class _Plan:
         # (the merged last iteration ran the upsampling-mask head's first conv with the flow head's)
         for p in self.prog_mask[1 if iters > 1 and self.prog_iter_last is not None else 0:]:
             ops.run_conv(p)
-        if defer_wh:
-            assert e.weighted and not sp.small and self.wh_region is not None and not e.mask_head
-            self._upsample(None, crop, h, w, flow_up=flow_up, dst=dst, wout=None, do_sigmoid=do_sigmoid)
-            return
-        if skip_wh:
+        if defer_wh or skip_wh:
+            assert not defer_wh or (e.weighted and not sp.small and self.wh_region is not None and not e.mask_head)
             self._upsample(None, crop, h, w, flow_up=flow_up, dst=dst, wout=None, do_sigmoid=do_sigmoid)
             return
         if e.weighted:
-            self._weight_head(self.wh_region[1] if self.wh_region is not None else self.prog_wh,
-                              self.wh_region[0] if self.wh_region is not None else None)
+            index, prog = self.wh_region if self.wh_region is not None else (None, self.prog_wh)
+            self._weight_head(prog, index)
         wout = wout if e.weighted else None
         self._upsample(self.wlow, crop, h, w, flow_up=flow_up, dst=dst, wout=wout, do_sigmoid=do_sigmoid)
         if e.mask_head:
@@ -1143,6 +1217,16 @@ class _Plan:
             return
         self._upsample(self.wlow, crop, h, w, flow_up=flow_up, dst=dst, wout=wout, do_sigmoid=do_sigmoid)
 
+    def refresh_weight_head(self):
+        """After RaftEngine.repack_weight_head: this plan's own copies -- wh0_t, the closing bias tensor, the padded closing weights
+        -- refreshed in place, and no captured graph (a captured launch bakes the closing bias in as an argument)."""
+        e = self.eng
+        self.wh0_t.copy_(e.wh0.wgt[:128].t())
+        self.wh6_b.fill_(e.wh6_b)
+        if self._wh6_pad is not None:
+            self._wh6_pad[:e.wh6_c].copy_(e.wh6_w[:e.wh6_c])
+        self._graphs.clear()
+
     def _wh6_padded(self, cs):
         """The closing 1x1 conv's weights padded with zeros to the activation's channel stride (woft_wh_reduce walks whole rows)."""
         if self._wh6_pad is None or self._wh6_pad.numel() != cs:
@@ -1150,19 +1234,23 @@ class _Plan:
             self._wh6_pad[:self.eng.wh6_c] = self.eng.wh6_w[:self.eng.wh6_c]
         return self._wh6_pad
 
-    def _weight_head(self, prog_wh, index, n_needed=None, need=None):
-        """Final lookup + the weight head (weighted_raft.py:266-272, 347-384) on all source pixels (index None) or on the
-        windows listed in `index` -> self.wlow."""
-        e, sp = self.eng, self.eng.spec
-        if self.otf:                                             # final lookup, weighted_raft.py:266 -- with `need`, only the
-            self.lookup.need = _lib.ptr(need)                    # 8x8 blocks that hold a wanted window (volume-free lookup)
+    def _head_input(self, need, x8):
+        """What the weight head reads: the final lookup (weighted_raft.py:266; with `need`, on the volume-free lookup, only the 8x8
+        blocks that hold a wanted window) -> corr, then the mean response -> wmean and, with x8, the packed patches."""
+        sp = self.eng.spec
+        if self.otf:
+            self.lookup.need = _lib.ptr(need)
         self._lookup(self.lookup)
         if self.otf:
             self.lookup.need = None
-        n = sp.nwin
         ops.colsum(self.f2act[0].t, self.P, sp.fdim, self.cs_ws, self.cs_tot)
-        ops.wh_pack(self.corr, self.f1, self.cs_tot, 1.0 / (math.sqrt(float(sp.fdim)) * self.P), n, self.wmean,
-                    None if self.wh0_direct else self.x8)
+        ops.wh_pack(self.corr, self.f1, self.cs_tot, 1.0 / (math.sqrt(float(sp.fdim)) * self.P), sp.nwin, self.wmean, x8)
+
+    def _weight_head(self, prog_wh, index, n_needed=None, need=None):
+        """Final lookup + the weight head (weighted_raft.py:266-272, 347-384) on all source pixels (index None) or on the
+        windows listed in `index` -> self.wlow."""
+        e, n = self.eng, self.eng.spec.nwin
+        self._head_input(need, None if self.wh0_direct else self.x8)
         if self.x32 is not None:
             self.x32.t[:, :8].copy_(self.x8.t)                   # (generic head, first kernel wider than 3)
         n_win = int(index.numel()) if index is not None else self.P
@@ -1214,13 +1302,7 @@ class _Plan:
         n_win = int(index.numel())
         if n_win == 0:
             return wsel, None
-        if self.otf:                                     # final lookup, weighted_raft.py:266, on the blocks that hold a wanted window
-            self.lookup.need = _lib.ptr(t["bitmap"])
-        self._lookup(self.lookup)
-        if self.otf:
-            self.lookup.need = None
-        ops.colsum(self.f2act[0].t, self.P, sp.fdim, self.cs_ws, self.cs_tot)
-        ops.wh_pack(self.corr, self.f1, self.cs_tot, 1.0 / (math.sqrt(float(sp.fdim)) * self.P), n, self.wmean, None)
+        self._head_input(t["bitmap"], None)
         li = index.long()
         x8 = t["x8"][:n_win]                             # woft_wh_pack's rows of the listed windows (channels 5..7 stay zero)
         x8[:, :, :4] = self.corr.t[li, :4 * n * n].view(n_win, n * n, 4)

@@ -100,6 +100,16 @@ class _Recent:
         return dropped
 
 
+class _LastFlow:
+    """What the last compute_flow() of a provider left for the calls that follow it; a new one per call and per cache hit."""
+
+    def __init__(self, low_plan=None):
+        self.low_plan = low_plan   # flow_low(): the plan of the last COMPUTED flow (a cache hit since then leaves it)
+        self.wh = None             # weights_at(): (plan, crop) of this call's computed flow
+        self.flow_map = None       # flow_map(): the (2, H, W) buffer this call wrote, if it wrote one
+        self.deferred = None       # finish_weights(): (plan, crop, oh, ow, outputs, do_sigmoid) while weights are deferred
+
+
 class RAFTWrapper:
     def __init__(self, config):
         self.C = config
@@ -183,24 +193,22 @@ class RAFTWrapper:
                                  volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked,
                                  corr_band=self.corr_band)
         # training of the weight head (weight_head_parameters / weights_at / sync_weight_head): the head's tensors as loaded, the
-        # Parameters made of them at the first request, and the plan + crop of the last COMPUTED flow (None: none, or a cache hit)
+        # Parameters made of them at the first request
         self._wh_loaded = {k: v for k, v in state_dict.items() if k.startswith("weight_head.net.")}
-        self._wh_params, self._wh_flow = None, None
+        self._wh_params = None
         # restricted refinement iterations for callers that declare where they read the flow (pin_flow_region + flow_region=True)
         v = getattr(self.C, "flow_region", None)
         self.flow_region_on = (os.environ.get("WOFT_FLOW_REGION", "1") != "0") if (v is None or isinstance(v, type(self.C))) else bool(v)
         # opt-in (flow config key `graph`, env WOFT_GRAPH=1): the ~330 launches of a flow -- a static list per
         # resolution, fixed buffers, no allocation -- are captured once into a hipGraph and replayed per frame
         self.use_graph = (os.environ.get("WOFT_GRAPH") or str(int(bool(getattr(self.C, "graph", False))))) == "1"
-        self._pinned = None
-        self._pinned_key = None
+        self._pinned, self._pins = None, 0     # the pinned source image; how many pin_source() calls there have been
         self._wmask, self._wregion, self._all_pixels = None, {}, {}
         self._fmask, self._fregion = None, {}
-        self.weights_deferred, self._deferred = False, None
+        self.weights_deferred, self._last = False, _LastFlow()
         self.defer_min_ratio = 6           # defer_weights: region windows per named pixel from which deferring pays
         self._out = {}
         self._cache_errors = set()
-        self._last_dst = {}                # per buffer set: (id of the last dst_img object, padding geometry)
         self.source_features_reused = False
         self._plan_bound = None
         self._recent_plans, self._recent_outs, self._recent_pixels = _Recent(), _Recent(), _Recent()
@@ -221,49 +229,11 @@ class RAFTWrapper:
         if n is None:
             return
         for key in self._recent_plans.touch(plan_key, n, protect=pinned_here):
-            plan = self.engine.drop_plan(key)
-            self._last_dst.pop(id(plan), None)
+            self.engine.drop_plan(key)
         for key in self._recent_outs.touch(out_key, n, protect=pinned_here):
             self._out.pop(key, None)
         for key in self._recent_pixels.touch(n_pix, n, protect=pinned_here):
             self._all_pixels.pop(key, None)
-
-    def _run_flow(self, plan, iters, crop, oh, ow, o, weighted, do_sigmoid, defer_wh=False, want_flow=True, mask_sigmoid=False,
-                  has_init=False, skip_wh=False, target_restored=False):
-        """plan.flow() eagerly, or -- use_graph -- as ONE hipGraph launch (captured at the second call with the same
-        arguments; the per-launch event hooks of bench.py force the eager path).
-        has_init: start from the plan's flow_init buffer (filled by the caller BEFORE this call: a replayed graph reads the
-        buffer's fixed address, the copy into it is not part of the graph).
-        target_restored: the target's fnet map was restored from a record (also before this call, outside any graph) -- no target
-        encoder pass: other launches, another graph."""
-        self._wh_flow = (plan, crop)                       # (what weights_at() evaluates the head on)
-        if plan._wh_train is not None:                     # (a weights_at() graph of an earlier flow in this plan is stale now: its
-            plan._wh_train["gen"] += 1                     #  backward would read this flow's upsampling mask -- it raises instead)
-
-        def eager():
-            # (mode "TC" hands out dst = grid + flow only: the (2, H, W) flow map is then not written at all)
-            plan.flow(iters, crop, oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"], wout=o["w"] if weighted else None,
-                      do_sigmoid=do_sigmoid, defer_wh=defer_wh, mout=o.get("m"), mask_sigmoid=mask_sigmoid,
-                      flow_init=True if has_init else None, skip_wh=skip_wh, target_restored=target_restored)
-        if not self.use_graph or plan.lookup_events is not None or plan.wh_events is not None or plan.conv_events is not None:
-            return eager()
-        region = plan.wh_region
-        fregion = plan.flow_region if not has_init else None     # (restricted iterations are other launches: other graphs)
-        key = (iters, crop, oh, ow, weighted, do_sigmoid, want_flow, bool(defer_wh), o["flow"].data_ptr(),
-               region[0].data_ptr() if region is not None else 0, bool(mask_sigmoid), bool(has_init),
-               fregion["key"] if fregion is not None else None, bool(skip_wh), bool(target_restored))
-        g = plan._graphs.get(key)
-        if g is None:
-            eager()                                        # this call's results; also the warm-up the capture needs
-            if key in plan._graphs:                              # (second sighting: capture for the calls to come)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    eager()
-            plan._graphs[key] = g
-            plan._graph_band[key] = plan.band_valid
-        else:
-            g.replay()
-            plan.band_valid = plan._graph_band[key]          # (whether this flow rebuilt the correlation band for its operands)
 
     def finish_weights(self, pts, count, n_max, out=None):
         """After compute_flow(..., defer_weights=True) with `weights_deferred` set: evaluate the weight head for the
@@ -272,11 +242,15 @@ class RAFTWrapper:
         the named pixels, in their order.  The weights of a source pixel do not depend on the
         other pixels (weighted_raft.py:363-383), and the caller knows which correspondences it keeps before it needs
         their weights (TRK:287-312 + subsampler: decided by the flow alone)."""
-        plan, crop, oh, ow, o, do_sigmoid = self._deferred
-        self._deferred = None
+        plan, crop, oh, ow, o, do_sigmoid = self._last.deferred
+        self._last.deferred = None
         plan.finish_weights(pts, count, n_max, crop, crop, oh, ow, flow_up=o["flow"], dst=o["dst"], wout=o["w"],
                             do_sigmoid=do_sigmoid, w_points=out)
         return o["w"] if out is None else out
+
+    @property
+    def _wh_flow(self):
+        return self._last.wh
 
     # ---- training of the weight head (woft_amd/wh_train.py, DESIGN.md section 17) ----
     def _wh_trainable(self):
@@ -308,7 +282,7 @@ class RAFTWrapper:
         (once differentiable; deterministic); nothing else receives a gradient -- RAFT stays frozen.  backward() must run before
         the next compute_flow / weights_at of this provider: it reads the plan's buffers."""
         self._wh_trainable()
-        if self._wh_flow is None:
+        if self._last.wh is None:
             raise RuntimeError("weights_at(): no computed flow to evaluate the head on (none yet, or the last one came from the "
                                "flow cache)")
         if not (isinstance(pts, torch.Tensor) and pts.is_cuda and pts.dtype == torch.float32 and pts.dim() == 2
@@ -319,7 +293,7 @@ class RAFTWrapper:
         if count is not None and not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32
                                       and count.numel() == 1):
             raise TypeError("weights_at(): count must be a device int32 scalar")
-        plan, crop = self._wh_flow
+        plan, crop = self._last.wh
         params = self.weight_head_parameters().values()
         return wh_train.weights_at(plan, params, pts.detach().contiguous(), count, int(pts.shape[0]), crop, do_sigmoid)
 
@@ -334,7 +308,7 @@ class RAFTWrapper:
         """Declare `src_img` (an ndarray the caller will not mutate) as a recurring source image:
         its feature/context tensors are computed once and reused by compute_flow(src_img, ...)."""
         self._pinned = src_img
-        self._pinned_key = None
+        self._pins += 1                                    # (a source resident under an earlier pin is not this one's: see compute_flow)
         self._wmask, self._wregion = None, {}
         self._fmask, self._fregion = None, {}
 
@@ -408,7 +382,7 @@ class RAFTWrapper:
         'half_flow' (2,H,W) and 'half_weights' (1,H,W) (any float dtype, cast to fp32); then the same
         post-processing as a computed flow (raft.py:152-195)."""
         dataset_name, seq_name, frame_i = identifier
-        self._wh_flow = None                               # (a cache hit leaves the network's buffers at an older flow: weights_at() refuses)
+        self._last = _LastFlow(self._last.low_plan)        # (a cache hit leaves the network's buffers at an older flow: weights_at() refuses)
         path = Path(self.C.flow_cache_dir) / dataset_name / seq_name / f"{frame_i}-{frame_i + 1}.npz"
         data = np.load(path, allow_pickle=False)           # plain float arrays: nothing to unpickle
         flow = np.ascontiguousarray(data["half_flow"].astype(np.float32))
@@ -483,7 +457,7 @@ class RAFTWrapper:
         """After any COMPUTED flow (not a cache hit): its final 1/8-resolution flow coords1 - coords0, (2, hp/8, wp/8) fp32 on
         the device, in 1/8-resolution pixels of the padded image -- the reference network's flow_low (weighted_raft.py:240-255),
         which its wrapper drops.  copy=False: a view of the engine's buffer, valid until the next flow in the same buffer set."""
-        plan = getattr(self, "_low_plan", None)
+        plan = self._last.low_plan
         if plan is None:
             raise RuntimeError("flow_low(): no flow has been computed yet")
         return plan.flow_low() if copy else plan.flow4.t[:, :2].t().reshape(2, plan.hf, plan.wf)
@@ -491,7 +465,7 @@ class RAFTWrapper:
     def flow_map(self):
         """After a computed compute_flow(mode='flow') or compute_flow(mode='TC', keep_flow=True): the (2, H, W) flow map of that
         call -- the provider's own buffer, valid until the next call at the same output size."""
-        m = getattr(self, "_flow_map", None)
+        m = self._last.flow_map
         if m is None:
             raise RuntimeError("flow_map(): the last flow wrote no flow map (mode 'TC' without keep_flow, or no flow yet)")
         return m
@@ -529,9 +503,6 @@ class RAFTWrapper:
         plan = self.engine.plan(hp, wp, slot)
         self._touch_plan((hp, wp) if slot == 0 else (hp, wp, slot), (oh, ow), plan.P, False)
         plan.load_image(0, self._upload(img, H, W, lh, lw, "encode_frame"), top, left)
-        self._last_dst.pop(id(plan), None)
-        if slot == 0:
-            self._pinned_key = None
         record = plan.new_record()
         plan.encode_record(record)
         return FrameFeatures(self, record, (hp, wp, top, left), (H, W))
@@ -617,7 +588,7 @@ class RAFTWrapper:
                 raise ValueError(f"compute_flow: the operands have different padded geometries (hp, wp, top, left, H, W): src {gs}, "
                                  f"dst {gd} -- a FrameFeatures record serves only the geometry it was encoded at")
         assert src_img.shape == dst_img.shape
-        self._flow_map = None
+        self._last = _LastFlow(self._last.low_plan)
         if src_img_identifier is not None and self.masked:
             # (deviation: the flow cache holds no mask -- utils/caching.py:53-59 -- and the reference raises UnboundLocalError on a
             #  cache hit with 'weighted_masked' (raft.py:171,202); here the cache is skipped and the flow computed, with its mask)
@@ -651,24 +622,20 @@ class RAFTWrapper:
 
         up = lambda a: self._upload(a, H, W, lh, lw)
         key = (hp, wp, top, left)
-        if pinned_here and self._pinned_key == key and plan.source_tag is self:
+        # (the pinned source claims what encode_source() leaves; the plan drops the claim when anything overwrites that state)
+        owner = (self, (self._pins,) + key) if pinned_here else None
+        if owner is not None and plan.source_owner == owner:
             pass                                           # fmap1 / net / inp still resident in the plan
         elif src_rec is not None:                          # the source state of an encode_source() of the record's image
             plan.restore_source(src_rec.record)
             self.source_features_reused = False
-            if slot == 0:
-                self._pinned_key = None
         else:
-            s = up(src_img)
-            plan.load_image(0, s, top, left)
+            plan.load_image(0, up(src_img), top, left)
             # src_is_previous_dst (extension, the shim's tracker on consecutive lost frames): the caller states that src_img is the
             # image it passed as dst_img in its previous call for this buffer set; honoured only when that is the very same object
             # and geometry -- then the source features are the previous call's target features (engine.encode_source)
-            reuse = bool(src_is_previous_dst) and self._last_dst.get(id(plan)) == (id(src_img), key)
-            self.source_features_reused = bool(plan.encode_source(reuse_target=reuse))
-            plan.source_tag = self if pinned_here else None
-            if pinned_here:
-                self._pinned_key = key
+            reuse = bool(src_is_previous_dst) and plan.target_owner == (id(src_img), key)
+            self.source_features_reused = bool(plan.encode_source(reuse_target=reuse, owner=owner))
         post = self.C.weights_postprocessing_fn or None     # (a map -> map callable may read any pixel: full map)
         region = None
         if weight_region and not post:
@@ -686,12 +653,10 @@ class RAFTWrapper:
             frect = self._flow_region(key, hp, wp, top, left, oh, ow)
         plan.set_flow_region(frect, n_iters)
         if dst_rec is not None:
-            plan.restore_target(dst_rec.record)
-            self._last_dst.pop(id(plan), None)             # (img[1] is not this target: nothing for src_is_previous_dst to reuse)
+            plan.restore_target(dst_rec.record)            # (img[1] is not this target: nothing for src_is_previous_dst to reuse)
         else:
-            d = up(dst_img)
-            plan.load_image(1, d, top, left)
-            self._last_dst[id(plan)] = (id(dst_img), key)     # (what this buffer set's target features will belong to after this call)
+            # (owner: what this buffer set's target features will belong to after this call)
+            plan.load_image(1, up(dst_img), top, left, owner=(id(dst_img), key))
         o = self._outputs(oh, ow)
         weighted = self.C.raft_type in ("weighted", "weighted_masked") and not skip_weights
         # (defer_weights = the number of pixels the caller will name: worth it only if their 3x3 supports cannot cover most
@@ -701,15 +666,15 @@ class RAFTWrapper:
                                      and plan.wh_region is not None
                                      and mode == "TC" and not numpy_out
                                      and int(plan.wh_region[0].numel()) > self.defer_min_ratio * int(defer_weights))
-        self._deferred = (plan, (top, left), oh, ow, o, bool(do_sigmoid)) if self.weights_deferred else None
-        if flow_init is not None:
-            plan.set_flow_init(flow_init)                   # (outside any graph: see _run_flow)
-        self._run_flow(plan, n_iters, (top, left), oh, ow, o, weighted, bool(do_sigmoid) and not post,
-                       defer_wh=self.weights_deferred, want_flow=(mode == "flow" or bool(keep_flow)),
-                       mask_sigmoid=bool(visibility), has_init=flow_init is not None,
-                       skip_wh=bool(skip_weights) and not self.masked, target_restored=dst_rec is not None)
-        self._flow_map = o["flow"] if (mode == "flow" or keep_flow) else None
-        self._low_plan, self.last_flow_key = plan, (slot,) + key
+        self._last.wh = (plan, (top, left))
+        self._last.deferred = (plan, (top, left), oh, ow, o, bool(do_sigmoid)) if self.weights_deferred else None
+        want_flow = mode == "flow" or bool(keep_flow)      # (mode "TC" hands out dst = grid + flow only: no (2, H, W) flow map)
+        plan.flow(n_iters, (top, left), oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"],
+                  wout=o["w"] if weighted else None, do_sigmoid=bool(do_sigmoid) and not post, defer_wh=self.weights_deferred,
+                  mout=o.get("m"), mask_sigmoid=bool(visibility), flow_init=flow_init, skip_wh=bool(skip_weights) and not self.masked,
+                  target_restored=dst_rec is not None, graph=self.use_graph)
+        self._last.flow_map = o["flow"] if want_flow else None
+        self._last.low_plan, self.last_flow_key = plan, (slot,) + key
         if self.weights_deferred:
             return self._deliver(o, None, mode, oh, ow, numpy_out, borrow)
         logger.debug(f"flow enqueue time [s]: {float(timer() - start_time)}")

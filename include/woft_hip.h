@@ -335,6 +335,10 @@ typedef struct woft_lookup_band_params {
     float* band;                /* [hf*wf][rows][WOFT_BAND_LD]                                                     */
     int32_t* miss;              /* [hf*wf]: 1 where the pixel's 8 x 8 block was launched and missed the band, else 0 */
     int32_t* miss_count;        /* [1]: + 1 per missed block                                                      */
+    int32_t defer_samples;      /* woft_corr_lookup_band only.  Non-zero: everything as with 0 (need / roi_* / smp_* rules, folded
+                                   flow-head gather with all its stores, hit test, miss flags, miss counter) except that the samples
+                                   of HIT blocks are not written -- their rows of otf.out are left untouched; woft_conv1x1_band
+                                   interpolates them inside convc1's launch.  Missed blocks are the fallback's as before.        */
 } woft_lookup_band_params;
 /* Fills the band from otf.f1 / otf.f2 (every value bit-identical to woft_corr_gemm_bf16's for that pair: the volume-free
  * lookup's chunk loop on the band's bounding boxes); reads no coordinates, ignores need / fh_* / roi_* / smp_* / out. */
@@ -346,6 +350,22 @@ int woft_corr_band_build(const woft_lookup_band_params* p, void* stream);
  * set and *miss_count grows by one: woft_corr_lookup_otf with need = miss, fh_part = NULL and the same rectangles then
  * computes exactly the missed blocks.  Blocks skipped by need or smp_* are flagged 0. */
 int woft_corr_lookup_band(const woft_lookup_band_params* p, void* stream);
+/* The motion encoder's convc1 (update.py:89; 324 lookup samples -> 256, 1x1) with the band lookup's sampling inside its launch
+ * (csrc/conv_1x1_band.hip): the third launch of an iteration after woft_corr_lookup_band(defer_samples = 1) and its fallback
+ * woft_corr_lookup_otf(need = miss).  A workgroup owns one 8 x 8 block of source pixels (the band lookup's blocks, order and XCD
+ * mapping) x all 256 columns.  It reads the block's coordinates -- already updated; nothing is gathered here -- derives window
+ * origins and fractions with the band lookup's expressions and applies the hit rule itself (block-uniform; the miss flags are
+ * not read, the band is never addressed outside a pixel's rows).  Hit: the levels' band rows stream through LDS and are
+ * interpolated with the band lookup's arithmetic, cell for cell, into the split A tiles of the streamed GEMM kernel; the samples
+ * never reach memory.  Miss: the block's rows are loaded from c1->in0, where the fallback has just written them.  Then
+ * conv1x1_kernel's K loop and epilogue: 11 chunks of 32 channels (324..351 zero), ascending, same products in the same order --
+ * c1->out equals woft_conv2d's on the three-launch form bit for bit.  f1 (optional): a flat layer (convf1) that shares the launch
+ * as in woft_conv2d_pair, on the workgroups behind the blocks'.
+ * Instance: bp->otf radius 4, k 256, 4 levels, no need / roi_* / smp_* / ablate, otf.out == c1->in0 and otf.ldo == c1->cs0;
+ * c1: halo 16, 1x1, n_img 1, h x w = hf x wf, cin_pad 352, cout_pad 256, tile_n 256, no in1 / statistics / rectangle, an
+ * element-wise or GRU epilogue; precision 1, 2 or 3 (the band's terms, 1 or 3, are independent of it: the band holds fp32
+ * correlations); f1 as woft_conv2d_pair asks of a flat partner -- the same precision -- and no rectangle.  bp's fh_* fields are ignored.  Anything else: WOFT_EINVAL before any launch. */
+int woft_conv1x1_band(const woft_conv_params* c1, const woft_conv_params* f1, const woft_lookup_band_params* bp, void* stream);
 /* NHWC map [h][w][c] -> its rows in 4x4-tile order [(ceil(h/4)*ceil(w/4)*16)][c], zero rows outside
  * the map: the B operand of the correlation GEMM that yields the tiled volume layout above. */
 int woft_tile_rows(const float* in, int32_t h, int32_t w, int32_t c, float* out, void* stream);

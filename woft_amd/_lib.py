@@ -59,7 +59,7 @@ class LookupOtfParams(C.Structure):
 class LookupBandParams(C.Structure):
     # woft_lookup_band_params: the embedded woft_lookup_otf_params spelled out field by field (the same layout; a flat mirror
     # keeps every field a scalar, a pointer or an array of them)
-    _fields_ = LookupOtfParams._fields_ + [("band", vp), ("miss", vp), ("miss_count", vp)]
+    _fields_ = LookupOtfParams._fields_ + [("band", vp), ("miss", vp), ("miss_count", vp), ("defer_samples", i32)]
 
 
 _SIGS = {
@@ -76,6 +76,7 @@ _SIGS = {
     "woft_corr_band_geometry": (i32, [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "woft_corr_band_build": (i32, [C.POINTER(LookupBandParams), vp]),
     "woft_corr_lookup_band": (i32, [C.POINTER(LookupBandParams), vp]),
+    "woft_conv1x1_band": (i32, [C.POINTER(ConvParams), C.POINTER(ConvParams), C.POINTER(LookupBandParams), vp]),
     "woft_conv3x3_narrow": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i64, i32, vp]),
     "woft_flow_head_update": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     "woft_flow_head_gather": (i32, [vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, i32, vp]),

@@ -1073,6 +1073,8 @@ static int conv_check(const woft_conv_params& p) {
         return WOFT_EINVAL;
     return WOFT_OK;
 }
+// (the argument checks of woft_conv2d for another unit's entry point: conv_1x1_band.hip)
+int woft_conv_check(const woft_conv_params& p) { return conv_check(p); }
 #endif  // WOFT_ONLY_PREC == 1 (argument checks)
 
 // second != NULL: one launch for two layers that run on the same kernel instance (woft_conv2d_pair)

@@ -8,6 +8,8 @@
 // memory -- stream into LDS as 16-byte pieces, the next level's while this level's samples are interpolated with the arithmetic of
 // corr_lookup_kernel (the volume-free lookup's sampling loop, cell for cell).  No MFMA, no source fragments; 130 registers and
 // 54 KB of LDS: two workgroups per CU, which is what a 1080p launch (510 blocks on 256 CUs) asks for.
+// woft_lookup_band_params.defer_samples: the launch stops after the hit test -- flags, counter and the gather's stores as ever, no
+// sample written; the interpolation below then runs inside convc1's launch (conv_1x1_band.hip), which repeats the hit test.
 #include "common.h"
 #include "lookup_blocks.h"
 
@@ -115,6 +117,7 @@ __global__ __launch_bounds__(256) void corr_lookup_band_kernel(const woft_lookup
         if (tid == 0) atomicAdd(bp.miss_count, 1);
         return;
     }
+    if (bp.defer_samples != 0) return;                   // (the samples of hit blocks are woft_conv1x1_band's: conv_1x1_band.hip)
     const int rows = band_row_off(R, p.levels);
     // this thread's pieces of a level: piece k = (pixel, band row, quarter) = it / (4 WS), (it / 4) % WS, it % 4 with it = tid + k NT
     f32x4 pc[NLD];

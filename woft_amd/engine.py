@@ -53,6 +53,11 @@ FOLD_GATHER = os.environ.get("WOFT_FOLD_GATHER", "1") != "0"
 # results.  RaftEngine(corr_band=): "auto" = flows of at least BAND_MIN_LOOKUPS lookups, True = every flow the band applies to,
 # False = none; WOFT_CORR_BAND=0 switches it off everywhere.
 CORR_BAND = os.environ.get("WOFT_CORR_BAND", "1") != "0"
+# convc1 samples the band inside its own launch (csrc/conv_1x1_band.hip): on a plan with a valid band an
+# unrestricted iteration runs the band lookup with its samples deferred, the fallback, and woft_conv1x1_band in place of
+# conv2(convc1, convf1) -- the samples of hit blocks never reach memory.  Bit-identical results.  RaftEngine(fuse_c1=False) or
+# WOFT_FUSE_C1=0: the three launches as they were (A/Bs, tests).
+FUSE_C1 = os.environ.get("WOFT_FUSE_C1", "1") != "0"
 # lookups from which the once-per-flow build pays: build time / saving per lookup, rounded up -- 132.8 us / (69.4 - 30.6 us) = 3.4
 # -> 4 at 1080p (profiles/lookup_band_ab.txt) -- and never below 6: below that the gain is inside the run-to-run spread, and
 # short flows keep their launch programs
@@ -183,7 +188,7 @@ class _Enc:
 
 class RaftEngine:
     def __init__(self, state_dict, small=False, weighted=True, precision="fp32", corr="volume", volume_storage=None,
-                 mask_head=False, corr_band="auto"):
+                 mask_head=False, corr_band="auto", fuse_c1=True):
         """precision: "fp32" (exact fp32 MFMA), "bf16x3" (split-bf16, fp32-emulating), "bf16", or "fp16" = the reference's
         `mixed_precision` scoping (weighted_raft.py:204-219,233-234,258-290: autocast around fnet, cnet and the update block
         only): those convolutions on fp16 operands with fp32 accumulation, the correlation, the weight head and both
@@ -209,6 +214,7 @@ class RaftEngine:
         if corr_band not in ("auto", True, False):
             raise ValueError("corr_band must be 'auto', True or False")
         self.corr_band = corr_band
+        self.fuse_c1 = bool(fuse_c1)
         self.volume_storage = volume_storage or ("bf16" if precision == "bf16" else "fp32")
         if self.volume_storage not in ("fp32", "bf16") or (self.volume_storage == "bf16" and precision == "fp32"):
             raise ValueError("volume_storage: 'fp32', or 'bf16' with the split-bf16 precisions (their GEMM packs it)")
@@ -379,6 +385,7 @@ class _Plan:
         # volume-free struct they mirror)
         self._band = None
         self._band_params = {}
+        self._fuse_c1 = False      # this flow's iterations may run convc1 on the band (set by _flow: never under a trace)
         # what only some plans have: the full model's upsampling mask, a merged last iteration, the folded programs, fh_part (flow
         # head folded into one conv launch: per-pixel partial products of its second conv), the two heads
         self.mk = self.mask = self.prog_iter_last = self.folded = self.fh_part = None
@@ -880,7 +887,11 @@ class _Plan:
     # ---- execution ------------------------------------------------------------------------
     def run(self, prog):
         ev = self.conv_events
-        for kind, a, tag in prog:
+        fused = False
+        for k, (kind, a, tag) in enumerate(prog):
+            if fused:                                        # (convc1 [+ convf1]: ran with the lookup before it)
+                fused = False
+                continue
             if kind == "conv":                               # (ev, a bench hook: HIP events around the launches whose tag it names)
                 ops.run_conv(a) if ev is None else _timed(ev.get(tag), ops.run_conv, a)
             elif kind == "conv2":
@@ -902,7 +913,11 @@ class _Plan:
             elif kind == "cgemm":
                 ops.corr_gemm_bf16(*a)
             elif kind == "lookup":
-                self._lookup(a)
+                fused = k + 1 < len(prog) and self._c1_on_band(a, prog[k + 1])
+                if fused:
+                    self._lookup_c1_band(a, prog[k + 1])
+                else:
+                    self._lookup(a)
             elif kind == "copy":
                 a[1].copy_(a[0])
             elif kind == "fh_gather":
@@ -968,6 +983,39 @@ class _Plan:
         bp = self._band_variant(params)
         ops.run_lookup_band(bp)
         ops.run_lookup_otf(bp._fallback)
+
+    def _c1_on_band(self, params, nxt):
+        """Whether the lookup `params` and the step after it run as the fused form: a valid band, whole-map launches (a
+        restricted iteration keeps its three launches: the fused kernel takes no rectangle), and the step is convc1 -- alone or
+        paired with convf1 -- of the instance woft_conv1x1_band is built for."""
+        if not (self._fuse_c1 and self.band_valid) or nxt.tag not in ("convc1+convf1", "convc1"):
+            return False
+        sp = self.eng.spec
+        c1 = nxt.arg[0] if nxt.kind == "conv2" else nxt.arg
+        rect = lambda q: (q.roi_y0 | q.roi_x0 | q.roi_h | q.roi_w) != 0
+        if params.need or rect(params) or (params.smp_y0 | params.smp_x0 | params.smp_h | params.smp_w) != 0 or rect(c1):
+            return False
+        return ((sp.radius, sp.fdim, sp.levels) == (4, 256, 4) and Kernel(c1.halo) is Kernel.GEMM_1X1
+                and c1.precision in (1, 2, 3) and (c1.cin_pad, c1.cout_pad) == (352, 256)
+                and c1.in0 == params.out and c1.cs0 == params.ldo)
+
+    def _lookup_c1_band(self, params, nxt):
+        """Band lookup with the samples deferred, the fallback on the blocks it flagged, then convc1 sampling the band itself
+        (+ convf1 on the workgroups behind).  The lookup buffer keeps stale rows where blocks hit: nothing reads it before the
+        next lookup (the final lookup, which feeds the weight head, is never followed by convc1)."""
+        bp = self._band_variant(params)
+
+        def lookup():
+            bp.defer_samples = 1
+            try:
+                ops.run_lookup_band(bp)
+            finally:
+                bp.defer_samples = 0
+            ops.run_lookup_otf(bp._fallback)
+        _timed(self.lookup_events, lookup)
+        c1, f1 = nxt.arg if nxt.kind == "conv2" else (nxt.arg, None)
+        ev = self.conv_events
+        _timed(None if ev is None else ev.get(nxt.tag), ops.run_conv1x1_band, c1, f1, bp)
 
     @property
     def band_miss_blocks(self):
@@ -1139,6 +1187,7 @@ class _Plan:
               target_restored, region):
         """The launches of flow() (has_init: from the plan's flow_init buffer; region: the restricted programs, or None)."""
         e, sp = self.eng, self.eng.spec
+        self._fuse_c1 = FUSE_C1 and e.fuse_c1 and trace is None    # (a trace reads the lookup buffer after every iteration)
         self._target_changed(self.target_owner)              # (the maps become those of the image or record already put in place)
         if not target_restored:
             self.run(self.prog_f_dst)

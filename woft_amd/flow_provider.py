@@ -189,9 +189,13 @@ class RAFTWrapper:
         # computed once per flow, the lookups sampling from them (engine.py: CORR_BAND) -- "auto": flows long enough for it to pay
         v = getattr(self.C, "corr_band", None)
         self.corr_band = "auto" if (v is None or isinstance(v, type(self.C))) else (v if v == "auto" else bool(v))
+        # flow config key `fuse_c1` (default True; env WOFT_FUSE_C1=0: off): on a band flow convc1 samples the band inside its
+        # own launch (engine.py: FUSE_C1)
+        v = getattr(self.C, "fuse_c1", None)
+        self.fuse_c1 = True if (v is None or isinstance(v, type(self.C))) else bool(v)
         self.engine = RaftEngine(state_dict, small=small, weighted=weighted, precision=self.precision, corr=self.corr,
                                  volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked,
-                                 corr_band=self.corr_band)
+                                 corr_band=self.corr_band, fuse_c1=self.fuse_c1)
         # training of the weight head (weight_head_parameters / weights_at / sync_weight_head): the head's tensors as loaded, the
         # Parameters made of them at the first request
         self._wh_loaded = {k: v for k, v in state_dict.items() if k.startswith("weight_head.net.")}

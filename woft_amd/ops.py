@@ -520,6 +520,13 @@ def run_lookup_band(p):
     check(_lib.load().woft_corr_lookup_band(C.byref(p), stream_ptr()), "woft_corr_lookup_band")
 
 
+def run_conv1x1_band(c1, f1, bp):
+    """convc1 with the band lookup's sampling inside its launch, convf1 (or None) on the workgroups behind (woft_conv1x1_band);
+    bp: the band lookup's struct of the iteration, launched before with defer_samples = 1 and followed by its fallback."""
+    check(_lib.load().woft_conv1x1_band(C.byref(c1), C.byref(f1) if f1 is not None else None, C.byref(bp), stream_ptr()),
+          "woft_conv1x1_band")
+
+
 def split_bf16_lines(x, out):
     """x fp32 [rows][k] -> out bf16 [rows][2k]: per 32 values one 128-byte line [hi | lo] (woft_split_bf16_lines)."""
     check(_lib.load().woft_split_bf16_lines(ptr(x), x.numel(), ptr(out), stream_ptr()), "woft_split_bf16_lines")

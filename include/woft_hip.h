@@ -594,6 +594,35 @@ int woft_wh_train_conv(const float* x, int32_t cin, const float* wt, const float
 int64_t woft_wh_wgrad_ws_bytes(int32_t n_win, int32_t cin);
 int woft_wh_wgrad(const float* gy, const float* x, int32_t cin, int32_t cin_out, int32_t n_win, float* ws, float* gw,
                   float* gb, void* stream);
+/* ---- Training of the MaskHead (weighted_raft.py:295-309, 387-422) ------------------------------------
+ * The head is an ordinary conv stack over the whole 1/8-resolution map: 3x3 convs with zero padding at the map border, a ReLU
+ * after each, a closing 1x1 conv to one logit per pixel.  Maps are NHWC fp32, [hf * wf pixels][channel stride]; channel counts
+ * are multiples of 32, cout <= 128, cin <= 512.  A map may come as two sources (the first layer reads [fmap1 | warped fmap2],
+ * weighted_raft.py:297-302, without a concatenated copy): channels below c_split from x0, the others from x1 (x1 NULL:
+ * c_split = cin).  Exact fp32 (v_mfma_f32_32x32x2_f32 products); no floating-point atomics: the parameter gradients are written
+ * as one partial per WOFT_MH_TRAIN_CHUNK tiles of WOFT_MH_TRAIN_TILE positions of a map row (per WOFT_MH_REDUCE_CHUNK pixels
+ * for the closing conv) -- a partition of the map that does not depend on the grid -- and added in chunk order in fp64.
+ *
+ * woft_mh_train_conv: y[p][co] = sum_{tap,ci} x[p + tap][ci] * wt[tap][ci][co]  (wt: [9][cin][cout], tap = ky*3+kx; taps outside
+ *   the map read zero), then with bias: relu(y + bias[co]) -- a forward layer (weighted_raft.py:411-422) --, or with gate
+ *   ([pixels][gate_cs]): y where gate > 0, else 0 -- the data gradient of a layer when wt holds its transposed, flipped filter and
+ *   gate the activation below it.  Not both.
+ * woft_mh_wgrad: gw[co][ci][ky][kx] = sum_p gy[p][co] * x[p + tap][ci] (the state dict's layout), gb[co] = sum_p gy[p][co].
+ *   ws: woft_mh_wgrad_ws_bytes(hf, wf, cin, cout) bytes of partial sums.
+ * woft_mh_reduce_bwd: adjoint of the closing 1x1 conv low[p] = b + <w, act[p]>:  g_act[p][c] = g_low[p] * w[c] * (act[p][c] > 0),
+ *   g_w[c] = sum_p g_low[p] * act[p][c], g_b[0] = sum_p g_low[p].  ws: ceil(n_pix / WOFT_MH_REDUCE_CHUNK) * 129 doubles.
+ * All return WOFT_EINVAL before any launch on a NULL required pointer or a size outside the stated range. */
+#define WOFT_MH_TRAIN_TILE 32
+#define WOFT_MH_TRAIN_CHUNK 16
+#define WOFT_MH_REDUCE_CHUNK 256
+int woft_mh_train_conv(const float* x0, int32_t cs0, const float* x1, int32_t cs1, int32_t c_split, int32_t cin, const float* wt,
+                       int32_t cout, const float* bias, const float* gate, int32_t gate_cs, int32_t hf, int32_t wf, float* y,
+                       int32_t y_cs, void* stream);
+int64_t woft_mh_wgrad_ws_bytes(int32_t hf, int32_t wf, int32_t cin, int32_t cout);
+int woft_mh_wgrad(const float* gy, int32_t gy_cs, int32_t cout, const float* x0, int32_t cs0, const float* x1, int32_t cs1,
+                  int32_t c_split, int32_t cin, int32_t hf, int32_t wf, float* ws, float* gw, float* gb, void* stream);
+int woft_mh_reduce_bwd(const float* act, int32_t act_cs, int32_t c, const float* w, const float* g_low, int32_t n_pix,
+                       float* g_act, int32_t g_cs, double* ws, float* g_w, float* g_b, void* stream);
 /* Pre-computed flow read from the reference's cache files (utils/caching.py:53-59; raft.py:93-106) to the same
  * outputs: dst[2][h*w] = pixel grid + flow[2][h*w] (may be NULL), wout[h*w] = weights or sigmoid(weights)
  * (weights / wout may be NULL). */

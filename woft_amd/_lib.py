@@ -113,6 +113,10 @@ _SIGS = {
     "woft_wh_train_conv": (i32, [vp, i32, vp, vp, vp, i32, vp, vp]),
     "woft_wh_wgrad_ws_bytes": (i64, [i32, i32]),
     "woft_wh_wgrad": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "woft_mh_train_conv": (i32, [vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp]),
+    "woft_mh_wgrad_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "woft_mh_wgrad": (i32, [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "woft_mh_reduce_bwd": (i32, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
     "woft_upflow8": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "woft_warp_perspective_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), vp, vp, i32, vp]),
     "woft_resize_linear_u8": (i32, [vp, i32, i32, i32, vp, i32, i32, f32, f32, vp]),

@@ -30,7 +30,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib, conv_select, flow_region, ops, wh_train
+from . import _lib, conv_select, flow_region, mh_train, ops, wh_train
 from .conv_select import KERNELS, Kernel
 from .ops import Act, new_act
 
@@ -343,10 +343,30 @@ class RaftEngine:
         if not ok:
             raise ValueError(f"mask head layers {shapes}: not a MaskHead on {2 * sp.fdim} channels (weighted_raft.py:387-409)")
         self.mh_shapes = shapes
-        self.mh_layers = [ops.pack_conv(sd[f"{m}{i}.weight"], sd[f"{m}{i}.bias"]) for i in idx[:-1]]
         self.mh_c = shapes[-1][1]
-        self.mh_wlast = sd[f"{m}{idx[-1]}.weight"].reshape(-1).clone()
-        self.mh_b = float(sd[f"{m}{idx[-1]}.bias"].item())
+        self.mh_layers, self.mh_wlast, self.mh_b = self._mh_packed(sd, idx)
+
+    @staticmethod
+    def _mh_packed(sd, idx):
+        """The MaskHead's layers net.{idx} of `sd` packed for the conv kernels -> (mh_layers, mh_wlast, mh_b)."""
+        m = "mask_head.net."
+        layers = [ops.pack_conv(sd[f"{m}{i}.weight"], sd[f"{m}{i}.bias"]) for i in idx[:-1]]
+        return layers, sd[f"{m}{idx[-1]}.weight"].reshape(-1).clone(), float(sd[f"{m}{idx[-1]}.bias"].item())
+
+    def repack_mask_head(self, sd):
+        """Re-pack the MaskHead from `sd` (its mask_head.net.* tensors) IN PLACE into every device buffer the inference path reads
+        head parameters from -- the engine's packed layers in every form they have, the closing conv's weights and bias, and every
+        plan's own copy (_Plan.refresh_mask_head, which also drops the plan's captured graphs: a captured launch bakes the closing
+        bias in as an argument).  The next flow then has the bits of an engine built from `sd`."""
+        assert self.mask_head
+        sd = {k: v.detach().float().cpu() for k, v in sd.items() if k.startswith("mask_head.net.")}
+        layers, wlast, b = self._mh_packed(sd, list(range(0, 2 * len(self.mh_shapes), 2)))
+        for old, new in zip(self.mh_layers, layers):
+            ops.repack_conv_(old, new)
+        self.mh_wlast.copy_(wlast)
+        self.mh_b = b
+        for plan in self._plans.values():
+            plan.refresh_mask_head()
 
     def plan(self, hp, wp, slot=0):
         """Buffers + launch programs for one padded input size.  slot: an independent second set for the same size (the
@@ -398,6 +418,7 @@ class _Plan:
         self.wh_region, self._wh_regions = None, {}            # None = every source pixel (set_weight_region)
         self._wh_dyn = {}                                      # per region: (dynamic window list, its programs, scratch)
         self._wh_train = None                                  # buffers of wh_train_forward / wh_train_backward (first use)
+        self._mh_train = None                                  # buffers of mh_train_forward / mh_train_backward (first use)
         self._plan_features()
         self._plan_update_block()
         if eng.weighted:
@@ -1157,6 +1178,8 @@ class _Plan:
             raise ValueError("iters must be >= 1")
         if self._wh_train is not None:                       # (a weights_at() graph of an earlier flow in this plan is stale now: its
             self._wh_train["gen"] += 1                       #  backward would read this flow's upsampling mask -- it raises instead)
+        if self._mh_train is not None:                       # (a visibility_at() graph alike)
+            self._mh_train["gen"] += 1
         if flow_init is not None and flow_init is not True:
             self.set_flow_init(flow_init)                    # (a captured graph reads the plan's buffer: the copy stays outside)
         # restricted iterations (set_flow_region): not under a trace (it reads whole maps) nor a warm start (flow_low is read everywhere)
@@ -1384,4 +1407,61 @@ class _Plan:
                                   state["crop"], t["g_wlow"], index=index, do_sigmoid=state["do_sigmoid"])
         wh_train.head_backward(t["x8"], n_win, (state["w2"], state["w4"], state["w6"]), t["act"], t["g_wlow"], index, t["g"],
                                t["ws"], t["ws64"], grads)
+        return grads
+
+    # ---- training of the mask head (woft_amd/mh_train.py) --------------------------------------------
+    def refresh_mask_head(self):
+        """After RaftEngine.repack_mask_head: this plan's own copy of the closing conv's weights refreshed in place, and no
+        captured graph (a captured launch bakes the closing bias in as an argument)."""
+        self.mh_w[:self.eng.mh_c].copy_(self.eng.mh_wlast)
+        self._graphs.clear()
+
+    def _mh_train_buffers(self):
+        """Buffers of the training path, sized by the map (P pixels) and the head, allocated at the first use: one activation
+        map per layer, two gradient maps as wide as the widest layer, the 1/8-resolution logits and their gradient, the partial
+        sums of the widest weight gradient (ceil(hf * ceil(wf / 32) / 16) partials of 9 * C * cin + C floats) and of the closing
+        conv (ceil(P / 256) * 129 doubles).  None of them is read by flow()."""
+        t = self._mh_train
+        if t is None:
+            z, P, hf, wf = self._z, self.P, self.hf, self.wf
+            shapes = self.eng.mh_shapes[:-1]
+            t = dict(act=[z(P, s[0]) for s in shapes], g=[z(P, max(s[0] for s in shapes)) for _ in range(2)], out=z(P), low=z(P),
+                     g_low=z(P), ws=z(max(ops.mh_wgrad_ws_floats(hf, wf, s[1], s[0]) for s in shapes)),
+                     ws64=z(-(-P // ops.MH_REDUCE_CHUNK) * 129, dtype=torch.float64), gen=0)
+            self._mh_train = t
+        return t
+
+    def mh_train_forward(self, params, pts, count, n_max, crop, do_sigmoid=False):
+        """The visibility of the last flow() at the (count) pixels pts (n_max, 2) = (x, y), by an exact-fp32 forward of the
+        MaskHead that keeps its activations: woft_mh_train_conv layers over the whole map on [fmap1 | mh_warped] (the warped target
+        features that flow left), the closing conv, woft_convex_weights_at on the logits.  params: the head's tensors in state-dict
+        order (net.0.weight, net.0.bias, ...), fp32 on the device, read as they are now.
+        -> (vsel (n_max,) with exact zeros at and beyond count, state for mh_train_backward)."""
+        e = self.eng
+        assert e.mask_head and not e.spec.small and mh_train.refusal(e.mh_shapes) is None and 0 < n_max <= ops.HFIT_SINGLE_MAX
+        t = self._mh_train_buffers()
+        t["gen"] += 1
+        ps = [p.detach() for p in params]
+        vsel = torch.zeros(n_max, dtype=torch.float32, device="cuda")
+        mh_train.head_forward(self.f1rows, self.mh_warped.t, self.hf, self.wf, ps[:-1], t["act"], t["out"])
+        torch.add(t["out"], ps[-1].reshape(()), out=t["low"])
+        ops.convex_weights_at(pts, count, n_max, t["low"], self.mask.t, self.hf, self.wf, crop, vsel, do_sigmoid=do_sigmoid)
+        return vsel, dict(gen=t["gen"], pts=pts, count=count, n_max=n_max, crop=crop, do_sigmoid=bool(do_sigmoid),
+                          shapes=[tuple(p.shape) for p in ps], w=[p.clone() for p in ps[2::2]])
+
+    def mh_train_backward(self, state, g_vsel):
+        """Gradients of the head's parameters for the gradient g_vsel (n_max,) of mh_train_forward's result: upsampling adjoint ->
+        closing conv -> per layer the weight gradient (woft_mh_wgrad) and, above the first layer, the data gradient
+        (woft_mh_train_conv with the transposed, flipped filter and the ReLU gate).  Reads the activations the forward left in the
+        plan's training buffers, fmap1, mh_warped and the upsampling mask: it must run before the next mh_train_forward or flow() of
+        this plan.  Deterministic: two calls return equal bytes."""
+        t = self._mh_train
+        if t is None or t["gen"] != state["gen"]:
+            raise RuntimeError("visibility_at(): backward after a later flow or visibility_at() in the same flow plan -- the "
+                               "activations and the upsampling mask it reads are gone")
+        grads = tuple(torch.zeros(s, dtype=torch.float32, device="cuda") for s in state["shapes"])
+        ops.convex_weights_at_bwd(state["pts"], state["count"], state["n_max"], g_vsel, t["low"], self.mask.t, self.hf, self.wf,
+                                  state["crop"], t["g_low"], do_sigmoid=state["do_sigmoid"])
+        mh_train.head_backward(self.f1rows, self.mh_warped.t, self.hf, self.wf, state["w"], t["act"], t["g_low"], t["g"], t["ws"],
+                               t["ws64"], grads)
         return grads

@@ -12,7 +12,7 @@ from timeit import default_timer as timer
 import numpy as np
 import torch
 
-from . import _lib, ops, wh_train
+from . import _lib, mh_train, ops, wh_train
 from .engine import RaftEngine
 
 logger = logging.getLogger(__name__)
@@ -200,6 +200,9 @@ class RAFTWrapper:
         # Parameters made of them at the first request
         self._wh_loaded = {k: v for k, v in state_dict.items() if k.startswith("weight_head.net.")}
         self._wh_params = None
+        # training of the mask head (mask_head_parameters / visibility_at / sync_mask_head), alike
+        self._mh_loaded = {k: v for k, v in state_dict.items() if k.startswith("mask_head.net.")}
+        self._mh_params = None
         # restricted refinement iterations for callers that declare where they read the flow (pin_flow_region + flow_region=True)
         v = getattr(self.C, "flow_region", None)
         self.flow_region_on = (os.environ.get("WOFT_FLOW_REGION", "1") != "0") if (v is None or isinstance(v, type(self.C))) else bool(v)
@@ -306,6 +309,57 @@ class RAFTWrapper:
         plans read head parameters from is rewritten in place and every captured graph is dropped.  Afterwards compute_flow
         returns the bits of a fresh provider built from the original state dict with dict(weight_head_parameters()) merged in."""
         self.engine.repack_weight_head({k: v.detach() for k, v in self.weight_head_parameters().items()})
+
+    # ---- training of the mask head (woft_amd/mh_train.py, DESIGN.md section 21) ----
+    def _mh_trainable(self):
+        """NotImplementedError, naming the reason, unless this provider is a case the training path covers."""
+        eng = self.engine
+        why = (f"raft_type '{self.C.raft_type}' (only 'weighted_masked' has a mask head)" if not self.masked else
+               "the small model (no upsampling mask: its visibility is upsampled bilinearly)" if eng.small else
+               mh_train.refusal(eng.mh_shapes))
+        if why:
+            raise NotImplementedError(f"training of the mask head is not provided for {why}")
+
+    def mask_head_parameters(self):
+        """The MaskHead's parameters as an OrderedDict of fp32 device torch.nn.Parameter (requires_grad=True) under the reference's
+        state-dict names mask_head.net.{0,2,...}.{weight,bias}, initialised from the loaded checkpoint; the same objects at every
+        call.  visibility_at() reads their current values; the inference path (compute_flow) reads its own packed copies, which
+        sync_mask_head() refreshes.  torch.optim takes list(d.values()); dict(d) saves as a state dict."""
+        self._mh_trainable()
+        if self._mh_params is None:
+            self._mh_params = mh_train.make_parameters(self._mh_loaded, self.engine.mh_shapes)
+        return self._mh_params
+
+    def visibility_at(self, pts, count=None, do_sigmoid=False):
+        """After a computed compute_flow(src, dst, ...) of this provider (not after a flow-cache hit): the visibility logit at the
+        pixels pts (n_max, 2) float32 = (x, y) of the un-padded source image (n_max <= 2048), evaluated with the CURRENT values
+        of mask_head_parameters() in exact fp32, whatever the provider's precision -> (n_max,) float32, the logit or (do_sigmoid)
+        its sigmoid; rows at and beyond count (a device int32 scalar, optional) are exact zeros.  With grad enabled and a
+        parameter that requires grad the result carries a graph whose backward accumulates into the parameters' .grad (once
+        differentiable; deterministic); nothing else receives a gradient -- fmap1, the warped fmap2, the upsampling mask and pts
+        are frozen.  backward() must run before the next compute_flow / visibility_at of this provider: it reads the plan's
+        buffers."""
+        self._mh_trainable()
+        if self._last.wh is None:
+            raise RuntimeError("visibility_at(): no computed flow to evaluate the head on (none yet, or the last one came from "
+                               "the flow cache)")
+        if not (isinstance(pts, torch.Tensor) and pts.is_cuda and pts.dtype == torch.float32 and pts.dim() == 2
+                and pts.shape[1] == 2 and pts.shape[0] >= 1):
+            raise TypeError("visibility_at(): pts must be a (n_max, 2) float32 device tensor of (x, y) pixels")
+        if pts.shape[0] > ops.HFIT_SINGLE_MAX:
+            raise ValueError(f"visibility_at(): at most {ops.HFIT_SINGLE_MAX} points per call, got {pts.shape[0]}")
+        if count is not None and not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32
+                                      and count.numel() == 1):
+            raise TypeError("visibility_at(): count must be a device int32 scalar")
+        plan, crop = self._last.wh
+        params = self.mask_head_parameters().values()
+        return mh_train.visibility_at(plan, params, pts.detach().contiguous(), count, int(pts.shape[0]), crop, do_sigmoid)
+
+    def sync_mask_head(self):
+        """Push the current values of mask_head_parameters() into the inference path: every packed buffer the engine and its plans
+        read MaskHead parameters from is rewritten in place and every captured graph is dropped.  Afterwards compute_flow returns
+        the bits of a fresh provider built from the original state dict with dict(mask_head_parameters()) merged in."""
+        self.engine.repack_mask_head({k: v.detach() for k, v in self.mask_head_parameters().items()})
 
     # ---- template caching (results-identical: InstanceNorm is per sample, extractor.py:171-190) ----
     def pin_source(self, src_img):

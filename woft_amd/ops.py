@@ -892,6 +892,64 @@ def wh_wgrad(gy, x, cin, n_win, ws, gw, gb):
           "woft_wh_wgrad")
 
 
+# ---- training of the mask head (csrc/mh_train.hip) ----
+MH_TRAIN_TILE = 32                      # WOFT_MH_TRAIN_TILE: positions of a map row per tile
+MH_TRAIN_CHUNK = 16                     # WOFT_MH_TRAIN_CHUNK: tiles per partial sum of a weight gradient
+MH_REDUCE_CHUNK = 256                   # WOFT_MH_REDUCE_CHUNK: pixels per partial sum of the closing conv's gradient
+
+
+def _mh_map(t, n_pix, c):
+    """A map of the training kernels: (rows >= n_pix, channel stride >= c) fp32, contiguous, on the device."""
+    return _f32c(t) and t.dim() == 2 and t.shape[0] >= n_pix and t.shape[1] >= c
+
+
+def _mh_sources(x0, x1, cin, n_pix):
+    """-> the two-source arguments (x0, cs0, x1, cs1, c_split) of an input map of cin channels: x0 alone, or [x0 | x1] with
+    cin / 2 channels each (the first layer's [fmap1 | warped fmap2])."""
+    c_split = cin if x1 is None else cin // 2
+    assert _mh_map(x0, n_pix, c_split) and (x1 is None or _mh_map(x1, n_pix, cin - c_split))
+    return ptr(x0), x0.shape[1], ptr(x1), (0 if x1 is None else x1.shape[1]), c_split
+
+
+def mh_train_conv(x0, x1, wt, hf, wf, y, bias=None, gate=None):
+    """One 3x3 layer over the hf x wf map, zero padding, exact fp32 (woft_mh_train_conv): wt (9, cin, cout), input map x0 (or
+    [x0 | x1], half of cin each), y a map of cout channels; with bias: relu(conv + bias); with gate (a map of cout channels): conv
+    where gate > 0, else 0."""
+    cin, cout = int(wt.shape[1]), int(wt.shape[2])
+    P = hf * wf
+    assert _f32c(wt, 9, cin, cout) and _mh_map(y, P, cout)
+    assert bias is None or _f32c(bias, cout)
+    assert gate is None or _mh_map(gate, P, cout)
+    check(_lib.load().woft_mh_train_conv(*_mh_sources(x0, x1, cin, P), cin, ptr(wt), cout, ptr(bias), ptr(gate),
+                                         0 if gate is None else gate.shape[1], hf, wf, ptr(y), y.shape[1], stream_ptr()),
+          "woft_mh_train_conv")
+
+
+def mh_wgrad_ws_floats(hf, wf, cin, cout):
+    return int(_lib.load().woft_mh_wgrad_ws_bytes(hf, wf, cin, cout)) // 4
+
+
+def mh_wgrad(gy, x0, x1, hf, wf, ws, gw, gb):
+    """Parameter gradient of such a layer (woft_mh_wgrad): gy a map of cout channels, the input map x0 (or [x0 | x1]) -> gw
+    (cout, cin, 3, 3), gb (cout); ws: mh_wgrad_ws_floats(hf, wf, cin, cout) floats."""
+    cout, cin = int(gw.shape[0]), int(gw.shape[1])
+    P = hf * wf
+    assert _f32c(gw, cout, cin, 3, 3) and _f32c(gb, cout) and _mh_map(gy, P, cout)
+    assert _f32c(ws) and ws.numel() >= mh_wgrad_ws_floats(hf, wf, cin, cout)
+    check(_lib.load().woft_mh_wgrad(ptr(gy), gy.shape[1], cout, *_mh_sources(x0, x1, cin, P), cin, hf, wf, ptr(ws), ptr(gw),
+                                    ptr(gb), stream_ptr()), "woft_mh_wgrad")
+
+
+def mh_reduce_bwd(act, c, w, g_low, n_pix, g_act, ws, g_w, g_b):
+    """Backward of the closing 1x1 conv on the n_pix pixels of a map of c channels: g_act (a map), g_w (c), g_b (1); ws: at least
+    ceil(n_pix / MH_REDUCE_CHUNK) * 129 doubles (woft_mh_reduce_bwd)."""
+    assert _mh_map(act, n_pix, c) and _mh_map(g_act, n_pix, c) and _f32c(g_low) and g_low.numel() >= n_pix
+    assert ws.dtype == torch.float64 and ws.is_cuda and ws.numel() >= -(-n_pix // MH_REDUCE_CHUNK) * 129
+    assert _f32c(w) and w.numel() >= c and _f32c(g_w) and g_w.numel() >= c and _f32c(g_b)
+    check(_lib.load().woft_mh_reduce_bwd(ptr(act), act.shape[1], c, ptr(w), ptr(g_low), n_pix, ptr(g_act), g_act.shape[1], ptr(ws),
+                                         ptr(g_w), ptr(g_b), stream_ptr()), "woft_mh_reduce_bwd")
+
+
 def upflow8(coords, wlow, hf, wf, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False):
     check(_lib.load().woft_upflow8(ptr(coords), ptr(wlow), hf, wf, crop[0], crop[1], h, w, ptr(flow_up), ptr(dst),
                                    ptr(wout), int(do_sigmoid), stream_ptr()), "woft_upflow8")

@@ -623,6 +623,23 @@ int woft_mh_wgrad(const float* gy, int32_t gy_cs, int32_t cout, const float* x0,
                   int32_t c_split, int32_t cin, int32_t hf, int32_t wf, float* ws, float* gw, float* gb, void* stream);
 int woft_mh_reduce_bwd(const float* act, int32_t act_cs, int32_t c, const float* w, const float* g_low, int32_t n_pix,
                        float* g_act, int32_t g_cs, double* ws, float* g_w, float* g_b, void* stream);
+/* ---- Dense adjoint of the convex upsampling (weighted_raft.py:92-103, 305-308) -------------------------
+ * woft_convex_upsample_bwd: adjoint of the wout output of woft_convex_upsample with respect to wlow.  g_up [h*w]: the gradient
+ *   of the cropped full-resolution map; mask, ld_mask, hf, wf, the crop window and do_sigmoid as in the forward; g_wlow [hf*wf]
+ *   is written whole:
+ *     g_wlow[q] = sum over the cells n and taps k = ky*3+kx with q = n + (ky-1, kx-1), over the fine positions of n inside the
+ *                 crop window, of ((g_up[pixel] * dsig) / 8) * (softmax_k(mask[n])[position] * 8)
+ *   dsig = 1, or with do_sigmoid v (1 - v), v the forward's sigmoid output at the pixel recomputed from wlow in the forward's
+ *   order of operations (wlow is read only then; else it may be NULL).  Fine positions outside the crop window send nothing;
+ *   neighbours outside the map receive nothing (zero padding); mask columns beyond 576 and rows beyond hf*wf are never read.
+ *   Two launches, the mask read once: part[n][k] = the sum over the 64 positions of cell n by a fixed butterfly (ws:
+ *   woft_convex_upsample_bwd_ws_bytes(hf, wf) = 9 * hf * wf floats), then g_wlow[q] = the partials addressed to q in k order.
+ *   No floating-point atomics: two calls give equal bytes.  WOFT_EINVAL before any launch on a NULL required pointer,
+ *   ld_mask < 576, non-positive sizes, hf * wf >= 2^28, a crop window that leaves the padded map, or do_sigmoid without wlow. */
+int64_t woft_convex_upsample_bwd_ws_bytes(int32_t hf, int32_t wf);
+int woft_convex_upsample_bwd(const float* g_up, const float* mask, int32_t ld_mask, const float* wlow, int32_t hf, int32_t wf,
+                             int32_t crop_top, int32_t crop_left, int32_t h, int32_t w, int32_t do_sigmoid, float* ws,
+                             float* g_wlow, void* stream);
 /* Pre-computed flow read from the reference's cache files (utils/caching.py:53-59; raft.py:93-106) to the same
  * outputs: dst[2][h*w] = pixel grid + flow[2][h*w] (may be NULL), wout[h*w] = weights or sigmoid(weights)
  * (weights / wout may be NULL). */

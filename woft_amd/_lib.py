@@ -117,6 +117,8 @@ _SIGS = {
     "woft_mh_wgrad_ws_bytes": (i64, [i32, i32, i32, i32]),
     "woft_mh_wgrad": (i32, [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "woft_mh_reduce_bwd": (i32, [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+    "woft_convex_upsample_bwd_ws_bytes": (i64, [i32, i32]),
+    "woft_convex_upsample_bwd": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "woft_upflow8": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "woft_warp_perspective_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), vp, vp, i32, vp]),
     "woft_resize_linear_u8": (i32, [vp, i32, i32, i32, vp, i32, i32, f32, f32, vp]),

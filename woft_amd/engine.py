@@ -1178,7 +1178,7 @@ class _Plan:
             raise ValueError("iters must be >= 1")
         if self._wh_train is not None:                       # (a weights_at() graph of an earlier flow in this plan is stale now: its
             self._wh_train["gen"] += 1                       #  backward would read this flow's upsampling mask -- it raises instead)
-        if self._mh_train is not None:                       # (a visibility_at() graph alike)
+        if self._mh_train is not None:                       # (a visibility_at() / visibility_map() graph alike)
             self._mh_train["gen"] += 1
         if flow_init is not None and flow_init is not True:
             self.set_flow_init(flow_init)                    # (a captured graph reads the plan's buffer: the copy stays outside)
@@ -1420,15 +1420,36 @@ class _Plan:
         """Buffers of the training path, sized by the map (P pixels) and the head, allocated at the first use: one activation
         map per layer, two gradient maps as wide as the widest layer, the 1/8-resolution logits and their gradient, the partial
         sums of the widest weight gradient (ceil(hf * ceil(wf / 32) / 16) partials of 9 * C * cin + C floats) and of the closing
-        conv (ceil(P / 256) * 129 doubles).  None of them is read by flow()."""
+        conv (ceil(P / 256) * 129 doubles), the 9 P partial sums of the dense upsampling adjoint.  None of them is read by flow()."""
         t = self._mh_train
         if t is None:
             z, P, hf, wf = self._z, self.P, self.hf, self.wf
             shapes = self.eng.mh_shapes[:-1]
             t = dict(act=[z(P, s[0]) for s in shapes], g=[z(P, max(s[0] for s in shapes)) for _ in range(2)], out=z(P), low=z(P),
                      g_low=z(P), ws=z(max(ops.mh_wgrad_ws_floats(hf, wf, s[1], s[0]) for s in shapes)),
-                     ws64=z(-(-P // ops.MH_REDUCE_CHUNK) * 129, dtype=torch.float64), gen=0)
+                     ws64=z(-(-P // ops.MH_REDUCE_CHUNK) * 129, dtype=torch.float64),
+                     up=z(ops.convex_upsample_bwd_ws_floats(hf, wf)), gen=0)
             self._mh_train = t
+        return t
+
+    def _mh_head_forward(self, params):
+        """The head part both training forwards share: a new generation of the training buffers, the exact-fp32 head on
+        [fmap1 | mh_warped] into t["act"], t["out"] and, with the closing bias, t["low"] -> (t, the detached parameters)."""
+        e = self.eng
+        assert e.mask_head and not e.spec.small and mh_train.refusal(e.mh_shapes) is None
+        t = self._mh_train_buffers()
+        t["gen"] += 1
+        ps = [p.detach() for p in params]
+        mh_train.head_forward(self.f1rows, self.mh_warped.t, self.hf, self.wf, ps[:-1], t["act"], t["out"])
+        torch.add(t["out"], ps[-1].reshape(()), out=t["low"])
+        return t, ps
+
+    def _mh_live(self, state, what):
+        """The training buffers if they still hold the forward that made `state`, else the stale-graph error."""
+        t = self._mh_train
+        if t is None or t["gen"] != state["gen"]:
+            raise RuntimeError(f"{what}(): backward after a later flow, visibility_at() or visibility_map() in the same flow plan "
+                               "-- the activations and the upsampling mask it reads are gone")
         return t
 
     def mh_train_forward(self, params, pts, count, n_max, crop, do_sigmoid=False):
@@ -1437,14 +1458,9 @@ class _Plan:
         features that flow left), the closing conv, woft_convex_weights_at on the logits.  params: the head's tensors in state-dict
         order (net.0.weight, net.0.bias, ...), fp32 on the device, read as they are now.
         -> (vsel (n_max,) with exact zeros at and beyond count, state for mh_train_backward)."""
-        e = self.eng
-        assert e.mask_head and not e.spec.small and mh_train.refusal(e.mh_shapes) is None and 0 < n_max <= ops.HFIT_SINGLE_MAX
-        t = self._mh_train_buffers()
-        t["gen"] += 1
-        ps = [p.detach() for p in params]
+        assert 0 < n_max <= ops.HFIT_SINGLE_MAX
+        t, ps = self._mh_head_forward(params)
         vsel = torch.zeros(n_max, dtype=torch.float32, device="cuda")
-        mh_train.head_forward(self.f1rows, self.mh_warped.t, self.hf, self.wf, ps[:-1], t["act"], t["out"])
-        torch.add(t["out"], ps[-1].reshape(()), out=t["low"])
         ops.convex_weights_at(pts, count, n_max, t["low"], self.mask.t, self.hf, self.wf, crop, vsel, do_sigmoid=do_sigmoid)
         return vsel, dict(gen=t["gen"], pts=pts, count=count, n_max=n_max, crop=crop, do_sigmoid=bool(do_sigmoid),
                           shapes=[tuple(p.shape) for p in ps], w=[p.clone() for p in ps[2::2]])
@@ -1455,13 +1471,33 @@ class _Plan:
         (woft_mh_train_conv with the transposed, flipped filter and the ReLU gate).  Reads the activations the forward left in the
         plan's training buffers, fmap1, mh_warped and the upsampling mask: it must run before the next mh_train_forward or flow() of
         this plan.  Deterministic: two calls return equal bytes."""
-        t = self._mh_train
-        if t is None or t["gen"] != state["gen"]:
-            raise RuntimeError("visibility_at(): backward after a later flow or visibility_at() in the same flow plan -- the "
-                               "activations and the upsampling mask it reads are gone")
+        t = self._mh_live(state, "visibility_at")
         grads = tuple(torch.zeros(s, dtype=torch.float32, device="cuda") for s in state["shapes"])
         ops.convex_weights_at_bwd(state["pts"], state["count"], state["n_max"], g_vsel, t["low"], self.mask.t, self.hf, self.wf,
                                   state["crop"], t["g_low"], do_sigmoid=state["do_sigmoid"])
+        mh_train.head_backward(self.f1rows, self.mh_warped.t, self.hf, self.wf, state["w"], t["act"], t["g_low"], t["g"], t["ws"],
+                               t["ws64"], grads)
+        return grads
+
+    def mh_dense_forward(self, params, crop, h, w, do_sigmoid=False):
+        """The visibility of the last flow() at every pixel of the (h, w) crop window: the head as in mh_train_forward, then the
+        inference path's own woft_convex_upsample on the logits (its weight output alone) -- at a pixel the bytes mh_train_forward
+        returns there.  -> (map (h, w), a fresh tensor; state for mh_dense_backward)."""
+        t, ps = self._mh_head_forward(params)
+        out = torch.empty(h, w, dtype=torch.float32, device="cuda")
+        ops.convex_upsample(self.coords, t["low"], self.mask.t, self.hf, self.wf, crop, h, w, wout=out, do_sigmoid=do_sigmoid)
+        return out, dict(gen=t["gen"], crop=crop, size=(h, w), do_sigmoid=bool(do_sigmoid), shapes=[tuple(p.shape) for p in ps],
+                         w=[p.clone() for p in ps[2::2]])
+
+    def mh_dense_backward(self, state, g_map):
+        """Gradients of the head's parameters for the gradient g_map (h, w) of mh_dense_forward's result: the dense upsampling
+        adjoint (woft_convex_upsample_bwd: the mask read once, 9 P partials) -> t["g_low"], then mh_train_backward's head part.  The
+        same conditions: before the next training forward or flow() of this plan; two calls return equal bytes."""
+        t = self._mh_live(state, "visibility_map")
+        grads = tuple(torch.zeros(s, dtype=torch.float32, device="cuda") for s in state["shapes"])
+        h, w = state["size"]
+        ops.convex_upsample_bwd(g_map, self.mask.t, t["low"], self.hf, self.wf, state["crop"], h, w, t["up"], t["g_low"],
+                                do_sigmoid=state["do_sigmoid"])
         mh_train.head_backward(self.f1rows, self.mh_warped.t, self.hf, self.wf, state["w"], t["act"], t["g_low"], t["g"], t["ws"],
                                t["ws64"], grads)
         return grads

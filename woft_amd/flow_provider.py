@@ -106,6 +106,7 @@ class _LastFlow:
     def __init__(self, low_plan=None):
         self.low_plan = low_plan   # flow_low(): the plan of the last COMPUTED flow (a cache hit since then leaves it)
         self.wh = None             # weights_at(): (plan, crop) of this call's computed flow
+        self.size = None           # visibility_map(): (H, W) of that flow's un-padded outputs
         self.flow_map = None       # flow_map(): the (2, H, W) buffer this call wrote, if it wrote one
         self.deferred = None       # finish_weights(): (plan, crop, oh, ow, outputs, do_sigmoid) while weights are deferred
 
@@ -354,6 +355,22 @@ class RAFTWrapper:
         plan, crop = self._last.wh
         params = self.mask_head_parameters().values()
         return mh_train.visibility_at(plan, params, pts.detach().contiguous(), count, int(pts.shape[0]), crop, do_sigmoid)
+
+    def visibility_map(self, do_sigmoid=False):
+        """The dense form of visibility_at(), for supervision by a dense occlusion mask: after a computed compute_flow(src, dst,
+        ...) of this provider (not after a flow-cache hit), the visibility logit -- or (do_sigmoid) its sigmoid -- at every pixel
+        of the un-padded source image -> (H, W) float32 on the device, a fresh tensor; at a pixel it has the bytes visibility_at()
+        returns there.  Evaluated with the CURRENT values of mask_head_parameters() in exact fp32, whatever the provider's
+        precision.  With grad enabled and a parameter that requires grad the result carries a graph whose backward accumulates
+        into the parameters' .grad (once differentiable; deterministic); nothing else receives a gradient.  backward() must run
+        before the next compute_flow / visibility_at / visibility_map of this provider: it reads the plan's buffers."""
+        self._mh_trainable()
+        if self._last.wh is None:
+            raise RuntimeError("visibility_map(): no computed flow to evaluate the head on (none yet, or the last one came from "
+                               "the flow cache)")
+        plan, crop = self._last.wh
+        h, w = self._last.size
+        return mh_train.visibility_map(plan, self.mask_head_parameters().values(), crop, h, w, do_sigmoid)
 
     def sync_mask_head(self):
         """Push the current values of mask_head_parameters() into the inference path: every packed buffer the engine and its plans
@@ -724,7 +741,7 @@ class RAFTWrapper:
                                      and plan.wh_region is not None
                                      and mode == "TC" and not numpy_out
                                      and int(plan.wh_region[0].numel()) > self.defer_min_ratio * int(defer_weights))
-        self._last.wh = (plan, (top, left))
+        self._last.wh, self._last.size = (plan, (top, left)), (oh, ow)
         self._last.deferred = (plan, (top, left), oh, ow, o, bool(do_sigmoid)) if self.weights_deferred else None
         want_flow = mode == "flow" or bool(keep_flow)      # (mode "TC" hands out dst = grid + flow only: no (2, H, W) flow map)
         plan.flow(n_iters, (top, left), oh, ow, flow_up=o["flow"] if want_flow else None, dst=o["dst"],

@@ -1,9 +1,10 @@
-"""Training of the visibility MaskHead on HIP: the autograd node behind RAFTWrapper.visibility_at().
+"""Training of the visibility MaskHead on HIP (DESIGN.md sections 21, 22): the autograd nodes behind RAFTWrapper.visibility_at()
+and RAFTWrapper.visibility_map().
 
 The exact analogue of wh_train.py for the reference's second head (weighted_raft.py:387-422, raft_type 'weighted_masked'): a frozen
 RAFT and a trainable MaskHead -- 3x3 convs with a ReLU after each over the whole 1/8-resolution map of [fmap1 | warped fmap2]
 (weighted_raft.py:295-304), a closing 1x1 conv, the x8 convex upsampling the weights share (weighted_raft.py:305-308).  This node
-carries the gradient from the visibility at a list of pixels into the head's parameters; it stops at the head's inputs (fmap1, the
+carries the gradient from the visibility at a list of pixels (or, VisibilityMap, at every pixel) into the head's parameters; it stops at the head's inputs (fmap1, the
 warped fmap2, the upsampling mask, the points): RAFT stays frozen.
 """
 from collections import OrderedDict
@@ -102,3 +103,29 @@ def visibility_at(plan, params, pts, count, n_max, crop, do_sigmoid):
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         return VisibilityAt.apply(plan, pts, count, n_max, crop, bool(do_sigmoid), *params)
     return plan.mh_train_forward(params, pts, count, n_max, crop, do_sigmoid)[0]
+
+
+class VisibilityMap(torch.autograd.Function):
+    """The dense form: map = plan.mh_dense_forward(...), the visibility at every pixel of the un-padded
+    image, with a backward into the head's parameters (plan.mh_dense_backward: the dense adjoint of the convex upsampling, then
+    the same head backward).  Once differentiable; nothing but the parameters gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, plan, crop, h, w, do_sigmoid, *params):
+        out, state = plan.mh_dense_forward(params, crop, h, w, do_sigmoid)
+        ctx.plan, ctx.state = plan, state
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        grads = ctx.plan.mh_dense_backward(ctx.state, grad_output.to(torch.float32).contiguous())
+        need = ctx.needs_input_grad[5:]
+        return (None,) * 5 + tuple(g if n else None for g, n in zip(grads, need))
+
+
+def visibility_map(plan, params, crop, h, w, do_sigmoid):
+    params = tuple(params)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return VisibilityMap.apply(plan, crop, h, w, bool(do_sigmoid), *params)
+    return plan.mh_dense_forward(params, crop, h, w, do_sigmoid)[0]

@@ -950,6 +950,24 @@ def mh_reduce_bwd(act, c, w, g_low, n_pix, g_act, ws, g_w, g_b):
                                          ptr(g_w), ptr(g_b), stream_ptr()), "woft_mh_reduce_bwd")
 
 
+# ---- dense adjoint of the convex upsampling (csrc/upsample_bwd.hip) ----
+def convex_upsample_bwd_ws_floats(hf, wf):
+    return int(_lib.load().woft_convex_upsample_bwd_ws_bytes(hf, wf)) // 4
+
+
+def convex_upsample_bwd(g_up, mask, wlow, hf, wf, crop, h, w, ws, g_wlow, do_sigmoid=False):
+    """g_wlow (hf * wf floats, written whole) = the gradient of convex_upsample's wout (h * w, cropped at `crop`) with respect to
+    wlow for the upstream gradient g_up (h * w floats): woft_convex_upsample_bwd.  mask: (rows >= hf * wf, ld >= 576); wlow is
+    read only with do_sigmoid (else it may be None); ws: convex_upsample_bwd_ws_floats(hf, wf) floats."""
+    P = hf * wf
+    assert _f32c(g_up) and g_up.numel() == h * w and _f32c(g_wlow) and g_wlow.numel() == P
+    assert _f32c(mask) and mask.dim() == 2 and mask.shape[0] >= P and mask.shape[1] >= 576
+    assert wlow is None or (_f32c(wlow) and wlow.numel() >= P)
+    assert _f32c(ws) and ws.numel() >= convex_upsample_bwd_ws_floats(hf, wf)
+    check(_lib.load().woft_convex_upsample_bwd(ptr(g_up), ptr(mask), mask.shape[1], ptr(wlow), hf, wf, crop[0], crop[1], h, w,
+                                               int(do_sigmoid), ptr(ws), ptr(g_wlow), stream_ptr()), "woft_convex_upsample_bwd")
+
+
 def upflow8(coords, wlow, hf, wf, crop, h, w, flow_up=None, dst=None, wout=None, do_sigmoid=False):
     check(_lib.load().woft_upflow8(ptr(coords), ptr(wlow), hf, wf, crop[0], crop[1], h, w, ptr(flow_up), ptr(dst),
                                    ptr(wout), int(do_sigmoid), stream_ptr()), "woft_upflow8")

@@ -26,8 +26,8 @@ extern "C" {
 
 /* ABI / build identification: returns 10000*major + 100*minor + patch. */
 int woft_abi_version(void);
-/* sizeof(woft_conv_params) (which = 0) / woft_lookup_params (1) / woft_lookup_otf_params (2) / woft_lookup_band_params (3):
-   layout check for FFI mirrors. */
+/* sizeof(woft_conv_params) (which = 0) / woft_lookup_params (1) / woft_lookup_otf_params (2) / woft_lookup_band_params (3) /
+   woft_hsynth_occluder (4): layout check for FFI mirrors. */
 int woft_sizeof(int which);
 /* developer knob for the micro-benchmarks in tools/ (ablation bits of the correlation GEMM, key 2); 0 in production. */
 int woft_set_tuning(int key, int value);
@@ -677,6 +677,42 @@ int woft_crop_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, int32_t y0
 int64_t woft_mask_bbox_ws_bytes(void);
 int woft_mask_bbox(const uint8_t* mask, int32_t h, int32_t w, const double* hinv, uint8_t* warped, void* ws, int32_t* bbox,
                    void* stream);
+
+/* ---- Synthetic-homography training pairs (csrc/hsynth.hip) ------------------------------------------------
+ * This project's own semantics for what the reference's training configs call COCOHSynth (an image, the same image through a known
+ * homography, with occluders); the data set's code is not part of the reference.  An occluder is a BGRA texture and the inverse
+ * homography that maps the destination frame to that texture.  The array of occluders and its hinv live on the HOST (copied by
+ * value); tex is a device pointer, 4-byte aligned (one pixel is read as one dword). */
+#define WOFT_HSYNTH_MAX_OCC 4
+typedef struct {
+    const uint8_t* tex; /* (ho, wo, 4) B, G, R, alpha */
+    int32_t ho, wo;
+    int32_t pad_;
+    double hinv[9];
+} woft_hsynth_occluder;
+/* woft_hsynth_render: destination pixel (x, y) of the (h, w) frame, channel c:
+ *   1. v_c = base ((hs, ws, 3) uint8) at hinv (x, y, 1): the source coordinates, fp64 de-homogenisation, bilinear taps, zero
+ *      border and float operations of woft_warp_perspective_u8 before its rounding (one device function, csrc/warp_pixel.h);
+ *   2. v_c = gain[c] * v_c + bias[c], a multiply and then an add (gain, bias: 3 floats on the HOST; NULL = 1 / 0);
+ *   3. for k = 0 .. n_occ-1 in order, premultiplied compositing: with m the in-texture flag of a tap of occ[k].hinv (x, y, 1),
+ *      A_k = bilinear(m * (alpha_tap / 255)), O_kc = bilinear((m * (alpha_tap / 255)) * colour_tap), v_c = (1 - A_k) * v_c + O_kc;
+ *   4. out_u8 (h, w, 3) = (uint8) clamp(rintf(v_c), 0, 255); out_f32 (h, w, 3; may be NULL) = v_c; cover (h, w; may be NULL) =
+ *      1 - prod_k (1 - A_k).
+ * woft_hsynth_labels: template pixel (x, y) of the (hs, ws) base image: (px, py) = hfwd (x, y, 1) de-homogenised in fp64 with
+ *   denominator d; flow (2, hs, ws) = ((float)(px - x), (float)(py - y)), written everywhere; inside = d > 0 && 0 <= px <= w-1 &&
+ *   0 <= py <= h-1; T = 1 - prod_k (1 - A_k) with A_k of step 3 at occ[k].hinv (px, py, 1) (the alpha field the render composites,
+ *   at the non-integer point); visible (hs, ws) = 1 iff inside && T <= lo; valid (hs, ws; uint8 0 / 1) = 0 iff inside && lo < T < hi
+ *   (an occluder's soft edge, or a T that is NaN), where visible = 0 too.
+ * One launch each, a thread per four adjacent pixels (dword stores when the outputs are 4- / 16-byte aligned, byte and float
+ * stores otherwise: the same values); no atomics, no workspace: two calls give equal bytes.  WOFT_EINVAL before any launch on a
+ * NULL required pointer (base, hinv, out_u8; hfwd, flow, visible, valid), non-positive sizes, n_occ outside
+ * 0 .. WOFT_HSYNTH_MAX_OCC, n_occ > 0 with occ == NULL, an occluder with a NULL or misaligned texture or a non-positive size,
+ * !(0 <= lo < hi <= 1), hs * ws or h * w at or above 2^31. */
+int woft_hsynth_render(const uint8_t* base, int32_t hs, int32_t ws, const double* hinv, const float* gain, const float* bias,
+                       const woft_hsynth_occluder* occ, int32_t n_occ, uint8_t* out_u8, float* out_f32, float* cover, int32_t h,
+                       int32_t w, void* stream);
+int woft_hsynth_labels(int32_t hs, int32_t ws, const double* hfwd, const woft_hsynth_occluder* occ, int32_t n_occ, int32_t h,
+                       int32_t w, float lo, float hi, float* flow, float* visible, uint8_t* valid, void* stream);
 
 /* cv2.resize(img, None, fx, fy) with INTER_LINEAR geometry (tracker/YAOF_tracker_single_control.py:27-30,60-61,
  * `downscale_inputs`): src = (dst + 0.5) * scale - 0.5, edge clamped; scale = 1 / fx. */

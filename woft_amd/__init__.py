@@ -12,6 +12,9 @@ def __getattr__(name):
     if name in ("chain_correspondences", "WOFTChained"):
         from .chained import WOFTChained, chain_correspondences
         return chain_correspondences if name == "chain_correspondences" else WOFTChained
+    if name in ("HSynth", "HSynthSample", "render_pair", "pair_labels", "random_homography", "make_occluder"):
+        from . import hsynth
+        return getattr(hsynth, name)
     if name == "FrameFeatures":
         from .flow_provider import FrameFeatures
         return FrameFeatures

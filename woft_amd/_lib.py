@@ -62,6 +62,11 @@ class LookupBandParams(C.Structure):
     _fields_ = LookupOtfParams._fields_ + [("band", vp), ("miss", vp), ("miss_count", vp), ("defer_samples", i32)]
 
 
+class HSynthOccluder(C.Structure):
+    # woft_hsynth_occluder: a BGRA texture (device) and the inverse homography destination frame -> texture (host, by value)
+    _fields_ = [("tex", vp), ("ho", i32), ("wo", i32), ("pad_", i32), ("hinv", C.c_double * 9)]
+
+
 _SIGS = {
     "woft_abi_version": (i32, []),
     "woft_sizeof": (i32, [i32]),
@@ -121,6 +126,9 @@ _SIGS = {
     "woft_convex_upsample_bwd": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "woft_upflow8": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "woft_warp_perspective_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), vp, vp, i32, vp]),
+    "woft_hsynth_render": (i32, [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(f32), C.POINTER(f32), C.POINTER(HSynthOccluder), i32,
+                                 vp, vp, vp, i32, i32, vp]),
+    "woft_hsynth_labels": (i32, [i32, i32, C.POINTER(C.c_double), C.POINTER(HSynthOccluder), i32, i32, i32, f32, f32, vp, vp, vp, vp]),
     "woft_resize_linear_u8": (i32, [vp, i32, i32, i32, vp, i32, i32, f32, f32, vp]),
     "woft_warp_perspective_window_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), i32, i32, i32, i32, vp, vp, i32, vp]),
     "woft_crop_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
@@ -164,7 +172,8 @@ def load():
         fn = getattr(lib, name)           # AttributeError if a declared symbol is not exported
         fn.restype, fn.argtypes = res, args
     if lib.woft_sizeof(0) != C.sizeof(ConvParams) or lib.woft_sizeof(1) != C.sizeof(LookupParams) \
-            or lib.woft_sizeof(2) != C.sizeof(LookupOtfParams) or lib.woft_sizeof(3) != C.sizeof(LookupBandParams):
+            or lib.woft_sizeof(2) != C.sizeof(LookupOtfParams) or lib.woft_sizeof(3) != C.sizeof(LookupBandParams) \
+            or lib.woft_sizeof(4) != C.sizeof(HSynthOccluder):
         raise WoftHipError("ctypes mirror of woft_conv_params / woft_lookup_params is out of sync with the library")
     _lib = lib
     return lib

@@ -327,6 +327,7 @@ extern "C" int woft_sizeof(int which) {
     if (which == 1) return (int)sizeof(woft_lookup_params);
     if (which == 2) return (int)sizeof(woft_lookup_otf_params);
     if (which == 3) return (int)sizeof(woft_lookup_band_params);
+    if (which == 4) return (int)sizeof(woft_hsynth_occluder);
     return -1;
 }
 

@@ -5,11 +5,51 @@
 
 struct H9 { double v[9]; };
 
-// Source coordinates of destination pixel (x, y): Hinv (x, y, 1), de-homogenised, in fp64.
-__device__ __forceinline__ void warp_source(const H9& hi, int x, int y, double& sx, double& sy) {
+// Source coordinates of the destination point (x, y): Hinv (x, y, 1), de-homogenised, in fp64; -> the denominator.  (A pixel's
+// integer coordinates convert to double exactly, so the full-frame kernels and the callers with a non-integer point share this.)
+__device__ __forceinline__ double warp_source(const H9& hi, double x, double y, double& sx, double& sy) {
     const double d = hi.v[6] * x + hi.v[7] * y + hi.v[8];
     sx = (hi.v[0] * x + hi.v[1] * y + hi.v[2]) / d;
     sy = (hi.v[3] * x + hi.v[4] * y + hi.v[5]) / d;
+    return d;
+}
+
+// The four bilinear taps of source point (sx, sy) in an h x w image: fractions, in-image flags (zero border) and clamped indices.
+struct WarpTaps {
+    float fx, fy, m00, m01, m10, m11;
+    int cx0, cx1, cy0, cy1;
+};
+
+__device__ __forceinline__ WarpTaps warp_taps(int h, int w, double sx, double sy) {
+    WarpTaps t;
+    double fx0 = floor(sx), fy0 = floor(sy);
+    t.fx = (float)(sx - fx0);
+    t.fy = (float)(sy - fy0);
+    fx0 = fmin(fmax(fx0, -4.0), (double)w + 4.0);
+    fy0 = fmin(fmax(fy0, -4.0), (double)h + 4.0);
+    const int x0 = (int)fx0, y0 = (int)fy0;
+    const bool okx0 = x0 >= 0 && x0 < w, okx1 = x0 + 1 >= 0 && x0 + 1 < w;
+    const bool oky0 = y0 >= 0 && y0 < h, oky1 = y0 + 1 >= 0 && y0 + 1 < h;
+    t.m00 = (okx0 && oky0) ? 1.f : 0.f, t.m01 = (okx1 && oky0) ? 1.f : 0.f;
+    t.m10 = (okx0 && oky1) ? 1.f : 0.f, t.m11 = (okx1 && oky1) ? 1.f : 0.f;
+    t.cx0 = min(max(x0, 0), w - 1), t.cx1 = min(max(x0 + 1, 0), w - 1);
+    t.cy0 = min(max(y0, 0), h - 1), t.cy1 = min(max(y0 + 1, 0), h - 1);
+    return t;
+}
+
+// Bilinear combination of four tap values (already multiplied by their flags), un-rounded.
+__device__ __forceinline__ float warp_blend(const WarpTaps& t, float t00, float t01, float t10, float t11) {
+    const float top = t00 * (1.f - t.fx) + t01 * t.fx, bot = t10 * (1.f - t.fx) + t11 * t.fx;
+    return top * (1.f - t.fy) + bot * t.fy;
+}
+
+// Channel k of a c-channel uint8 image at source point taps t, un-rounded (what warp_pixel rounds).
+__device__ __forceinline__ float warp_sample(const uint8_t* __restrict__ img, int w, int c, const WarpTaps& t, int k) {
+    const float t00 = t.m00 * (float)img[((int64_t)t.cy0 * w + t.cx0) * c + k];
+    const float t01 = t.m01 * (float)img[((int64_t)t.cy0 * w + t.cx1) * c + k];
+    const float t10 = t.m10 * (float)img[((int64_t)t.cy1 * w + t.cx0) * c + k];
+    const float t11 = t.m11 * (float)img[((int64_t)t.cy1 * w + t.cx1) * c + k];
+    return warp_blend(t, t00, t01, t10, t11);
 }
 
 // Nearest-neighbour source pixel of (x, y): -1 outside the h x w image, else its index y * w + x.
@@ -34,30 +74,9 @@ __device__ __forceinline__ void warp_pixel(const uint8_t* __restrict__ img, int 
     }
     double sx, sy;
     warp_source(hi, x, y, sx, sy);
-    double fx0 = floor(sx), fy0 = floor(sy);
-    const float fx = (float)(sx - fx0), fy = (float)(sy - fy0);
-    fx0 = fmin(fmax(fx0, -4.0), (double)w + 4.0);
-    fy0 = fmin(fmax(fy0, -4.0), (double)h + 4.0);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const bool okx0 = x0 >= 0 && x0 < w, okx1 = x0 + 1 >= 0 && x0 + 1 < w;
-    const bool oky0 = y0 >= 0 && y0 < h, oky1 = y0 + 1 >= 0 && y0 + 1 < h;
-    const float m00 = (okx0 && oky0) ? 1.f : 0.f, m01 = (okx1 && oky0) ? 1.f : 0.f;
-    const float m10 = (okx0 && oky1) ? 1.f : 0.f, m11 = (okx1 && oky1) ? 1.f : 0.f;
-    const int cx0 = min(max(x0, 0), w - 1), cx1 = min(max(x0 + 1, 0), w - 1);
-    const int cy0 = min(max(y0, 0), h - 1), cy1 = min(max(y0 + 1, 0), h - 1);
+    const WarpTaps t = warp_taps(h, w, sx, sy);
     if (out != nullptr) {
-        for (int k = 0; k < c; ++k) {
-            const float t00 = m00 * (float)img[((int64_t)cy0 * w + cx0) * c + k];
-            const float t01 = m01 * (float)img[((int64_t)cy0 * w + cx1) * c + k];
-            const float t10 = m10 * (float)img[((int64_t)cy1 * w + cx0) * c + k];
-            const float t11 = m11 * (float)img[((int64_t)cy1 * w + cx1) * c + k];
-            const float top = t00 * (1.f - fx) + t01 * fx, bot = t10 * (1.f - fx) + t11 * fx;
-            const float v = top * (1.f - fy) + bot * fy;
-            out[o * c + k] = (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f);
-        }
+        for (int k = 0; k < c; ++k) out[o * c + k] = (uint8_t)fminf(fmaxf(rintf(warp_sample(img, w, c, t, k)), 0.f), 255.f);
     }
-    if (valid != nullptr) {
-        const float top = m00 * (1.f - fx) + m01 * fx, bot = m10 * (1.f - fx) + m11 * fx;
-        valid[o] = (top * (1.f - fy) + bot * fy) > 0.f ? 1 : 0;
-    }
+    if (valid != nullptr) valid[o] = warp_blend(t, t.m00, t.m01, t.m10, t.m11) > 0.f ? 1 : 0;
 }

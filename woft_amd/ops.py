@@ -986,6 +986,40 @@ def _hinv9(Hmat):
     return (C.c_double * 9)(*np.linalg.inv(np.asarray(Hmat, dtype=np.float64)).ravel().tolist())
 
 
+def _hsynth_occluders(occluders):
+    """[(tex (ho, wo, 4) uint8 device tensor, H_occ 3x3 texture -> destination)] -> (ctypes array or None, n); the caller keeps
+    `occluders` alive until the launch is enqueued."""
+    n = len(occluders)
+    if n == 0:
+        return None, 0
+    arr = (_lib.HSynthOccluder * n)()
+    for k, (tex, H_occ) in enumerate(occluders):
+        arr[k].tex, arr[k].ho, arr[k].wo = ptr(tex), tex.shape[0], tex.shape[1]
+        arr[k].hinv[:] = np.linalg.inv(np.asarray(H_occ, dtype=np.float64)).ravel().tolist()
+    return arr, n
+
+
+def hsynth_render(base, Hmat, occluders, gain, bias, out_u8, out_f32=None, cover=None):
+    """woft_hsynth_render: out_u8 (h, w, 3) = base (hs, ws, 3) seen through Hmat (base -> destination), times gain plus bias
+    (3 floats each or None), under the occluders in order; out_f32 / cover as the header says.  Inversions in fp64 on the host."""
+    hs, ws = base.shape[:2]
+    h, w = out_u8.shape[:2]
+    occ, n = _hsynth_occluders(occluders)
+    g = None if gain is None else (C.c_float * 3)(*[float(v) for v in gain])
+    b = None if bias is None else (C.c_float * 3)(*[float(v) for v in bias])
+    check(_lib.load().woft_hsynth_render(ptr(base), hs, ws, _hinv9(Hmat), g, b, occ, n, ptr(out_u8), ptr(out_f32), ptr(cover),
+                                         h, w, stream_ptr()), "woft_hsynth_render")
+
+
+def hsynth_labels(src_hw, Hmat, occluders, out_hw, lo, hi, flow, visible, valid):
+    """woft_hsynth_labels: flow (2, hs, ws) float32, visible (hs, ws) float32, valid (hs, ws) bool / uint8 of the template pixels
+    under Hmat (base -> destination) and the occluders."""
+    occ, n = _hsynth_occluders(occluders)
+    hf = (C.c_double * 9)(*np.asarray(Hmat, dtype=np.float64).ravel().tolist())
+    check(_lib.load().woft_hsynth_labels(src_hw[0], src_hw[1], hf, occ, n, out_hw[0], out_hw[1], lo, hi, ptr(flow), ptr(visible),
+                                         ptr(valid), stream_ptr()), "woft_hsynth_labels")
+
+
 def warp_perspective_window_u8(img, Hmat, rect, out=None, valid=None, nearest=False):
     """The rectangle rect = (y0, x0, rows, cols) of warp_perspective_u8(img, Hmat, ...) into contiguous (rows, cols[, C]) `out`
     and (rows, cols) `valid`: the same bytes as the full-frame call gives those destination pixels, for the window's work."""

@@ -713,6 +713,42 @@ int woft_hsynth_render(const uint8_t* base, int32_t hs, int32_t ws, const double
                        int32_t w, void* stream);
 int woft_hsynth_labels(int32_t hs, int32_t ws, const double* hfwd, const woft_hsynth_occluder* occ, int32_t n_occ, int32_t h,
                        int32_t w, float lo, float hi, float* flow, float* visible, uint8_t* valid, void* stream);
+/* woft_hsynth_render_bg: woft_hsynth_render with a background behind the warped plane.  bg: (hb, wb, 3)
+ * uint8 on the device; hinv_bg: 9 doubles on the HOST, destination frame -> background image; plane: (h, w) float output, may be
+ * NULL.  Destination pixel (x, y), channel c:
+ *   1. v_c as in step 1 of woft_hsynth_render (the same device function: the zero border already premultiplies it);
+ *   2. P = bilinear(m) of the four taps' in-image flags m with the fractional weights of the colour taps: the plane's coverage,
+ *      built the way an occluder's A_k is built; P = 0 where hinv's denominator is not positive or all four taps are outside;
+ *   3. g_c = bg at hinv_bg (x, y, 1): fp64 de-homogenisation, four bilinear taps with indices CLAMPED to the image (replicate
+ *      border: a background has no holes), the float operations of step 1; g_c = 0 where the denominator is not positive or a
+ *      coordinate is not finite;
+ *   4. v_c = v_c + (1 - P) * g_c: a subtraction, a multiply and an add, in this order;
+ *   5. steps 2 - 4 of woft_hsynth_render (gain / bias, occluders, rounding, cover); plane = P.
+ * The launch shape, the store paths and the guarantees of woft_hsynth_render (no atomics, no workspace, equal bytes on two calls).
+ * WOFT_EINVAL before any launch on bg == NULL (a caller without a background uses woft_hsynth_render), hinv_bg == NULL,
+ * non-positive hb / wb, hb * wb at or above 2^31, and everything woft_hsynth_render rejects. */
+int woft_hsynth_render_bg(const uint8_t* base, int32_t hs, int32_t ws, const double* hinv, const float* gain, const float* bias,
+                          const woft_hsynth_occluder* occ, int32_t n_occ, const uint8_t* bg, int32_t hb, int32_t wb,
+                          const double* hinv_bg, uint8_t* out_u8, float* out_f32, float* cover, float* plane, int32_t h, int32_t w,
+                          void* stream);
+/* woft_hsynth_augment (csrc/hsynth_aug.hip): photometric augmentation of a float frame in_f32 (h, w, 3), one
+ * launch.  Pixel (x, y), channel c (memory order B, G, R); all arithmetic fp32, every product followed by its add:
+ *   a. blur, separable with replicate border, 0 <= radius <= WOFT_HSYNTH_MAX_BLUR: t_c(x, y) = sum_{j=-r..r} taps[j+r] *
+ *      (sum_{i=-r..r} taps[i+r] * in_c(clamp(x+i), clamp(y+j))), both sums in ascending index order starting from 0.f; taps:
+ *      2 radius + 1 floats on the HOST (NULL with radius 0: t = in, no LDS touched);
+ *   b. colour: u_c = o_c + M_c0 * t_0 + M_c1 * t_1 + M_c2 * t_2 in that order; colour: 12 floats on the HOST, the 3x3 M row-major
+ *      and then o (NULL = identity: u = t);
+ *   c. noise, skipped when noise_sigma == 0: u_c += noise_sigma * z with idx = (uint32)((y * w + x) * 3 + c),
+ *      mix(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16,  a = mix(seed ^ mix(idx)),
+ *      b = mix(a + 0x9e3779b9), S = the sum of the four 16-bit halves of a and b, z = (float)(S - 131070) * (float)(sqrt(3) / 65536)
+ *      (a sum of four uniforms, unit variance, |z| <= 3.47; a stateless function of seed, pixel and channel);
+ *   d. out_f32 (h, w, 3; may be NULL) = u_c; out_u8 (h, w, 3) = (uint8) clamp(rintf(u_c), 0, 255).
+ * No atomics, no workspace: two calls give equal bytes.  in_f32 may equal out_f32 only when radius == 0.  WOFT_EINVAL before any
+ * launch on a NULL in_f32 / out_u8, non-positive sizes, h * w at or above 2^31, a radius outside 0 .. WOFT_HSYNTH_MAX_BLUR,
+ * radius > 0 with taps == NULL or with in_f32 == out_f32, a negative or non-finite noise_sigma. */
+#define WOFT_HSYNTH_MAX_BLUR 7
+int woft_hsynth_augment(const float* in_f32, int32_t h, int32_t w, const float* taps, int32_t radius, const float* colour,
+                        float noise_sigma, uint32_t seed, uint8_t* out_u8, float* out_f32, void* stream);
 
 /* cv2.resize(img, None, fx, fy) with INTER_LINEAR geometry (tracker/YAOF_tracker_single_control.py:27-30,60-61,
  * `downscale_inputs`): src = (dst + 0.5) * scale - 0.5, edge clamped; scale = 1 / fx. */

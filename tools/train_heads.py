@@ -8,7 +8,10 @@ as a command.  Not a trainer framework: one process, one device, batch size one,
                  torch_reproj_errors(H_gt, H, pts) clamped at the configs' max_loss       (raft_type 'weighted')
 
 Images: files given on the command line (.npy arrays of (H, W, 3) uint8 BGR; this project reads no image format), cropped to a
-multiple of 8, or --textures N synth.make_template textures of --size.  --weights synthetic uses the seeded synthetic checkpoint
+multiple of 8, or --textures N synth.make_template textures of --size.  --backgrounds a.npy ... puts one of those images behind the
+warped plane, --blur / --noise / --saturation / --hue / --contrast LO HI draw the parameters of woft_amd.hsynth.augment for the
+second frame from those ranges and --augment-src blurs and noises the first frame too (HSynth's keywords; all off by default).
+--weights synthetic uses the seeded synthetic checkpoint
 (with it the numbers mean nothing beyond "the loop runs"); --weights PATH a torch.load-able state dict with the reference's key
 set.  Prints the loss of every step, ends with sync_*_head() and a torch.save of the head's parameters to --out.
 """
@@ -75,13 +78,18 @@ def weight_loss(provider, s, rs, n_points=N_POINTS, max_loss=MAX_LOSS):
     return torch.clamp(err, max=max_loss).mean()
 
 
+def load_npy(p):
+    a = np.load(p)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise SystemExit(f"{p}: an (H, W, 3) uint8 array is expected, got {a.dtype} {a.shape}")
+    return a
+
+
 def load_images(paths, n_textures, size):
     if paths:
         out = []
         for p in paths:
-            a = np.load(p)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise SystemExit(f"{p}: an (H, W, 3) uint8 array is expected, got {a.dtype} {a.shape}")
+            a = load_npy(p)
             out.append(np.ascontiguousarray(a[:a.shape[0] // 8 * 8, :a.shape[1] // 8 * 8]))
         return out
     return [synth.make_template(size[0], size[1], seq_id=k) for k in range(n_textures)]
@@ -99,13 +107,23 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=12, help="RAFT refinement iterations")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="where the head's trained parameters are saved (default <head>_head.pt)")
+    ap.add_argument("--backgrounds", nargs="+", default=[], metavar="NPY", help=".npy (H, W, 3) uint8 images put behind the plane")
+    ap.add_argument("--blur", type=float, nargs=2, default=[0.0, 0.0], metavar=("LO", "HI"), help="blur sigma range, pixels")
+    ap.add_argument("--noise", type=float, nargs=2, default=[0.0, 0.0], metavar=("LO", "HI"), help="noise sigma range, grey levels")
+    ap.add_argument("--saturation", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"))
+    ap.add_argument("--hue", type=float, nargs=2, default=[0.0, 0.0], metavar=("LO", "HI"), help="hue rotation range, radians")
+    ap.add_argument("--contrast", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"))
+    ap.add_argument("--augment-src", action="store_true", help="blur and noise the first frame too")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "training runs on the MI355X: there is no CPU path"
     if args.size[0] % 8 or args.size[1] % 8:
         raise SystemExit("--size: multiples of 8 are expected (the training configs' 'nopad' contract)")
     provider = make_provider(args.head, args.weights, args.iters)
     ds = HSynth(load_images(args.images, args.textures, args.size), seed=args.seed,
-                n_occluders=(0, 2) if args.head == "mask" else (0, 1))
+                n_occluders=(0, 2) if args.head == "mask" else (0, 1),
+                backgrounds=[np.ascontiguousarray(load_npy(p)) for p in args.backgrounds] or None, blur_sigma=args.blur,
+                noise_sigma=args.noise, saturation=args.saturation, hue=args.hue, contrast=args.contrast,
+                augment_src=args.augment_src)
     params = provider.mask_head_parameters() if args.head == "mask" else provider.weight_head_parameters()
     opt = torch.optim.Adam(list(params.values()), lr=args.lr)
     rs = np.random.RandomState([args.seed, 0x7EAD])

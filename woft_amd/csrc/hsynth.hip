@@ -16,6 +16,13 @@ struct OccSet {
 
 struct Photo { float gain[3], bias[3]; };
 
+// The background behind the plane (woft_hsynth_render_bg): an image and the homography destination frame -> image.
+struct Backdrop {
+    const uint8_t* img;
+    int hb, wb;
+    H9 hinv;
+};
+
 // One BGRA tap of an occluder, premultiplied: a = m * (alpha / 255), p[c] = a * colour[c].
 __device__ __forceinline__ void occ_tap(const uint8_t* __restrict__ tex, int wo, int cy, int cx, float m, float& a, float* p) {
     const uint32_t q = *reinterpret_cast<const uint32_t*>(tex + ((int64_t)cy * wo + cx) * 4);
@@ -43,24 +50,51 @@ __device__ __forceinline__ float occ_sample(const OccSet& oc, int k, double x, d
     return warp_blend(t, a00, a01, a10, a11);
 }
 
+// Channels g[0..2] of the background at destination pixel (x, y): replicate border (every tap counts, at its clamped index), zero
+// where the denominator is not positive or a coordinate is not finite.
+__device__ __forceinline__ void backdrop_sample(const Backdrop& bg, int x, int y, float* g) {
+    double gx, gy;
+    const double d = warp_source(bg.hinv, x, y, gx, gy);
+    g[0] = g[1] = g[2] = 0.f;
+    if (!(d > 0.0) || !isfinite(gx) || !isfinite(gy)) return;
+    WarpTaps t = warp_taps(bg.hb, bg.wb, gx, gy);
+    t.m00 = t.m01 = t.m10 = t.m11 = 1.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g[c] = warp_sample(bg.img, bg.wb, 3, t, c);
+}
+
 // Thread i renders pixels 4i .. 4i+3 of the flattened (h, w) frame: 12 bytes of out_u8, 12 floats of out_f32, 4 of cover, stored
-// as 3 dwords / 3 + 1 float4 when `vec` (every output base aligned; n a multiple of 4 or the thread not the last one).
+// as 3 dwords / 3 + 1 float4 when `vec` (every output base aligned; n a multiple of 4 or the thread not the last one).  BG: the
+// background composited behind the plane and the plane's coverage written next to cover (woft_hsynth_render_bg); without it the
+// instructions of woft_hsynth_render.
+template <bool BG>
 __global__ __launch_bounds__(256) void hsynth_render_kernel(const uint8_t* __restrict__ base, int hs, int ws, H9 hi, Photo ph,
-                                                            OccSet oc, uint8_t* __restrict__ out_u8, float* __restrict__ out_f32,
-                                                            float* __restrict__ cover, int h, int w, int vec) {
+                                                            OccSet oc, Backdrop bg, uint8_t* __restrict__ out_u8,
+                                                            float* __restrict__ out_f32, float* __restrict__ cover,
+                                                            float* __restrict__ plane, int h, int w, int vec) {
     const int64_t n = (int64_t)h * w, o0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (o0 >= n) return;
-    float v[12], cv[4];
+    float v[12], cv[4], pv[4];
     int y = (int)(o0 / w), x = (int)(o0 - (int64_t)y * w);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (o0 + j < n) {
             double sx, sy;
-            warp_source(hi, x, y, sx, sy);
+            const double den = warp_source(hi, x, y, sx, sy);
             const WarpTaps t = warp_taps(hs, ws, sx, sy);
             float u[3];
+            if (BG) {
+                const float P = den > 0.0 ? warp_blend(t, t.m00, t.m01, t.m10, t.m11) : 0.f;
+                const float behind = 1.f - P;
+                float g[3];
+                backdrop_sample(bg, x, y, g);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) u[c] = ph.gain[c] * warp_sample(base, ws, 3, t, c) + ph.bias[c];
+                for (int c = 0; c < 3; ++c) u[c] = ph.gain[c] * (warp_sample(base, ws, 3, t, c) + behind * g[c]) + ph.bias[c];
+                pv[j] = P;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) u[c] = ph.gain[c] * warp_sample(base, ws, 3, t, c) + ph.bias[c];
+            }
             float keep = 1.f;
 #pragma unroll
             for (int k = 0; k < WOFT_HSYNTH_MAX_OCC; ++k) {
@@ -79,6 +113,7 @@ __global__ __launch_bounds__(256) void hsynth_render_kernel(const uint8_t* __res
 #pragma unroll
             for (int c = 0; c < 3; ++c) v[3 * j + c] = 0.f;
             cv[j] = 0.f;
+            if (BG) pv[j] = 0.f;
         }
         if (++x == w) { x = 0; ++y; }
     }
@@ -99,6 +134,7 @@ __global__ __launch_bounds__(256) void hsynth_render_kernel(const uint8_t* __res
             for (int q = 0; q < 3; ++q) of[q] = f32x4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
         }
         if (cover != nullptr) *reinterpret_cast<f32x4*>(cover + o0) = f32x4{cv[0], cv[1], cv[2], cv[3]};
+        if (BG && plane != nullptr) *reinterpret_cast<f32x4*>(plane + o0) = f32x4{pv[0], pv[1], pv[2], pv[3]};
         return;
     }
 #pragma unroll
@@ -110,6 +146,7 @@ __global__ __launch_bounds__(256) void hsynth_render_kernel(const uint8_t* __res
             if (out_f32 != nullptr) out_f32[(o0 + j) * 3 + c] = v[3 * j + c];
         }
         if (cover != nullptr) cover[o0 + j] = cv[j];
+        if (BG && plane != nullptr) plane[o0 + j] = pv[j];
     }
 }
 
@@ -185,22 +222,45 @@ bool hsynth_args(int hs, int ws, const woft_hsynth_occluder* occ, int n_occ, int
     return true;
 }
 
-}  // namespace
-
-extern "C" int woft_hsynth_render(const uint8_t* base, int32_t hs, int32_t ws, const double* hinv, const float* gain,
-                                  const float* bias, const woft_hsynth_occluder* occ, int32_t n_occ, uint8_t* out_u8,
-                                  float* out_f32, float* cover, int32_t h, int32_t w, void* stream) {
+// Both render entries: arguments checked, one launch of the kernel with or without the background.
+int hsynth_render(const uint8_t* base, int hs, int ws, const double* hinv, const float* gain, const float* bias,
+                  const woft_hsynth_occluder* occ, int n_occ, const Backdrop* bg, uint8_t* out_u8, float* out_f32, float* cover,
+                  float* plane, int h, int w, void* stream) {
     OccSet oc;
     if (!base || !hinv || !out_u8 || !hsynth_args(hs, ws, occ, n_occ, h, w, oc)) return WOFT_EINVAL;
     H9 hi;
     for (int i = 0; i < 9; ++i) hi.v[i] = hinv[i];
     Photo ph;
     for (int c = 0; c < 3; ++c) ph.gain[c] = gain ? gain[c] : 1.f, ph.bias[c] = bias ? bias[c] : 0.f;
-    const int vec = aligned_to(out_u8, 4) && aligned_to(out_f32, 16) && aligned_to(cover, 16);
+    const int vec = aligned_to(out_u8, 4) && aligned_to(out_f32, 16) && aligned_to(cover, 16) && aligned_to(plane, 16);
     const int64_t n4 = ceil_div64((int64_t)h * w, 4);
-    hipLaunchKernelGGL(hsynth_render_kernel, dim3((unsigned)ceil_div64(n4, 256)), dim3(256), 0, (hipStream_t)stream, base, hs,
-                       ws, hi, ph, oc, out_u8, out_f32, cover, h, w, vec);
+    const dim3 grid((unsigned)ceil_div64(n4, 256));
+    if (bg != nullptr)
+        hipLaunchKernelGGL(hsynth_render_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, base, hs, ws, hi, ph, oc, *bg,
+                           out_u8, out_f32, cover, plane, h, w, vec);
+    else
+        hipLaunchKernelGGL(hsynth_render_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, base, hs, ws, hi, ph, oc,
+                           Backdrop{}, out_u8, out_f32, cover, plane, h, w, vec);
     return woft_launch_status();
+}
+
+}  // namespace
+
+extern "C" int woft_hsynth_render(const uint8_t* base, int32_t hs, int32_t ws, const double* hinv, const float* gain,
+                                  const float* bias, const woft_hsynth_occluder* occ, int32_t n_occ, uint8_t* out_u8,
+                                  float* out_f32, float* cover, int32_t h, int32_t w, void* stream) {
+    return hsynth_render(base, hs, ws, hinv, gain, bias, occ, n_occ, nullptr, out_u8, out_f32, cover, nullptr, h, w, stream);
+}
+
+extern "C" int woft_hsynth_render_bg(const uint8_t* base, int32_t hs, int32_t ws, const double* hinv, const float* gain,
+                                     const float* bias, const woft_hsynth_occluder* occ, int32_t n_occ, const uint8_t* bg,
+                                     int32_t hb, int32_t wb, const double* hinv_bg, uint8_t* out_u8, float* out_f32, float* cover,
+                                     float* plane, int32_t h, int32_t w, void* stream) {
+    if (!bg || !hinv_bg || hb <= 0 || wb <= 0 || (int64_t)hb * wb >= (1ll << 31)) return WOFT_EINVAL;
+    Backdrop b;
+    b.img = bg, b.hb = hb, b.wb = wb;
+    for (int i = 0; i < 9; ++i) b.hinv.v[i] = hinv_bg[i];
+    return hsynth_render(base, hs, ws, hinv, gain, bias, occ, n_occ, &b, out_u8, out_f32, cover, plane, h, w, stream);
 }
 
 extern "C" int woft_hsynth_labels(int32_t hs, int32_t ws, const double* hfwd, const woft_hsynth_occluder* occ, int32_t n_occ,

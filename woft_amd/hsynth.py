@@ -5,6 +5,9 @@ homography with a photometric change and pasted occluders, the exact homography,
 label with its valid mask.  The reference's training configs name such a data set (`COCOHSynth`), its code is not part of the
 reference: the semantics here are this project's own (include/woft_hip.h, `woft_hsynth_render` / `woft_hsynth_labels`).  Two HIP
 launches per sample; everything random comes from `numpy.random.RandomState`, so a sample is a function of its seed.
+
+Opt-in (`woft_hsynth_render_bg`, `woft_hsynth_augment`): a background image behind the warped plane, and
+`augment` -- blur, colour map, noise -- over the rendered frame, one more launch each for the frames it is asked for.
 """
 from collections import namedtuple
 
@@ -14,6 +17,7 @@ import torch
 from . import ops, synth
 
 HSynthSample = namedtuple("HSynthSample", "src dst H_gt flow_gt visible valid")
+HSynthAugment = namedtuple("HSynthAugment", "background background_H blur_sigma saturation hue contrast noise_sigma seed_dst seed_src")
 MAX_OCCLUDERS = 4          # WOFT_HSYNTH_MAX_OCC
 
 
@@ -68,16 +72,25 @@ def _occluders(occluders):
     return out
 
 
-def render_pair(base, H_gt, occluders=(), gain=None, bias=None, out_hw=None, want_f32=False, want_cover=False):
+def render_pair(base, H_gt, occluders=(), gain=None, bias=None, out_hw=None, want_f32=False, want_cover=False, background=None,
+                background_H=None, want_plane=False):
     """The second frame of a pair: `base` ((hs, ws, 3) uint8, device tensor or numpy image) seen through H_gt (3x3, base ->
     destination), times gain plus bias (a number or three, per channel), under the occluders [(tex_bgra (ho, wo, 4) uint8, H_occ
-    3x3 texture -> destination)] composited in order; black outside the base image.  -> dst (h, w, 3) uint8 on the device
-    (out_hw, default the base's size); with want_f32 or want_cover: (dst, the un-rounded float32 (h, w, 3) image or None, the
-    occluders' joint coverage (h, w) float32 or None)."""
+    3x3 texture -> destination)] composited in order; black outside the base image, or `background` ((hb, wb, 3) uint8, numpy or
+    device) seen through background_H (3x3, background -> destination; default the identity) with a replicate border, behind the
+    plane and under the gain, the bias and the occluders.  -> dst (h, w, 3) uint8 on the device (out_hw, default the base's
+    size); with want_f32 or want_cover: (dst, the un-rounded float32 (h, w, 3) image or None, the occluders' joint coverage (h, w)
+    float32 or None); with want_plane (a background is needed): those three and the plane's coverage (h, w) float32."""
     base = _device_u8(base, "base", 3)
     H_gt = _h33(H_gt, "H_gt")
     occ = _occluders(occluders)
     h, w = base.shape[:2] if out_hw is None else _hw(out_hw, "out_hw")
+    if background is None:
+        if background_H is not None or want_plane:
+            raise ValueError("background: background_H and want_plane need a background image")
+    else:
+        background = _device_u8(background, "background", 3)
+        background_H = np.eye(3) if background_H is None else _h33(background_H, "background_H")
 
     def three(v, what):
         if v is None:
@@ -91,8 +104,76 @@ def render_pair(base, H_gt, occluders=(), gain=None, bias=None, out_hw=None, wan
     dst = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
     f32 = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if want_f32 else None
     cover = torch.empty((h, w), dtype=torch.float32, device=dev) if want_cover else None
-    ops.hsynth_render(base, H_gt, occ, gain, bias, dst, f32, cover)
+    if background is None:
+        ops.hsynth_render(base, H_gt, occ, gain, bias, dst, f32, cover)
+        return (dst, f32, cover) if (want_f32 or want_cover) else dst
+    plane = torch.empty((h, w), dtype=torch.float32, device=dev) if want_plane else None
+    ops.hsynth_render_bg(base, H_gt, occ, gain, bias, background, background_H, dst, f32, cover, plane)
+    if want_plane:
+        return dst, f32, cover, plane
     return (dst, f32, cover) if (want_f32 or want_cover) else dst
+
+
+MAX_BLUR = 7               # WOFT_HSYNTH_MAX_BLUR
+GREY_BGR = (0.114, 0.587, 0.299)
+
+
+def blur_taps(sigma):
+    """The taps of augment's blur: exp(-i^2 / (2 sigma^2)) for i = -r .. r with r = min(7, ceil(3 sigma)), normalised to sum 1 in
+    float64 and then rounded to float32.  sigma = 0: the single tap 1 (no blur)."""
+    sigma = float(sigma)
+    if not (0.0 <= sigma < float("inf")):
+        raise ValueError(f"blur_sigma: a finite number >= 0 is expected, got {sigma!r}")
+    r = min(MAX_BLUR, int(np.ceil(3.0 * sigma)))
+    if r == 0:
+        return np.ones(1, np.float32)
+    i = np.arange(-r, r + 1, dtype=np.float64)
+    t = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    return (t / t.sum()).astype(np.float32)
+
+
+def colour_matrix(saturation=1.0, hue=0.0, contrast=1.0):
+    """augment's affine colour map u = M t + o on (B, G, R), composed in float64: a saturation about the grey 0.114 B + 0.587 G +
+    0.299 R, then a rotation by `hue` (radians) about the grey axis B = G = R, then a contrast about 127.5.  -> (M (3, 3), o (3,))
+    float64; (1, 0, 1) gives the identity and a zero offset exactly."""
+    s, th, k = float(saturation), float(hue), float(contrast)
+    if not all(np.isfinite(v) for v in (s, th, k)):
+        raise ValueError(f"saturation, hue, contrast: finite numbers are expected, got {(saturation, hue, contrast)!r}")
+    eye, ones = np.eye(3), np.ones((3, 3))
+    S = s * eye + (1.0 - s) * ones * np.asarray(GREY_BGR)[None, :]
+    c, sn = np.cos(th), np.sin(th)
+    K = np.array([[0.0, -1.0, 1.0], [1.0, 0.0, -1.0], [-1.0, 1.0, 0.0]])
+    R = c * eye + ((1.0 - c) / 3.0) * ones + (sn / np.sqrt(3.0)) * K
+    RS = R[:, 0:1] * S[0:1, :] + R[:, 1:2] * S[1:2, :] + R[:, 2:3] * S[2:3, :]       # (element-wise: no BLAS, the same bits everywhere)
+    return k * RS, np.full(3, 127.5 * (1.0 - k))
+
+
+def augment(frame, blur_sigma=0.0, saturation=1.0, hue=0.0, contrast=1.0, noise_sigma=0.0, seed=0, want_f32=False):
+    """Photometric augmentation of a device frame ((H, W, 3) uint8 or float32, B, G, R), in one launch: a Gaussian blur
+    (blur_taps(blur_sigma), replicate border), the colour map colour_matrix(saturation, hue, contrast) (left out when it is the
+    identity), noise of standard deviation noise_sigma that is a function of (seed, pixel, channel), rounding.  -> the uint8
+    frame; with want_f32: (uint8 frame, the un-rounded float32 one).  A uint8 frame is converted to float32 first (one torch
+    op); a float32 one, such as render_pair's un-rounded output, is read as it is and left unchanged."""
+    if not isinstance(frame, torch.Tensor) or frame.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"frame: a uint8 or float32 device tensor is expected, got {getattr(frame, 'dtype', type(frame).__name__)}")
+    if not frame.is_cuda:
+        raise ValueError(f"frame: a device tensor is expected, got a tensor on {frame.device}")
+    if frame.dim() != 3 or frame.shape[2] != 3 or frame.shape[0] < 1 or frame.shape[1] < 1:
+        raise ValueError(f"frame: shape (H, W, 3) is expected, got {tuple(frame.shape)}")
+    taps = blur_taps(blur_sigma)
+    M, o = colour_matrix(saturation, hue, contrast)
+    noise_sigma, seed = float(noise_sigma), int(seed)
+    if not (0.0 <= noise_sigma < float("inf")):
+        raise ValueError(f"noise_sigma: a finite number >= 0 is expected, got {noise_sigma!r}")
+    if not (0 <= seed < 1 << 32):
+        raise ValueError(f"seed: 0 <= seed < 2^32 is expected, got {seed!r}")
+    identity = np.array_equal(M, np.eye(3)) and not o.any()
+    colour = None if identity else np.concatenate([M.ravel(), o]).astype(np.float32)
+    src = frame.contiguous() if frame.dtype == torch.float32 else frame.float().contiguous()
+    out_u8 = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+    out_f32 = torch.empty_like(src) if want_f32 else None
+    ops.hsynth_augment(src, taps, colour, noise_sigma, seed, out_u8, out_f32)
+    return (out_u8, out_f32) if want_f32 else out_u8
 
 
 def pair_labels(src_hw, H_gt, occluders=(), out_hw=None, lo=0.25, hi=0.75):
@@ -210,10 +291,19 @@ class HSynth:
     numpy.random.RandomState([seed, i, epoch]): the homography (random_homography, max_shift), between n_occluders[0] and
     n_occluders[1] occluders (a texture of occluder_textures -- default: eight make_occluder textures drawn from the seed --
     through a random similarity times a random_homography of the texture, the longer side between 0.2 and 0.5 of the frame's
-    shorter one, centred anywhere in the frame), one gain and one bias for all channels from gain_range and bias_range."""
+    shorter one, centred anywhere in the frame), one gain and one bias for all channels from gain_range and bias_range.
+
+    Opt-in, all off by default (then a sample is the launches and the bytes it was without them): `backgrounds`, a list of uint8
+    (hb, wb, 3) images of at least 2 x 2 pixels, one of which is put behind the plane through a random similarity times a
+    random_homography of it that keeps the frame covered; `blur_sigma`, `noise_sigma`, `saturation`, `hue`, `contrast`, (low,
+    high) ranges drawn uniformly for `augment` of dst (render_pair's un-rounded frame is augmented: the render's own uint8 is not
+    the sample's dst); `augment_src`: src goes through `augment` too, with the same blur, its own noise seed and no colour
+    change.  These draws come from a RandomState of their own, numpy.random.RandomState([seed, i, epoch, 0xA06]): H_gt, the
+    occluders, gain and bias -- and with them flow_gt, visible and valid -- are what they are without the new keywords."""
 
     def __init__(self, images, occluder_textures=None, seed=0, max_shift=0.2, n_occluders=(0, 2), gain_range=(0.8, 1.2),
-                 bias_range=(-20, 20), lo=0.25, hi=0.75):
+                 bias_range=(-20, 20), lo=0.25, hi=0.75, backgrounds=None, blur_sigma=(0, 0), noise_sigma=(0, 0),
+                 saturation=(1, 1), hue=(0, 0), contrast=(1, 1), augment_src=False):
         self.images = [_device_u8(im, f"images[{k}]", 3, multiple=8) for k, im in enumerate(images)]
         self.seed = int(seed)
         if not (0 <= self.seed < 1 << 32):
@@ -239,12 +329,33 @@ class HSynth:
         self.textures = [_device_u8(t, f"occluder_textures[{k}]", 4) for k, t in enumerate(occluder_textures)]
         if n1 > 0 and not self.textures:
             raise ValueError("occluder_textures: at least one texture is expected when n_occluders allows an occluder")
+        self.backgrounds = [_device_u8(b, f"backgrounds[{k}]", 3) for k, b in enumerate(backgrounds or [])]
+        for k, b in enumerate(self.backgrounds):
+            if min(b.shape[:2]) < 2:
+                raise ValueError(f"backgrounds[{k}]: an image of at least 2 x 2 pixels is expected, got {tuple(b.shape[:2])}")
+
+        def span(v, what, least):
+            v = tuple(float(x) for x in v)
+            if len(v) != 2 or not (least <= v[0] <= v[1] < float("inf")):
+                raise ValueError(f"{what}: a finite (low, high) with {least} <= low <= high is expected, got {v!r}")
+            return v
+        self.blur_sigma = span(blur_sigma, "blur_sigma", 0.0)
+        self.noise_sigma = span(noise_sigma, "noise_sigma", 0.0)
+        self.saturation = span(saturation, "saturation", -float("inf"))
+        self.hue = span(hue, "hue", -float("inf"))
+        self.contrast = span(contrast, "contrast", -float("inf"))
+        self.augment_src = bool(augment_src)
+        self.augmented = bool(self.backgrounds) or self.augment_src or self.blur_sigma != (0.0, 0.0) \
+            or self.noise_sigma != (0.0, 0.0) or self.saturation != (1.0, 1.0) or self.hue != (0.0, 0.0) \
+            or self.contrast != (1.0, 1.0)
 
     def __len__(self):
         return len(self.images)
 
     def draw(self, i, epoch=0):
-        """The random part of sample (i, epoch), on the host: (H_gt, [(texture index, H_occ)], gain, bias)."""
+        """The random part of sample (i, epoch), on the host: (H_gt, [(texture index, H_occ)], gain, bias), and with any of the
+        background / augmentation keywords on a fifth field, an HSynthAugment (background index or None, background_H or None,
+        blur_sigma, saturation, hue, contrast, noise_sigma, seed_dst, seed_src)."""
         i, epoch = int(i), int(epoch)
         if not (0 <= i < len(self.images)):
             raise IndexError(f"HSynth index {i} out of range for {len(self.images)} images")
@@ -267,14 +378,48 @@ class HSynth:
             occ.append((t, place @ bend))
         gain = float(rs.uniform(*self.gain_range))
         bias = float(rs.uniform(*self.bias_range))
-        return H_gt, occ, gain, bias
+        if not self.augmented:
+            return H_gt, occ, gain, bias
+        return H_gt, occ, gain, bias, self._draw_augment(np.random.RandomState([self.seed, i, epoch, 0xA06]), h, w)
+
+    def _draw_augment(self, rs, h, w):
+        b, H_bg = None, None
+        if self.backgrounds:
+            b = int(rs.randint(0, len(self.backgrounds)))
+            hb, wb = self.backgrounds[b].shape[:2]
+            # the bent background holds its rectangle inset by the corners' largest move, and that the disc of radius `inner`
+            # about its centre; scaled to at least the frame's half diagonal and moved by no more than the excess, the disc covers
+            # the frame under any rotation
+            shift = min(self.max_shift, 0.2)
+            bend = random_homography(rs, hb, wb, shift)
+            inner = 0.5 * (min(hb, wb) - 1.0) - shift * min(hb, wb)
+            outer = 0.5 * float(np.hypot(h - 1.0, w - 1.0))
+            s = max(outer, 0.5) / inner * rs.uniform(1.0, 1.5)
+            a = rs.uniform(0.0, 2.0 * np.pi)
+            slack = (s * inner - outer) / np.sqrt(2.0)
+            cx, cy = (w - 1) / 2.0 + rs.uniform(-slack, slack), (h - 1) / 2.0 + rs.uniform(-slack, slack)
+            ca, sa = s * np.cos(a), s * np.sin(a)
+            tx, ty = (wb - 1) / 2.0, (hb - 1) / 2.0
+            place = np.array([[ca, -sa, cx - ca * tx + sa * ty], [sa, ca, cy - sa * tx - ca * ty], [0.0, 0.0, 1.0]])
+            H_bg = place @ bend
+        scalars = [float(rs.uniform(*r)) for r in (self.blur_sigma, self.saturation, self.hue, self.contrast, self.noise_sigma)]
+        seed_dst, seed_src = (int(v) for v in rs.randint(0, 1 << 32, 2, dtype=np.uint64))
+        return HSynthAugment(b, H_bg, *scalars, seed_dst, seed_src)
 
     def sample(self, i, epoch=0):
-        H_gt, occ, gain, bias = self.draw(i, epoch)
+        H_gt, occ, gain, bias, *aug = self.draw(i, epoch)
         src = self.images[int(i)]
         occluders = [(self.textures[t], H_occ) for t, H_occ in occ]
-        dst = render_pair(src, H_gt, occluders, gain=gain, bias=bias)
         flow, visible, valid = pair_labels(src.shape[:2], H_gt, occluders, lo=self.lo, hi=self.hi)
+        if not aug:
+            dst = render_pair(src, H_gt, occluders, gain=gain, bias=bias)
+            return HSynthSample(src, dst, H_gt, flow, visible, valid)
+        a = aug[0]
+        bg = None if a.background is None else self.backgrounds[a.background]
+        f32 = render_pair(src, H_gt, occluders, gain=gain, bias=bias, want_f32=True, background=bg, background_H=a.background_H)[1]
+        dst = augment(f32, a.blur_sigma, a.saturation, a.hue, a.contrast, a.noise_sigma, a.seed_dst)
+        if self.augment_src:
+            src = augment(src, blur_sigma=a.blur_sigma, noise_sigma=a.noise_sigma, seed=a.seed_src)
         return HSynthSample(src, dst, H_gt, flow, visible, valid)
 
     def __getitem__(self, i):

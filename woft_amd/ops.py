@@ -1011,6 +1011,32 @@ def hsynth_render(base, Hmat, occluders, gain, bias, out_u8, out_f32=None, cover
                                          h, w, stream_ptr()), "woft_hsynth_render")
 
 
+def hsynth_render_bg(base, Hmat, occluders, gain, bias, bg, Hbg, out_u8, out_f32=None, cover=None, plane=None):
+    """woft_hsynth_render_bg: hsynth_render with the background bg ((hb, wb, 3) uint8) seen through Hbg (background -> destination)
+    behind the plane; plane (h, w) float32 or None = the plane's coverage."""
+    hs, ws = base.shape[:2]
+    h, w = out_u8.shape[:2]
+    occ, n = _hsynth_occluders(occluders)
+    g = None if gain is None else (C.c_float * 3)(*[float(v) for v in gain])
+    b = None if bias is None else (C.c_float * 3)(*[float(v) for v in bias])
+    check(_lib.load().woft_hsynth_render_bg(ptr(base), hs, ws, _hinv9(Hmat), g, b, occ, n, ptr(bg), bg.shape[0], bg.shape[1],
+                                            _hinv9(Hbg), ptr(out_u8), ptr(out_f32), ptr(cover), ptr(plane), h, w, stream_ptr()),
+          "woft_hsynth_render_bg")
+
+
+def hsynth_augment(frame, taps, colour, noise_sigma, seed, out_u8, out_f32=None):
+    """woft_hsynth_augment: frame (h, w, 3) float32 -> out_u8 (and out_f32) through the blur with `taps` (2 r + 1 float32 values,
+    None or one value = no blur), the affine colour map `colour` (12 float32 values: M row-major, then the offset; None =
+    identity), noise of noise_sigma from the 32-bit seed.  out_f32 may be `frame` itself when there is no blur."""
+    assert _f32c(frame) and frame.dim() == 3 and frame.shape[2] == 3
+    h, w = frame.shape[:2]
+    radius = 0 if taps is None else (len(taps) - 1) // 2
+    t = None if radius == 0 else (C.c_float * len(taps))(*[float(v) for v in taps])
+    m = None if colour is None else (C.c_float * 12)(*[float(v) for v in colour])
+    check(_lib.load().woft_hsynth_augment(ptr(frame), h, w, t, radius, m, float(noise_sigma), int(seed) & 0xFFFFFFFF, ptr(out_u8),
+                                          ptr(out_f32), stream_ptr()), "woft_hsynth_augment")
+
+
 def hsynth_labels(src_hw, Hmat, occluders, out_hw, lo, hi, flow, visible, valid):
     """woft_hsynth_labels: flow (2, hs, ws) float32, visible (hs, ws) float32, valid (hs, ws) bool / uint8 of the template pixels
     under Hmat (base -> destination) and the occluders."""

@@ -481,6 +481,19 @@ int woft_flow_chain_fold(const float* prev_flow, const float* prev_cost, const f
 #define WOFT_CHAIN_HIST 130
 int woft_chain_tc(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask, int32_t gh,
                   int32_t gw, int32_t mh, int32_t mw, float vis_thr, float* dst, float* w, float* ok, int32_t* hist, void* stream);
+/* woft_chain_tc for several template masks at once (csrc/flow_multi.hip).  DESIGN.md section 25.  The masks are one bit plane:
+ * tbits, uint32 [mh][mw] with gh <= mh, gw <= mw, bit t of tbits[y * mw + x] set where pixel (x, y) lies in target t's mask,
+ * 1 <= n_targets <= 32, masks may overlap; bits at and above n_targets are ignored.  dst, w (may be NULL) and ok do not depend on
+ * a mask: they have the bytes woft_chain_tc writes.  hist: int32 [n_targets][WOFT_CHAIN_HIST], row t what woft_chain_tc writes
+ * for a uint8 mask equal to bit t.  Zeroed by this call on the stream; a wave counts its lanes per (counter, target) with
+ * ballots, blocks count in LDS and add their non-zero counters with integer atomics: deterministic, two calls give equal bytes.
+ * Same geometry as woft_chain_tc, no workspace, no floating-point atomics; sel indexes the LDS counters after its range check.
+ * -1 (before any launch) on a NULL flow / cost / vis / sel / tbits / dst / ok / hist, gh or gw <= 0 or > 2^24, mh < gh or mw < gw,
+ * n_targets outside [1, 32], vis_thr outside [0, 1] or NaN, an output that shares a byte with an input or with another output. */
+#define WOFT_MULTI_MAX_TARGETS 32
+int woft_chain_tc_multi(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits,
+                        int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t n_targets, float vis_thr, float* dst, float* w,
+                        float* ok, int32_t* hist, void* stream);
 
 /* Frame-features record (csrc/features.hip).  DESIGN.md section 20.  What the encoders produce for one image at one padded
  * geometry, P = (hp / 8) * (wp / 8) pixels, as one contiguous fp32 block: record = [P][fdim] fnet map | [P][hdim] net (after
@@ -786,6 +799,26 @@ int woft_tc_select_vis(const float* dst, const float* w, const uint8_t* tmask, c
 int woft_tc_flags_vis(const float* dst, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw, int32_t mh,
                       int32_t mw, int32_t check_dst, const float* vis, int32_t vis_mode, float vis_thr, uint8_t* flags,
                       void* stream);
+/* woft_tc_select_vis for n_targets template masks at once (csrc/select.hip).  DESIGN.md section 25.  tbits: the bit plane of
+ * woft_chain_tc_multi, uint32 [mh][mw], 1 <= n_targets <= 32.  For every target t the keep rule of woft_tc_select_vis with
+ * tmask = bit t and pwmask = NULL, then that call's order-preserving compaction and Sobol draw (float32 rint(N * u_k), sorted,
+ * duplicates removed; keep-all when n_draw == 0 or n_draw >= N).  The bounds test and the visibility gate do not depend on the
+ * target: dst and vis are read once per pixel.  Outputs: pa, pb [n_targets][cap][2], wout [n_targets][cap] (may be NULL),
+ * count int32 [2][n_targets]: count[t] = selected (<= cap), count[n_targets + t] = kept -- two rows, so that the first is the
+ * `counts` of woft_hfit_batched.  The first count[t] rows of target t's slices have the bytes the single-target call writes;
+ * rows beyond are not specified.  vis, vis_mode, vis_thr and w == NULL as in woft_tc_select_vis.
+ * ws: woft_tc_select_multi_ws_bytes(gh * gw, n_targets) bytes (-1 for n < 0 or n_targets outside [1, 32]): per target the
+ * int32 header, per-1024 counts, offsets and rank list of the single call, then one uint32 of keep bits per pixel.
+ * Three launches, no host round trip, no atomics: two calls give equal bytes.
+ * WOFT_EINVAL before any launch on a NULL dst / tbits / ws / pa / pb / count, gh or gw <= 0, gh * gw above 2^31 - 1024 (ranks
+ * are int32), mh < gh or mw < gw, cap <= 0,
+ * n_targets outside [1, 32], n_draw outside [0, 1024] or positive with a NULL sobol_u, a vis_mode outside [0, 2], a NaN
+ * vis_thr, an output (pa, pb, wout, count, ws) that shares a byte with an input or with another output. */
+int64_t woft_tc_select_multi_ws_bytes(int64_t n, int32_t n_targets);
+int woft_tc_select_multi(const float* dst, const float* w, const uint32_t* tbits, int32_t gh, int32_t gw, int32_t mh, int32_t mw,
+                         int32_t n_targets, int32_t check_dst, const float* sobol_u, int32_t n_draw, const float* vis,
+                         int32_t vis_mode, float vis_thr, void* ws, float* pa, float* pb, float* wout, int32_t cap,
+                         int32_t* count, void* stream);
 
 /* Weighted / iteratively re-weighted least-squares homography, utils/least_squares_H.py:142-210
  * (n_irls = 0) and :280-346 (n_irls = 5 -> 6 solves); reweight: 0 none, 1 L1 (:268-269),
@@ -841,6 +874,13 @@ int woft_hfit_step(const float* pa, const float* pb, const float* w, int32_t n, 
  * frac[0] = mean(|proj(H, A) - B| <= thr). */
 int woft_inlier_frac(const float* pa, const float* pb, int32_t n_max, const int32_t* count, const float* H,
                      float thr, float* frac, void* stream);
+/* `batch` inlier tests in ONE launch: workgroup b runs the code of woft_inlier_frac on element b -- pa, pb [batch][n_max][2],
+ * counts [batch] device int32 or NULL (n = min(counts[b], n_max); n_max without counts), H [batch][9], frac [batch] -- so
+ * frac[b] has the bits of woft_inlier_frac on element b alone (an integer count divided once).  No atomics.  WOFT_EINVAL before
+ * any launch on a NULL pa / pb / H / frac, batch < 1, batch > WOFT_HFIT_BATCH_MAX, n_max < 0, a frac that shares a byte with
+ * an input. */
+int woft_inlier_frac_batched(const float* pa, const float* pb, int32_t batch, int32_t n_max, const int32_t* counts,
+                             const float* H, float thr, float* frac, void* stream);
 
 /* RANSAC homography, what cv2.findHomography(pa, pb, cv2.RANSAC, thr, max_iters, conf) does in
  * utils/least_squares_H.py:366-396 (find_homography_cvransac; configs/..._cvransac.py, ablation_09.py:26-30), restated in

@@ -1,1 +1,1 @@
-from woft_amd.chained import WOFTChained, chain_correspondences  # noqa: F401
+from woft_amd.chained import WOFTChained, WOFTChainedMulti, chain_correspondences  # noqa: F401

@@ -12,6 +12,9 @@ def __getattr__(name):
     if name in ("chain_correspondences", "WOFTChained"):
         from .chained import WOFTChained, chain_correspondences
         return chain_correspondences if name == "chain_correspondences" else WOFTChained
+    if name in ("WOFTChainedMulti", "pack_target_bits"):
+        from . import chained
+        return getattr(chained, name)
     if name in ("HSynth", "HSynthSample", "HSynthAugment", "render_pair", "pair_labels", "random_homography", "make_occluder",
                 "augment", "blur_taps", "colour_matrix"):
         from . import hsynth

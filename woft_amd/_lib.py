@@ -103,6 +103,7 @@ _SIGS = {
     "woft_flow_fb": (i32, [vp, vp, i32, i32, f32, f32, vp, vp, vp]),
     "woft_flow_chain_fold": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp]),
     "woft_chain_tc": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "woft_chain_tc_multi": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
     "woft_features_pack": (i32, [vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, vp, vp]),
     "woft_features_unpack": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp]),
     "woft_colsum":(i32, [vp, i64, i32, vp, i32, vp, vp]),
@@ -142,12 +143,15 @@ _SIGS = {
     "woft_tc_flags": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "woft_tc_select_vis": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, i32, vp, vp]),
     "woft_tc_flags_vis": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, vp]),
+    "woft_tc_select_multi_ws_bytes": (i64, [i64, i32]),
+    "woft_tc_select_multi": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, i32, vp, vp]),
     "woft_hfit_ws_bytes": (i64, []),
     "woft_hfit": (i32, [vp, vp, vp, i32, vp, i32, f32, i32, vp, vp, vp, vp]),
     "woft_hfit_batched": (i32, [vp, vp, vp, i32, i32, vp, i32, f32, i32, vp, vp, vp]),
     "woft_hfit_batched_bwd": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "woft_hfit_step": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "woft_inlier_frac": (i32, [vp, vp, i32, vp, vp, f32, vp, vp]),
+    "woft_inlier_frac_batched": (i32, [vp, vp, i32, i32, vp, vp, f32, vp, vp]),
     "woft_ransac_ws_bytes": (i64, [i32, i32]),
     "woft_ransac": (i32, [vp, vp, i32, vp, i32, C.c_double, C.c_double, C.c_uint64, i32, vp, vp, vp, vp, vp, vp]),
     "woft_trs_ws_bytes": (i64, [i32, i32]),

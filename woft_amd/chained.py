@@ -10,8 +10,16 @@ homography fit.  DESIGN.md section 19.
 One HIP launch (woft_chain_tc, csrc/flow_multi.hip) turns a fold result into target coordinates, the fit weight exp(-cost) -- the
 product of the chain's sigmoid(reliability logit) --, the 0 / 1 occlusion gate and the histogram of winning candidates under the
 template mask.  Forward only: no autograd graph.  There is no CPU implementation.
+
+    trk = WOFTChainedMulti(load_config("pytracking/configs/WOFT_chained_multi.py"))
+    trk.init(frame0, [mask_a, mask_b, mask_c])
+    Hs, metas = trk.track(frame1)
+
+K planar targets on one dense track: the fold is shared, the planar stage is batched over the targets
+(woft_chain_tc_multi, woft_tc_select_multi, woft_hfit_batched, woft_inlier_frac_batched, one read).
 """
 import logging
+import time
 from types import SimpleNamespace
 
 import numpy as np
@@ -19,7 +27,7 @@ import torch
 
 from . import ops
 from .multiflow import MultiFlowTracker, _check_constants, _dev32
-from .tracker import YAOFTrackerSingleControl
+from .tracker import YAOFTrackerSingleControl, _count_components, _Fit
 
 logger = logging.getLogger(__name__)
 
@@ -172,10 +180,16 @@ class WOFTChained(YAOFTrackerSingleControl):
             self._grid = {(gh, gw): torch.stack([i % gw, torch.div(i, gw, rounding_mode="floor")])}
         return self._grid[(gh, gw)]
 
+    _SOLVE_ERRORS = (AssertionError,)             # what the planar stage turns into "no usable fit" (too few correspondences)
+
     def track(self, input_img, debug=False, img_identifier=None):
-        meta = SimpleNamespace()
         self._n_tracked += 1
         out = self.multi.track(input_img)                            # (uploads the frame: the ring keeps a copy of its own)
+        return self._planar_stage(out, input_img, img_identifier)
+
+    def _planar_stage(self, out, input_img, img_identifier):
+        """The fold result of one frame -> (H_cur2init, meta) for the template mask in `_template_mask_u8`: correspondences, the
+        fit, the state update."""
         Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
         gh, gw = int(out.flow.shape[1]), int(out.flow.shape[2])
         dst, w, ok, hist = self._tc[(gh, gw)] = ops.chain_tc(out.flow, out.cost, out.vis, out.sel, self._template_mask_u8,
@@ -185,8 +199,16 @@ class WOFTChained(YAOFTrackerSingleControl):
         self.n_kept = None
         try:
             fit = self._solve(src_xy, dst, w, (gh, gw), (Hh, Ww), self._template_mask_u8, None, bounds=True, judge=True, vis=ok)
-        except AssertionError:                                       # (too few correspondences for the estimator)
+        except self._SOLVE_ERRORS:                                   # (too few correspondences for the estimator)
             fit = None
+        return self._finish(fit, hist.cpu().numpy().astype(np.int64), input_img, img_identifier)
+
+    def _decision_for_meta(self):
+        return self.solver_decision
+
+    def _finish(self, fit, counts, input_img, img_identifier):
+        """A frame's fit (None: there was none), `n_kept` and its histogram (int64 numpy) -> the state update, (H_cur2init, meta)."""
+        meta = SimpleNamespace()
         usable = (fit is not None and not (self.n_kept is not None and self.n_kept < 4) and bool(np.all(np.isfinite(fit.H))))
         meta.n_kept = self.n_kept
         meta.H_global_cur2init = fit.H.copy() if usable else None
@@ -201,12 +223,200 @@ class WOFTChained(YAOFTrackerSingleControl):
         self.prev_img, self.prev_img_identifier = input_img, img_identifier
         self._set_pose(H_cur2init.copy(), good=not self.lost)
         meta.lost, meta.N_lost, meta.global_H_success = self.lost, self.N_lost, success
-        counts = hist.cpu().numpy().astype(np.int64)
         meta.chain_hist = counts[:len(self.chain_deltas)].copy()
         meta.chain_invalid, meta.chain_occluded = int(counts[ops.CHAIN_HIST - 2]), int(counts[ops.CHAIN_HIST - 1])
         if not self._announced:
             self._announced = True
             meta.precision = getattr(self.flower, "precision", None)
             meta.precision_source = getattr(self.flower, "precision_source", None)
-            meta.solver_decision = self.solver_decision
+            meta.solver_decision = self._decision_for_meta()
         return H_cur2init.copy(), meta
+
+
+MAX_TARGETS = ops.MULTI_MAX_TARGETS
+
+
+def pack_target_bits(masks):
+    """K (H, W) masks (anything numpy compares with 0; K <= 32, equal shapes) -> the (H, W) uint32 bit plane the multi-target
+    kernels read: bit t of a pixel is set where masks[t] is non-zero there.  Masks may overlap."""
+    if not 1 <= len(masks) <= MAX_TARGETS:
+        raise ValueError(f"1 to {MAX_TARGETS} masks fit a bit plane, got {len(masks)}")
+    bits = np.zeros(np.asarray(masks[0]).shape, np.uint32)
+    for t, m in enumerate(masks):
+        m = np.asarray(m)
+        if m.shape != bits.shape:
+            raise ValueError(f"mask {t}: shape {m.shape} differs from mask 0's {bits.shape}")
+        bits |= (m != 0).astype(np.uint32) << np.uint32(t)
+    return bits
+
+
+class WOFTChainedMulti(WOFTChained):
+    """K planar targets of one template frame on ONE chained dense track: nothing MultiFlowTracker computes
+    depends on a template mask, so the K flows of a frame and their fold are shared and only the planar stage runs per target.
+
+        trk.init(frame0, [mask_a, mask_b, mask_c])     # K = 1..32 masks (a list, or a (K, H, W) array); may overlap
+        Hs, metas = trk.track(frame1)                  # Hs (K, 3, 3) float64; metas: a list of K namespaces
+
+    Hs[t] and metas[t] are what a WOFTChained built from the same config returns when it is initialised with mask t alone and fed
+    the same frames, bit for bit.  Each target has its own lost / N_lost / previous pose / last good pose: a target with fewer
+    than 4 surviving correspondences or a non-finite fit keeps its previous pose and is lost, the others are not affected, and no
+    exception of a target's fit leaves track().  Config keys and refusals are WOFTChained's.  Not provided: adding or removing a
+    target after init(), autograd.
+
+    The planar stage, by back end (`solver_decision` names the one in use; `meta.solver_decision` stays WOFTChained's text):
+      device solver, Sobol draw, least-squares / IRLS estimator (the presets): chain_tc_multi, tc_select_multi, hfit_batched,
+          inlier_frac_batched and one pinned read of one result block -- H (K, 9) | inlier fraction (K) | status (K) | selected and
+          kept counts (2, K) | histograms (K, 130), 143 K words: the batched fit writes its H and status as planes, so the block
+          is planes, not rows of 16.  The number of launches and the one read do not depend on K.
+      device solver with the RANSAC or the similarity (TRS) estimator: the same selection, then that estimator's single-element
+          launch on each target's slices, inlier_frac_batched and the one read.
+      device solver without a subsampler (counts can exceed the one-workgroup fit's 2048), or the config's own callables: a loop
+          of WOFTChained's single-target stage over per-target uint8 masks (K times its launches and reads)."""
+    _SOLVE_ERRORS = (Exception,)                  # (a target's failed fit keeps that target's previous pose; nothing escapes)
+    _TARGET_STATE = ("lost", "N_lost", "prev_H2init", "last_good_H2init", "_announced", "_template_mask_u8", "n_kept")
+
+    def __init__(self, config):
+        super().__init__(config)
+        self._single_decision = self.solver_decision
+        F = self._fused
+        if F is None or not F["n_draw"]:
+            self._route = "loop"
+            how = "a loop of the single-target stage (" + ("the config's own callables" if F is None else "no subsampler") + ")"
+        elif F.get("ransac") is not None or F.get("trs") is not None:
+            self._route = "select"
+            how = ("one batched selection, the " + ("RANSAC" if F.get("ransac") is not None else "TRS")
+                   + " estimator per target, one batched inlier test, one read")
+        else:
+            self._route = "batched"
+            how = "one batched selection, one batched fit, one batched inlier test, one read"
+        self.solver_decision += f"; multi-target planar stage: {how}"
+        self._targets = []
+        self._announced_targets = set()           # (as `_announced`: once per tracker, not once per init())
+        self._mb = {}                             # per (K, grid size): the buffers of the batched stage
+
+    def _decision_for_meta(self):
+        return self._single_decision
+
+    @staticmethod
+    def _check_masks(img, masks):
+        if isinstance(masks, torch.Tensor):
+            masks = masks.detach().cpu().numpy()
+        if isinstance(masks, np.ndarray):
+            if masks.ndim != 3:
+                raise ValueError(f"masks: a list of (H, W) masks or a (K, H, W) array is expected, got shape {masks.shape}")
+            masks = list(masks)
+        masks = [m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in masks]
+        if not 1 <= len(masks) <= MAX_TARGETS:
+            raise ValueError(f"init() takes 1 to {MAX_TARGETS} masks, got {len(masks)}")
+        hw = (int(img.shape[0]), int(img.shape[1]))
+        for t, m in enumerate(masks):
+            if m.shape != hw:
+                raise ValueError(f"target {t}: the mask's shape {m.shape} is not the frame's {hw}")
+            if m.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"target {t}: the mask's dtype {m.dtype} is not uint8 or bool")
+        return masks
+
+    def init(self, img, masks, img_identifier=None):
+        masks = self._check_masks(img, masks)
+        for t, m in enumerate(masks):
+            assert _count_components(m > 0) == 1, f"target {t}: the mask is not a single contour"       # (the parent's check)
+        super().init(img, masks[0], img_identifier)                  # (template, provider pins, the dense tracker: shared)
+        eye = self.prev_H2init
+        self._targets = [SimpleNamespace(lost=False, N_lost=0, prev_H2init=eye.copy(), last_good_H2init=eye.copy(),
+                                         _announced=t in self._announced_targets, n_kept=None,
+                                         _template_mask_u8=torch.from_numpy((m > 0).astype(np.uint8) * 255).to(self.device))
+                         for t, m in enumerate(masks)]
+        self._tbits = torch.from_numpy(pack_target_bits(masks).view(np.int32)).to(self.device)
+
+    # ---- per-target state: the single-target code runs with one target's state swapped in ---------------------------------------
+    def _as_target(self, t, fn):
+        T = self._targets[t]
+        for k in self._TARGET_STATE:
+            setattr(self, k, getattr(T, k))
+        try:
+            return fn()
+        finally:
+            for k in self._TARGET_STATE:
+                setattr(T, k, getattr(self, k))
+            if T._announced:
+                self._announced_targets.add(t)
+
+    def track(self, input_img, debug=False, img_identifier=None):
+        if not self._targets:
+            raise RuntimeError("WOFTChainedMulti.track() before init()")
+        self._n_tracked += 1
+        out = self.multi.track(input_img)                            # (the one dense track every target shares)
+        K = len(self._targets)
+        if self._route == "loop":
+            res = [self._as_target(t, lambda: self._planar_stage(out, input_img, img_identifier)) for t in range(K)]
+        else:
+            fits = self._planar_batched(out, input_img)
+
+            def finish(fit, n_kept, counts):
+                self.n_kept = n_kept
+                return self._finish(fit, counts, input_img, img_identifier)
+            res = [self._as_target(t, lambda: finish(*fits[t])) for t in range(K)]
+        return np.stack([H for H, _ in res]), [meta for _, meta in res]
+
+    def _multi_buffers(self, K, n_grid):
+        if (K, n_grid) not in self._mb:
+            F, cap = self._fused, 1024                               # (these routes have a Sobol draw: at most 1024 selected)
+            new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+            blk = torch.zeros(K * (13 + ops.CHAIN_HIST), dtype=torch.float32, device=self.device)
+            iblk = blk.view(torch.int32)
+            host = torch.empty(blk.numel(), dtype=torch.float32).pin_memory()
+            b = dict(ws=ops.tc_select_multi_ws(n_grid, K), pa=new(K, cap, 2), pb=new(K, cap, 2), w=new(K, cap), blk=blk, host=host,
+                     H=blk[:9 * K].view(K, 9), frac=blk[9 * K:10 * K], status=iblk[10 * K:11 * K],
+                     count=iblk[11 * K:13 * K].view(2, K), hist=iblk[13 * K:].view(K, ops.CHAIN_HIST), fit_ws=None,
+                     event=torch.cuda.Event())
+            # chain_tc_multi's outputs, reused; its histograms land in the result block
+            b["tc"] = (new(2, n_grid), new(1, n_grid) if self._wants_weights() else None, new(1, n_grid), b["hist"])
+            if F.get("ransac") is not None:
+                b["fit_ws"] = ops.ransac_ws(cap, F["ransac"]["max_iters"], self.device)
+            if F.get("trs") is not None:
+                b["fit_ws"] = ops.trs_ws(cap, F["trs"]["max_iters"], self.device)
+            self._mb = {(K, n_grid): b}
+        return self._mb[(K, n_grid)]
+
+    def _planar_batched(self, out, input_img):
+        """The planar stage of every target on one fold result -> [(fit | None, n_kept, histogram int64 numpy)] per target."""
+        F, K = self._fused, len(self._targets)
+        Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
+        gh, gw = int(out.flow.shape[1]), int(out.flow.shape[2])
+        b = self._multi_buffers(K, gh * gw)
+        dst, w, ok, _ = ops.chain_tc_multi(out.flow, out.cost, out.vis, out.sel, self._tbits, K, self.chain_vis_thr,
+                                           want_w=self._wants_weights(), mask_hw=(Hh, Ww), out=b["tc"])
+        weighted = F.get("weighted", True)
+        ops.tc_select_multi(dst, w if weighted else None, self._tbits, K, Hh, Ww, True, F["sobol_u"], ok, self._vis_mode,
+                            self._vis_thr, b["ws"], b["pa"], b["pb"], b["w"], b["count"], grid=(gh, gw))
+        sel = b["count"][0]
+        R, T = F.get("ransac"), F.get("trs")
+        if R is not None or T is not None:
+            fn, P = (ops.ransac, R) if R is not None else (ops.trs, T)
+            for t in range(K):
+                fn(b["pa"][t], b["pb"][t], b["H"][t], b["status"][t:t + 1], count=sel[t:t + 1], max_iters=P["max_iters"],
+                   thr=P["thr"], conf=P["conf"], ws=b["fit_ws"])
+        else:
+            ops.hfit_batched(b["pa"], b["pb"], b["w"] if weighted else None, b["H"], b["status"], counts=sel,
+                             reweight=F["reweight"], huber_k=F["huber_k"], n_irls=F["n_irls"])
+        ops.inlier_frac_batched(b["pa"], b["pb"], b["H"], b["frac"], thr=F["thr"], counts=sel)
+        # the frame's single device->host read: the whole result block into a pinned buffer, then wait for it
+        host = b["host"]
+        host.copy_(b["blk"], non_blocking=True)
+        b["event"].record()
+        t0 = time.perf_counter()
+        b["event"].synchronize()
+        self.host_wait_s += time.perf_counter() - t0
+        ih = host.view(torch.int32).numpy()
+        fh = host.numpy()
+        hist = ih[13 * K:].reshape(K, ops.CHAIN_HIST)
+        fits = []
+        for t in range(K):
+            fit = None
+            if int(ih[10 * K + t]) != 1:                             # (1: too few points for the estimator -- no fit)
+                verdict = F.get("const_verdict")
+                if verdict is None:
+                    verdict = bool(np.float32(fh[9 * K + t]) > np.float32(F["min_frac"]))
+                fit = _Fit(H=fh[9 * t:9 * t + 9].astype(np.float64).reshape(3, 3), success=bool(verdict))
+            fits.append((fit, int(ih[12 * K + t]), hist[t].astype(np.int64)))
+        return fits

@@ -120,6 +120,60 @@ __global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict_
     }
 }
 
+// chain_tc_kernel for n_targets masks held as one bit plane: the same pixel work and the same dst, w, ok;
+// the pixel's counter is the same for every target, its mask bits say which targets count it.  Per distinct counter of the wave,
+// one ballot per target gives that target's number of lanes; lane t keeps target t's, so the wave ends in ONE LDS atomic
+// instruction per distinct counter (lanes 0 .. n_targets-1, one counter each).  LDS: n_targets * 130 counters, 16 640 B at 32.
+__global__ __launch_bounds__(FC_T) void chain_tc_multi_kernel(const float* __restrict__ flow, const float* __restrict__ cost,
+                                                              const float* __restrict__ vis, const int32_t* __restrict__ sel,
+                                                              const uint32_t* __restrict__ tbits, int gh, int gw, int mw,
+                                                              int n_targets, float vis_thr, float* __restrict__ dst,
+                                                              float* __restrict__ w, float* __restrict__ ok,
+                                                              int32_t* __restrict__ hist) {
+    __shared__ int32_t bins[WOFT_MULTI_MAX_TARGETS * WOFT_CHAIN_HIST];
+    const int tid = (int)threadIdx.y * FC_TX + (int)threadIdx.x;
+    const int n_bins = n_targets * WOFT_CHAIN_HIST;
+    for (int k = tid; k < n_bins; k += FC_T) bins[k] = 0;
+    __syncthreads();
+    const uint32_t live = n_targets >= 32 ? 0xffffffffu : ((1u << n_targets) - 1u);
+    const int64_t plane = (int64_t)gh * gw;
+    const int x = (int)blockIdx.x * FC_TX + (int)threadIdx.x;
+    const bool in = x < gw;
+    for (int y = (int)blockIdx.y * FC_TY + (int)threadIdx.y; y < gh; y += (int)gridDim.y * FC_TY) {
+        int bin = -1;                                 // the counter this lane adds to (-1: none)
+        uint32_t bits = 0;                            // the targets whose mask holds this pixel
+        if (in) {
+            const int64_t i = (int64_t)y * gw + x;
+            const float fx = flow[i], fy = flow[plane + i], c = cost[i], v = vis[i];
+            const int32_t s = sel[i];
+            const bool valid = s >= 0 && s < WOFT_CHAIN_HIST - 2 && isfinite(fx) && isfinite(fy) && isfinite(c) && isfinite(v);
+            const bool seen = valid && !(v < vis_thr);                    // the fold's occlusion rule
+            dst[i] = valid ? (float)x + fx : NAN;
+            dst[plane + i] = valid ? (float)y + fy : NAN;
+            if (w != nullptr) w[i] = valid ? expf(-c) : 0.f;
+            ok[i] = seen ? 1.f : 0.f;
+            bits = tbits[(int64_t)y * mw + x] & live;
+            if (bits != 0) bin = !valid ? WOFT_CHAIN_HIST - 2 : (seen ? s : WOFT_CHAIN_HIST - 1);
+        }
+        uint64_t todo = __ballot(bin >= 0);
+        while (todo != 0) {
+            const int lead = __ffsll((unsigned long long)todo) - 1;
+            const int b = __shfl(bin, lead);
+            const bool here = bin == b;
+            int mine = 0;
+            for (int t = 0; t < n_targets; ++t) {
+                const uint64_t m = __ballot(here && ((bits >> t) & 1u));
+                if ((int)threadIdx.x == t) mine = (int)__popcll(m);
+            }
+            if (mine != 0) atomicAdd(&bins[(int)threadIdx.x * WOFT_CHAIN_HIST + b], mine);   // (mine != 0 only for lanes < n_targets)
+            todo &= ~__ballot(here);
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < n_bins; k += FC_T)
+        if (bins[k] != 0) atomicAdd(&hist[k], bins[k]);
+}
+
 // [a, a + na) and [b, b + nb) share a byte
 inline bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
     const uint64_t pa = (uint64_t)(uintptr_t)a, pb = (uint64_t)(uintptr_t)b;
@@ -184,5 +238,34 @@ extern "C" int woft_chain_tc(const float* flow, const float* cost, const float* 
     }
     hipLaunchKernelGGL(chain_tc_kernel, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tmask, gh, gw,
                        tmask ? mw : gw, vis_thr, dst, w, ok, hist);
+    return woft_launch_status();
+}
+
+extern "C" int woft_chain_tc_multi(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits,
+                                   int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t n_targets, float vis_thr, float* dst,
+                                   float* w, float* ok, int32_t* hist, void* stream) {
+    if (!flow || !cost || !vis || !sel || !tbits || !dst || !ok || !hist || bad_side(gh, gw)) return WOFT_EINVAL;
+    if (mh < gh || mw < gw || n_targets < 1 || n_targets > WOFT_MULTI_MAX_TARGETS) return WOFT_EINVAL;
+    if (!(vis_thr >= 0.f && vis_thr <= 1.f)) return WOFT_EINVAL;                                                  // (NaN fails)
+    // as woft_chain_tc: an output may share no byte with an input or with another output (overlap() lets a NULL through)
+    const uint64_t pb = (uint64_t)gh * (uint64_t)gw * 4u;
+    const uint64_t hist_bytes = (uint64_t)n_targets * WOFT_CHAIN_HIST * sizeof(int32_t);
+    const void* outs[4] = {dst, w, ok, hist};
+    const uint64_t nout[4] = {2 * pb, pb, pb, hist_bytes};
+    const void* ins[5] = {flow, cost, vis, sel, tbits};
+    const uint64_t nin[5] = {2 * pb, pb, pb, pb, (uint64_t)mh * (uint64_t)mw * 4u};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = 0; b < 5; ++b)
+            if (overlap(outs[a], nout[a], ins[b], nin[b])) return WOFT_EINVAL;
+        for (int b = a + 1; b < 4; ++b)
+            if (overlap(outs[a], nout[a], outs[b], nout[b])) return WOFT_EINVAL;
+    }
+    if (hipMemsetAsync(hist, 0, hist_bytes, (hipStream_t)stream) != hipSuccess) return WOFT_ELAUNCH;
+    // the grid of woft_chain_tc with a histogram: about one resident set of blocks, the row loop does the rest
+    dim3 grid = pixel_grid(gh, gw);
+    const unsigned rows = CHAIN_TC_BLOCKS / grid.x;
+    grid.y = grid.y < rows ? grid.y : (rows > 0 ? rows : 1u);
+    hipLaunchKernelGGL(chain_tc_multi_kernel, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tbits, gh, gw,
+                       mw, n_targets, vis_thr, dst, w, ok, hist);
     return woft_launch_status();
 }

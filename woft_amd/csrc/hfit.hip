@@ -587,15 +587,13 @@ __global__ __launch_bounds__(HT) void hfit_batched_bwd_kernel(const float* __res
                  (gw != nullptr) ? gw + off : nullptr, (status != nullptr) ? status + b : nullptr);
 }
 
-// frac[0] = mean_i( || proj(H, A_i) - B_i || <= thr )
-__global__ __launch_bounds__(HT) void inlier_frac_kernel(const float* __restrict__ pa, const float* __restrict__ pb,
-                                                         int n_max, const int* __restrict__ count,
-                                                         const float* __restrict__ H, float thr,
-                                                         float* __restrict__ frac) {
+// frac[0] = mean_i( || proj(H, A_i) - B_i || <= thr ) of ONE set of n correspondences by one workgroup: the body of
+// `inlier_frac_kernel` (one set per launch) and of `inlier_frac_batched_kernel` (one set per workgroup).  The sum is a count of
+// whole numbers in fp64: exact in any order.
+__device__ __forceinline__ void inlier_frac_one(const float* __restrict__ pa, const float* __restrict__ pb, int n,
+                                                const float* __restrict__ H, float thr, float* __restrict__ frac) {
     __shared__ double red[HT / 64];
     __shared__ double tot[1];
-    int n = n_max;
-    if (count != nullptr) n = min(count[0], n_max);
     float h[9];
     for (int i = 0; i < 9; ++i) h[i] = H[i];
     double c[1] = {0.0};
@@ -608,6 +606,27 @@ __global__ __launch_bounds__(HT) void inlier_frac_kernel(const float* __restrict
     }
     block_sum<1>(c, red, tot);
     if (threadIdx.x == 0) frac[0] = (n > 0) ? (float)(tot[0] / n) : 0.f;
+}
+
+__global__ __launch_bounds__(HT) void inlier_frac_kernel(const float* __restrict__ pa, const float* __restrict__ pb,
+                                                         int n_max, const int* __restrict__ count,
+                                                         const float* __restrict__ H, float thr,
+                                                         float* __restrict__ frac) {
+    int n = n_max;
+    if (count != nullptr) n = min(count[0], n_max);
+    inlier_frac_one(pa, pb, n, H, thr, frac);
+}
+
+// Workgroup b tests element b of a [batch][n_max] problem: rows [0, n_b) of its own slice, H[b], frac[b].
+__global__ __launch_bounds__(HT) void inlier_frac_batched_kernel(const float* __restrict__ pa, const float* __restrict__ pb,
+                                                                 int n_max, const int* __restrict__ counts,
+                                                                 const float* __restrict__ H, float thr,
+                                                                 float* __restrict__ frac) {
+    const int b = blockIdx.x;
+    const int64_t off = (int64_t)b * n_max;
+    int n = n_max;
+    if (counts != nullptr) n = min(counts[b], n_max);
+    inlier_frac_one(pa + 2 * off, pb + 2 * off, n, H + 9 * b, thr, frac + b);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1021,6 +1040,23 @@ extern "C" int woft_inlier_frac(const float* pa, const float* pb, int32_t n_max,
                                 float thr, float* frac, void* stream) {
     if (!pa || !pb || !H || !frac || n_max < 0) return WOFT_EINVAL;
     hipLaunchKernelGGL(inlier_frac_kernel, dim3(1), dim3(HT), 0, (hipStream_t)stream, pa, pb, n_max, count, H, thr,
+                       frac);
+    return woft_launch_status();
+}
+
+extern "C" int woft_inlier_frac_batched(const float* pa, const float* pb, int32_t batch, int32_t n_max, const int32_t* counts,
+                                        const float* H, float thr, float* frac, void* stream) {
+    if (!pa || !pb || !H || !frac || batch < 1 || batch > WOFT_HFIT_BATCH_MAX || n_max < 0) return WOFT_EINVAL;
+    // frac[b] is written while other elements' inputs are still unread: it may share no byte with an input
+    const uint64_t f0 = (uint64_t)(uintptr_t)frac, f1 = f0 + (uint64_t)batch * 4u;
+    const uint64_t pts = (uint64_t)batch * (uint64_t)n_max * 8u;
+    const void* ins[4] = {pa, pb, H, counts};
+    const uint64_t nin[4] = {pts, pts, (uint64_t)batch * 36u, (uint64_t)batch * 4u};
+    for (int k = 0; k < 4; ++k) {
+        const uint64_t a = (uint64_t)(uintptr_t)ins[k];
+        if (ins[k] != nullptr && a < f1 && f0 < a + nin[k]) return WOFT_EINVAL;
+    }
+    hipLaunchKernelGGL(inlier_frac_batched_kernel, dim3(batch), dim3(HT), 0, (hipStream_t)stream, pa, pb, n_max, counts, H, thr,
                        frac);
     return woft_launch_status();
 }

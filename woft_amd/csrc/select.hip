@@ -125,9 +125,10 @@ __global__ __launch_bounds__(256) void select_flags_kernel(const float* __restri
     if (threadIdx.x == 0) s.counts[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(1024) void select_plan_kernel(int* ws, int nb, const float* __restrict__ sobol_u, int n_draw,
-                                                           int cap, int* __restrict__ count) {
-    const Ws s = ws_layout(ws, nb);
+// The plan of ONE selection by one workgroup of 1024 threads: the body of `select_plan_kernel` (one selection per launch) and of
+// `select_plan_multi_kernel` (one per workgroup) -- one piece of integer code.  selected / kept: where count[0] / count[1] go.
+__device__ __forceinline__ void select_plan(const Ws s, int nb, const float* __restrict__ sobol_u, int n_draw, int cap,
+                                            int* __restrict__ selected, int* __restrict__ kept) {
     __shared__ int part[1024];
     __shared__ int keys[MAX_DRAW];
     __shared__ int carry_s;
@@ -188,9 +189,14 @@ __global__ __launch_bounds__(1024) void select_plan_kernel(int* ws, int nb, cons
         s.hdr[0] = N;
         s.hdr[1] = M;
         s.hdr[2] = all ? 1 : 0;
-        count[0] = M < cap ? M : cap;
-        count[1] = N;
+        selected[0] = M < cap ? M : cap;
+        kept[0] = N;
     }
+}
+
+__global__ __launch_bounds__(1024) void select_plan_kernel(int* ws, int nb, const float* __restrict__ sobol_u, int n_draw,
+                                                           int cap, int* __restrict__ count) {
+    select_plan(ws_layout(ws, nb), nb, sobol_u, n_draw, cap, count, count + 1);
 }
 
 template <bool VIS_WEIGHT>
@@ -239,6 +245,132 @@ __global__ __launch_bounds__(256) void select_gather_kernel(const float* __restr
     }
 }
 
+// ---- the same selection for n_targets template masks held as one bit plane ---------------------------------
+// Workspace: per target the header / counts / offsets / rank list of the single selection (MWS_T(nb) int32 each), then one uint32
+// of keep bits per pixel.  (a) the target-independent part of the keep rule once per pixel, AND-ed onto the pixel's mask bits;
+// per chunk and target a count, by ballots: no atomics; (b) workgroup t plans target t; (c) a chunk's workgroup reads its keep
+// bits once and walks the targets that kept anything in the chunk.
+constexpr int MAX_TARGETS = WOFT_MULTI_MAX_TARGETS;
+__host__ __device__ inline int64_t mws_stride(int nb) { return 4 + 2 * (int64_t)nb + MAX_DRAW; }
+__host__ __device__ inline int64_t mws_bits_at(int nb, int n_targets) { return (mws_stride(nb) * n_targets + 3) / 4 * 4; }   // (16 B)
+__host__ __device__ inline uint32_t* mws_bits(int* ws, int nb, int n_targets) { return (uint32_t*)(ws + mws_bits_at(nb, n_targets)); }
+
+template <bool GATE>
+__global__ __launch_bounds__(256) void select_flags_multi_kernel(const float* __restrict__ dst, const uint32_t* __restrict__ tbits,
+                                                                 Geo g, int n_targets, int check_dst, int* ws, int nb, Gate v) {
+    __shared__ int wcnt[4][MAX_TARGETS];
+    uint32_t* __restrict__ keepbits = mws_bits(ws, nb, n_targets);
+    const uint32_t live = n_targets >= 32 ? 0xffffffffu : ((1u << n_targets) - 1u);
+    const int64_t n = (int64_t)g.gh * g.gw;
+    const int64_t i0 = (int64_t)blockIdx.x * CHUNK + threadIdx.x * 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t f[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int64_t i = i0 + e;
+        if (i >= n) continue;
+        const int64_t mi = (g.gw == g.mw) ? i : (i / g.gw) * g.mw + (i % g.gw);
+        uint32_t bits = tbits[mi] & live;
+        if (bits != 0) {                                 // (the rest of keep_flag, with pwmask == NULL: the same for every target)
+            bool keep = true;
+            if (GATE) keep = v.vis[i] > v.thr;           // (NaN compares false: dropped)
+            if (keep && check_dst) {
+                const float dx = dst[i], dy = dst[n + i];
+                const bool oob = !(dx >= 0.f) || !(dy >= 0.f) || rintf(dx) >= (float)g.mw || rintf(dy) >= (float)g.mh;
+                keep = !oob;
+            }
+            if (!keep) bits = 0;
+        }
+        f[e] = bits;
+    }
+    if (i0 < n) {
+        if (i0 + 3 < n) *(uint4*)(keepbits + i0) = make_uint4(f[0], f[1], f[2], f[3]);
+        else for (int e = 0; e < 4 && i0 + e < n; ++e) keepbits[i0 + e] = f[e];
+    }
+    // per target: the wave's count by four ballots, kept by lane t; then the four waves' counts through LDS
+    int mine = 0;
+    for (int t = 0; t < n_targets; ++t) {
+        int c = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) c += (int)__popcll(__ballot((f[e] >> t) & 1u));
+        if (lane == t) mine = c;
+    }
+    if (lane < MAX_TARGETS) wcnt[wave][lane] = mine;
+    __syncthreads();
+    if ((int)threadIdx.x < n_targets) {
+        const int t = threadIdx.x;
+        ws[mws_stride(nb) * t + 4 + blockIdx.x] = wcnt[0][t] + wcnt[1][t] + wcnt[2][t] + wcnt[3][t];
+    }
+}
+
+__global__ __launch_bounds__(1024) void select_plan_multi_kernel(int* ws, int nb, int n_targets, const float* __restrict__ sobol_u,
+                                                                 int n_draw, int cap, int* __restrict__ count) {
+    const int t = blockIdx.x;
+    select_plan(ws_layout(ws + mws_stride(nb) * t, nb), nb, sobol_u, n_draw, cap, count + t, count + n_targets + t);
+}
+
+template <bool VIS_WEIGHT>
+__global__ __launch_bounds__(256) void select_gather_multi_kernel(const float* __restrict__ dst, const float* __restrict__ wgt,
+                                                                  int h, int w, int n_targets, const int* ws, int nb,
+                                                                  float* __restrict__ pa, float* __restrict__ pb,
+                                                                  float* __restrict__ wo, int cap, const float* __restrict__ vis) {
+    const uint32_t* __restrict__ keepbits = mws_bits(const_cast<int*>(ws), nb, n_targets);
+    const int64_t n = (int64_t)h * w;
+    const int64_t i0 = (int64_t)blockIdx.x * CHUNK + threadIdx.x * 4;
+    uint32_t bits[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (i0 + e < n) bits[e] = keepbits[i0 + e];
+    for (int t = 0; t < n_targets; ++t) {
+        const Ws s = ws_layout(const_cast<int*>(ws) + mws_stride(nb) * t, nb);
+        if (s.counts[blockIdx.x] == 0) continue;         // (uniform over the workgroup: target t kept nothing in this chunk)
+        int f[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[e] = (int)((bits[e] >> t) & 1u);
+        const int cnt = f[0] + f[1] + f[2] + f[3];
+        int total;
+        int rank = s.offsets[blockIdx.x] + block_exclusive_scan(cnt, &total);
+        const bool all = s.hdr[2] != 0;
+        const int M = s.hdr[1];
+        float* __restrict__ pa_t = pa + (int64_t)t * cap * 2;
+        float* __restrict__ pb_t = pb + (int64_t)t * cap * 2;
+        float* __restrict__ wo_t = (wo != nullptr) ? wo + (int64_t)t * cap : nullptr;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (!f[e]) continue;
+            const int r = rank++;
+            int slot = r;
+            if (!all) {                                  // binary search r in the sorted unique rank list
+                int lo = 0, hi = M - 1;
+                slot = -1;
+                while (lo <= hi) {
+                    const int mid = (lo + hi) >> 1;
+                    const int v = s.sel[mid];
+                    if (v == r) { slot = mid; break; }
+                    if (v < r) lo = mid + 1; else hi = mid - 1;
+                }
+            }
+            if (slot < 0 || slot >= cap) continue;
+            const int64_t i = i0 + e;
+            pa_t[2 * slot] = dst[i];
+            pa_t[2 * slot + 1] = dst[n + i];
+            pb_t[2 * slot] = (float)(i % w);
+            pb_t[2 * slot + 1] = (float)(i / w);
+            if (VIS_WEIGHT) {
+                if (wo_t != nullptr) wo_t[slot] = (wgt != nullptr) ? __fmul_rn(wgt[i], vis[i]) : vis[i];
+            } else {
+                if (wo_t != nullptr) wo_t[slot] = (wgt != nullptr) ? wgt[i] : 1.f;
+            }
+        }
+    }
+}
+
+// [a, a + na) and [b, b + nb) share a byte (a NULL shares none)
+inline bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uint64_t pa = (uint64_t)(uintptr_t)a, pb = (uint64_t)(uintptr_t)b;
+    return a != nullptr && b != nullptr && pa < pb + nb && pb < pa + na;
+}
+
 enum { VIS_NONE = 0, VIS_GATE = 1, VIS_WEIGHTED = 2 };
 
 int launch_flags(const float* dst, const uint8_t* tmask, const uint8_t* pwmask, int32_t gh, int32_t gw, int32_t mh, int32_t mw,
@@ -285,6 +417,58 @@ int launch_select(const float* dst, const float* w, const uint8_t* tmask, const 
 }
 
 }  // namespace
+
+extern "C" int64_t woft_tc_select_multi_ws_bytes(int64_t n, int32_t n_targets) {
+    if (n < 0 || n_targets < 1 || n_targets > MAX_TARGETS) return -1;
+    const int64_t nb = (n + CHUNK - 1) / CHUNK;
+    return (mws_bits_at((int)nb, n_targets) + (n + 3) / 4 * 4) * 4;
+}
+
+extern "C" int woft_tc_select_multi(const float* dst, const float* w, const uint32_t* tbits, int32_t gh, int32_t gw, int32_t mh,
+                                    int32_t mw, int32_t n_targets, int32_t check_dst, const float* sobol_u, int32_t n_draw,
+                                    const float* vis, int32_t vis_mode, float vis_thr, void* ws, float* pa, float* pb, float* wout,
+                                    int32_t cap, int32_t* count, void* stream) {
+    if (!dst || !tbits || !ws || !pa || !pb || !count || gh <= 0 || gw <= 0 || gh > mh || gw > mw || cap <= 0) return WOFT_EINVAL;
+    if (n_targets < 1 || n_targets > MAX_TARGETS) return WOFT_EINVAL;
+    if (n_draw < 0 || n_draw > MAX_DRAW || (n_draw > 0 && !sobol_u)) return WOFT_EINVAL;
+    if (vis_mode < VIS_NONE || vis_mode > VIS_WEIGHTED || vis_thr != vis_thr) return WOFT_EINVAL;
+    if (vis == nullptr) vis_mode = VIS_NONE;
+    const int64_t n = (int64_t)gh * gw;
+    if (n > ((int64_t)1 << 31) - CHUNK) return WOFT_EINVAL;      // (ranks and counts are int32)
+    const int nb = (int)((n + CHUNK - 1) / CHUNK);
+    // the outputs are written while inputs are still unread: none may share a byte with an input or with another output
+    const uint64_t slots = (uint64_t)n_targets * (uint64_t)cap;
+    const void* outs[5] = {pa, pb, wout, count, ws};
+    const uint64_t nout[5] = {slots * 8u, slots * 8u, slots * 4u, (uint64_t)n_targets * 8u,
+                              (uint64_t)woft_tc_select_multi_ws_bytes(n, n_targets)};
+    const void* ins[5] = {dst, w, vis, tbits, sobol_u};
+    const uint64_t nin[5] = {(uint64_t)n * 8u, (uint64_t)n * 4u, (uint64_t)n * 4u, (uint64_t)mh * (uint64_t)mw * 4u,
+                             (uint64_t)n_draw * 4u};
+    for (int a = 0; a < 5; ++a) {
+        for (int b = 0; b < 5; ++b)
+            if (overlap(outs[a], nout[a], ins[b], nin[b])) return WOFT_EINVAL;
+        for (int b = a + 1; b < 5; ++b)
+            if (overlap(outs[a], nout[a], outs[b], nout[b])) return WOFT_EINVAL;
+    }
+    const Geo g = {gh, gw, mh, mw};
+    const Gate v = {vis, vis_thr};
+    hipStream_t s = (hipStream_t)stream;
+    if (vis_mode == VIS_GATE)
+        hipLaunchKernelGGL(select_flags_multi_kernel<true>, dim3(nb), dim3(256), 0, s, dst, tbits, g, n_targets, check_dst, (int*)ws,
+                           nb, v);
+    else
+        hipLaunchKernelGGL(select_flags_multi_kernel<false>, dim3(nb), dim3(256), 0, s, dst, tbits, g, n_targets, check_dst, (int*)ws,
+                           nb, v);
+    hipLaunchKernelGGL(select_plan_multi_kernel, dim3(n_targets), dim3(1024), 0, s, (int*)ws, nb, n_targets, sobol_u, n_draw, cap,
+                       count);
+    if (vis_mode == VIS_WEIGHTED)
+        hipLaunchKernelGGL(select_gather_multi_kernel<true>, dim3(nb), dim3(256), 0, s, dst, w, gh, gw, n_targets, (const int*)ws, nb,
+                           pa, pb, wout, cap, vis);
+    else
+        hipLaunchKernelGGL(select_gather_multi_kernel<false>, dim3(nb), dim3(256), 0, s, dst, w, gh, gw, n_targets, (const int*)ws, nb,
+                           pa, pb, wout, cap, vis);
+    return woft_launch_status();
+}
 
 extern "C" int64_t woft_tc_select_ws_bytes(int64_t n) {
     const int64_t nb = (n + CHUNK - 1) / CHUNK;

@@ -778,6 +778,46 @@ def chain_tc(flow, cost, vis, sel, tmask_u8, vis_thr, want_w=True, mask_hw=None,
     return dst, wout, ok, hist
 
 
+MULTI_MAX_TARGETS = 32  # WOFT_MULTI_MAX_TARGETS: the targets of one bit plane (uint32 per pixel)
+
+
+def _check_tbits(tbits, mh, mw, n_targets):
+    if not 1 <= int(n_targets) <= MULTI_MAX_TARGETS:
+        raise ValueError(f"n_targets must be in [1, {MULTI_MAX_TARGETS}], got {n_targets!r}")
+    # (torch has no unsigned 32-bit arithmetic worth the name: the plane travels as int32 with the same bits)
+    assert tbits.dtype == torch.int32 and tbits.is_contiguous() and tbits.is_cuda and tbits.numel() == mh * mw
+
+
+def chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=True, mask_hw=None, out=None):
+    """chain_tc for n_targets template masks at once (woft_chain_tc_multi) -> (dst (2, n), w (1, n) | None,
+    ok (1, n), hist (n_targets, 130) int32).  tbits: the masks as one bit plane, an int32 device tensor of mask_hw = (mh, mw) >=
+    (H, W) elements (default the grid's size), bit t set where the pixel lies in target t's mask.  dst, w, ok: chain_tc's bytes;
+    hist[t]: chain_tc's for a uint8 mask equal to bit t.  out: the tuple of an earlier call at this size, reused (its hist may
+    be a view into a larger result block)."""
+    assert flow.dim() == 3 and flow.shape[0] == 2 and _f32c(flow)
+    h, w = flow.shape[1:]
+    n = h * w
+    assert all(_f32c(t) and t.numel() == n for t in (cost, vis))
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.is_cuda and sel.numel() == n
+    vis_thr = float(vis_thr)
+    if not (0.0 <= vis_thr <= 1.0):
+        raise ValueError(f"chain_tc_multi: vis_thr must be in [0, 1], got {vis_thr!r}")
+    mh, mw = mask_hw or (h, w)
+    _check_tbits(tbits, mh, mw, n_targets)
+    if out is None:
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=flow.device)
+        out = (new(2, n), new(1, n) if want_w else None, new(1, n),
+               torch.empty(n_targets, CHAIN_HIST, dtype=torch.int32, device=flow.device))
+    dst, wout, ok, hist = out
+    if not want_w:
+        wout = None
+    assert _f32c(dst, 2, n) and _f32c(ok, 1, n) and (wout is None or _f32c(wout, 1, n))
+    assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda and hist.numel() == n_targets * CHAIN_HIST
+    check(_lib.load().woft_chain_tc_multi(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tbits), h, w, mh, mw, int(n_targets), vis_thr,
+                                          ptr(dst), ptr(wout), ptr(ok), ptr(hist), stream_ptr()), "woft_chain_tc_multi")
+    return dst, wout, ok, hist
+
+
 def coords_update(coords, delta, ld_delta, wf, flow4=None, flow_cat=None, ld_cat=0):
     check(_lib.load().woft_coords_update(ptr(coords), ptr(delta), ld_delta, wf, coords.shape[0], ptr(flow4),
                                          ptr(flow_cat), ld_cat, stream_ptr()), "woft_coords_update")
@@ -1148,6 +1188,34 @@ def tc_select_vis(dst, w, tmask_u8, pwmask_u8, h, wimg, check_dst, sobol_u, vis,
                                          ptr(wout), pa.shape[0], ptr(count), stream_ptr()), "woft_tc_select_vis")
 
 
+def tc_select_multi_ws(n, n_targets):
+    need = int(_lib.load().woft_tc_select_multi_ws_bytes(int(n), int(n_targets)))
+    if need < 0:
+        raise _lib.WoftHipError(f"woft_tc_select_multi_ws_bytes({n}, {n_targets}) rejected its arguments")
+    return torch.empty(need, dtype=torch.uint8, device=DEV)
+
+
+def tc_select_multi(dst, w, tbits, n_targets, h, wimg, check_dst, sobol_u, vis, vis_mode, vis_thr, ws, pa, pb, wout, count,
+                    grid=None):
+    """tc_select_vis for n_targets template masks at once (woft_tc_select_multi).  tbits: the bit plane of
+    chain_tc_multi (int32, h * wimg elements); pa, pb (n_targets, cap, 2), wout (n_targets, cap) or None, count (2, n_targets)
+    int32: row 0 the selected counts (the `counts` of hfit_batched), row 1 the kept ones.  The first count[0, t] rows of target
+    t's slices are what tc_select_vis writes for a uint8 mask equal to bit t and no pwmask."""
+    n_draw = 0 if sobol_u is None else sobol_u.numel()
+    gh, gw = grid or (h, wimg)
+    _check_tbits(tbits, h, wimg, n_targets)
+    assert dst.numel() == 2 * gh * gw and (w is None or w.numel() == gh * gw)
+    assert vis is None or (vis.numel() == gh * gw and vis.dtype == torch.float32)
+    cap = pa.shape[1]
+    assert tuple(pa.shape) == tuple(pb.shape) == (n_targets, cap, 2) and pa.is_contiguous() and pb.is_contiguous()
+    assert wout is None or (tuple(wout.shape) == (n_targets, cap) and wout.is_contiguous())
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == 2 * n_targets
+    mode = VIS_MODES[vis_mode] if isinstance(vis_mode, str) else int(vis_mode or 0)
+    check(_lib.load().woft_tc_select_multi(ptr(dst), ptr(w), ptr(tbits), gh, gw, h, wimg, int(n_targets), int(check_dst),
+                                           ptr(sobol_u), n_draw, ptr(vis), mode, float(vis_thr), ptr(ws), ptr(pa), ptr(pb),
+                                           ptr(wout), cap, ptr(count), stream_ptr()), "woft_tc_select_multi")
+
+
 def tc_flags_vis(dst, tmask_u8, pwmask_u8, h, wimg, check_dst, vis, vis_mode, vis_thr, grid=None, out=None):
     """The keep rule of tc_select_vis alone -> bool tensor (gh*gw,) (woft_tc_flags_vis): gated in mode 'gate' only."""
     gh, gw = grid or (h, wimg)
@@ -1279,3 +1347,14 @@ def trs(pa, pb, Hout, status, count=None, max_iters=10000, thr=3.0, conf=0.999, 
 def inlier_frac(pa, pb, Hm, frac, thr=5.0, count=None):
     check(_lib.load().woft_inlier_frac(ptr(pa), ptr(pb), pa.shape[0], ptr(count), ptr(Hm), float(thr), ptr(frac),
                                        stream_ptr()), "woft_inlier_frac")
+
+
+def inlier_frac_batched(pa, pb, Hm, frac, thr=5.0, counts=None):
+    """B inlier tests in one launch (woft_inlier_frac_batched): pa, pb (B, N, 2), Hm (B, 9) or (B, 3, 3), frac (B,), counts (B,)
+    int32 or None -- contiguous, on one device.  Element b gets the bits of inlier_frac() on element b alone."""
+    B, n = pa.shape[0], pa.shape[1]
+    assert tuple(pb.shape) == (B, n, 2) and pa.is_contiguous() and pb.is_contiguous() and Hm.is_contiguous() and frac.is_contiguous()
+    assert Hm.numel() == 9 * B and frac.numel() == B and (counts is None or (counts.dtype == torch.int32 and counts.numel() == B
+                                                                              and counts.is_contiguous()))
+    check(_lib.load().woft_inlier_frac_batched(ptr(pa), ptr(pb), B, n, ptr(counts), ptr(Hm), float(thr), ptr(frac), stream_ptr()),
+          "woft_inlier_frac_batched")

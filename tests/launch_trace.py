@@ -11,6 +11,12 @@ tests/golden/launch_traces.json holds, per scenario and per call, "<entry point>
 CRC32 of the scenario's outputs where two runs of the recording commit agreed on it.  The fixture is a record of what the engine
 launched at the commit BEFORE a change of the host code (`python tests/launch_trace.py --record` there): a refactor of the host
 code passes against it unchanged; a change that moves launches on purpose re-records it and shows the moved launches in its diff.
+
+The tracker scenarios (tracker_*, window_lost, chained*) run a whole tracker for three frames.  Their fixture entries hold only the
+lines of the entry points outside the engine (PLANAR below) and of everything FlowProvider.finish_weights calls; pointers are
+still numbered over the WHOLE trace, engine calls included, so a kept line's aliasing with the engine's buffers is pinned too.
+Between those lines stands one "d2h" line per device-to-host copy of the track() calls (d2h_copies), in program order: the number
+of reads per frame is part of the trace.
 """
 import ctypes as C
 import json
@@ -36,6 +42,7 @@ class LibProxy:
 
     def __init__(self, lib):
         self._real, self.calls, self._ids = lib, [], {}
+        self.only, self.inside = None, 0         # tracker scenarios: keep calls of these name prefixes, or made while `inside`
 
     def _pointer(self, v):
         v = v.value if isinstance(v, C.c_void_p) else v
@@ -65,7 +72,10 @@ class LibProxy:
 
         def call(*args):
             assert len(args) == len(sig[1]), name
-            self.calls.append((name, [self._value(t, a) for t, a in zip(sig[1], args)], _summary(args)))
+            canon = [self._value(t, a) for t, a in zip(sig[1], args)]      # (always: pointers are numbered over the whole trace)
+            # (a *_ws_bytes size query is no launch, and a scratch cached per process asks only once)
+            if self.only is None or self.inside or (name.startswith(self.only) and not name.endswith("_ws_bytes")):
+                self.calls.append((name, canon, _summary(args)))
             return fn(*args)
         self.__dict__[name] = call
         return call
@@ -194,6 +204,178 @@ def flow_region(patch):
     return out
 
 
+# ---- tracker scenarios: the planar stage of every tracker class and back end --------------------------------------------------
+PLANAR = ("woft_tc_", "woft_hfit", "woft_inlier_frac", "woft_ransac", "woft_trs", "woft_chain_tc", "woft_flow_fb",
+          "woft_warp_perspective", "woft_crop_u8", "woft_mask_bbox", "woft_wh_needed")
+
+
+def d2h_copies(patch, on_copy):
+    """For as long as `patch` (a pytest MonkeyPatch) holds: on_copy(name) after every device-to-host copy made through
+    Tensor.cpu / .item / .tolist / .to / .copy_."""
+    T = torch.Tensor
+    real = {n: getattr(T, n) for n in ("cpu", "item", "tolist", "copy_", "to")}
+
+    def d2h(name, is_copy):
+        def wrapped(self, *a, **kw):
+            out = real[name](self, *a, **kw)
+            if is_copy(self, a, out):
+                on_copy(name)
+            return out
+        return wrapped
+    from_dev = lambda self, a, out: self.is_cuda
+    patch.setattr(T, "cpu", d2h("cpu", from_dev))
+    patch.setattr(T, "item", d2h("item", from_dev))
+    patch.setattr(T, "tolist", d2h("tolist", from_dev))
+    patch.setattr(T, "to", d2h("to", lambda self, a, out: self.is_cuda and not out.is_cuda))
+    patch.setattr(T, "copy_", d2h("copy_", lambda self, a, out: not self.is_cuda and a[0].is_cuda))
+
+
+def _never():
+    from woft_amd import presets
+    return presets.redetection_by_inliers(1e-6, 0.999)               # (a re-detection test no fit satisfies)
+
+
+def _tracked(trk, frames, before=None):
+    """track() over the frames with the planar filter and the read recorder on -> the scenario's outputs: every H as a float64
+    tensor, lost / N_lost / n_kept (-1: None or no such field) as one int64 tensor per frame."""
+    import pytest
+    proxy = _lib._lib
+    proxy.only = PLANAR
+    fl = trk.flower
+    if hasattr(fl, "finish_weights"):
+        inner = fl.finish_weights
+
+        def finish_weights(*a, **kw):
+            proxy.inside += 1
+            try:
+                return inner(*a, **kw)
+            finally:
+                proxy.inside -= 1
+        fl.finish_weights = finish_weights
+    outs = []
+    for k, f in enumerate(frames, 1):
+        if before is not None:
+            before(k)
+        with pytest.MonkeyPatch.context() as p:
+            d2h_copies(p, lambda name: proxy.calls.append(("d2h", [], name)))
+            H, meta = trk.track(f)
+        metas = meta if isinstance(meta, list) else [meta]
+        ints = [[int(m.lost), int(m.N_lost), -1 if getattr(m, "n_kept", None) is None else int(m.n_kept)] for m in metas]
+        ints.append([-1 if trk.n_kept is None else int(trk.n_kept)] * 3)
+        outs += [torch.from_numpy(np.array(H, np.float64)), torch.tensor(ints, dtype=torch.int64)]
+    return outs
+
+
+_POOLS = []
+
+
+def _private_pool(run):
+    """Tracker scenarios free and allocate per frame (the cloned frame, the carried mask, a window's crops), and a pointer's
+    number says which freed block a later allocation got.  In the process's shared caching allocator that depends on every
+    tensor any earlier test left alive or cached; so the whole scenario allocates from a memory pool of its own, new and empty,
+    where it depends on the scenario's own sequence of allocations alone."""
+    def in_pool(patch):
+        import gc
+        from woft_amd import ops
+        for name in ("_BBOX_WS", "_HFIT_WS", "_RANSAC_WS", "_TRS_WS"):     # (the process's scratch caches: the scenario makes
+            patch.setattr(ops, name, {})                                   #  its own, in its pool, whatever ran before)
+        gc.collect()
+        torch.cuda.synchronize()
+        pool = torch.cuda.MemPool()
+        _POOLS.append(pool)                                          # (kept: a tensor that outlives the scenario keeps its memory)
+        with torch.cuda.use_mem_pool(pool):
+            try:
+                return run(patch)
+            finally:
+                gc.collect()                                         # (the scenario's tensors go back to its pool, not to the next one's)
+                torch.cuda.synchronize()
+    return in_pool
+
+
+def _tracker_scenario(cfg, edit=None, check=None, lost_from=None, mh=None):
+    """A shipped tracker config on the synthetic checkpoint, 128 x 160, iters 1, no graph, three frames.  lost_from: the first
+    frame from which the re-detection test always fails (the config is edited and _fused_specs() called again; the earlier spec
+    is kept alive, so its Sobol table's address is not handed out again)."""
+    def run(patch):
+        from pytracking.utils.config import load_config
+        conf = load_config(ROOT / "pytracking" / "configs" / cfg)
+        fc = conf.flow_config
+        fc.model = synth.make_state_dict(seed=7, **(dict(mask_head_structure=mh) if mh else {}))
+        fc.iters, fc.graph = 1, False
+        if edit is not None:
+            edit(conf)
+        trk = conf.tracker_class(conf)
+        trk.flower.defer_min_ratio = 0                               # (the sparse weight head at this small size too)
+        template, *frames = _pair(128, 160, 4, 4)
+        trk.init(template, synth.make_init_mask(128, 160))
+        if check is not None:
+            check(trk)
+        kept = []
+
+        def before(k):
+            if k == lost_from:
+                kept.append(trk._fused)
+                conf.redet_success_fn = _never()
+                trk._fused = trk._fused_specs()
+        return _tracked(trk, frames, before)
+    return _private_pool(run)
+
+
+def _set(**kw):
+    def edit(conf):
+        for k, v in kw.items():
+            setattr(conf, k, v)
+    return edit
+
+
+def _is(**want):
+    def check(trk):
+        for k, v in want.items():
+            got = getattr(trk, k)
+            assert (got is not None) == v if k == "_fused" else got == v, (k, got, v)
+    return check
+
+
+def _visibility_gate(conf):
+    conf.flow_config.raft_type = "weighted_masked"
+    conf.visibility_mode = "gate"
+
+
+def _chained_scenario(multi, **kw):
+    """The chained trackers on the stub provider and the sizes of tests/chained_multi_util.py (48 x 64, deltas (None, 1, 2, 4));
+    the stub's flows are kept alive for the scenario, as the frames are."""
+    def run(patch):
+        import chained_multi_util as U
+        patch.setenv("WOFT_FUSED", "1")
+        keep = []
+
+        class Keeping(U.AffineProvider):
+            def compute_flow(self, *a, **k):
+                out = super().compute_flow(*a, **k)
+                keep.append(out)
+                return out
+        sub = kw.get("subsampler_fn", True)
+        conf = U.stub_config(multi, estimator=kw.get("estimator"))
+        conf.flow_config.of_class = lambda fc: Keeping(fc)
+        if sub is None:
+            conf.subsampler_fn = None
+        trk = conf.tracker_class(conf)
+        frame0, frames = U.stub_frames()
+        masks = U.stub_masks()
+        trk.init(frame0, masks if multi else masks[0])
+        if multi:
+            assert trk._route == kw["route"], trk._route
+        outs = _tracked(trk, frames[:3])
+        del keep[:]
+        return outs
+    return _private_pool(run)
+
+
+def _ransac():
+    from woft_amd import presets
+    return presets.estimator_ransac(10000, 3.0, 0.995)
+
+
 SCENARIOS = {
     "full_bf16x3_otf": full_bf16x3_otf,
     "full_fp32": lambda patch: _one_flow(patch, iters=2, precision="fp32"),
@@ -206,6 +388,21 @@ SCENARIOS = {
     "generic_weight_head": lambda patch: _one_flow(patch, iters=2, precision="bf16x3", wh=[(64, 5), (32, 3)],
                                                    sd=dict(weight_head_structure=[(64, 5), (32, 3)])),
     "flow_region": flow_region,
+    "tracker_wlsq": _tracker_scenario("WOFT.py", check=_is(_sparse_weights=True, _fused=True), lost_from=2),
+    "tracker_irls": _tracker_scenario("WOFT_IRLS.py", check=_is(_fused=True)),
+    "tracker_ransac": _tracker_scenario("WOFT_RANSAC.py", check=_is(_fused=True)),
+    "tracker_trs": _tracker_scenario("WOFT_TRS.py", check=_is(_fused=True)),
+    "tracker_visibility_gate": _tracker_scenario("WOFT_visibility.py", edit=_visibility_gate, mh=[(128, 3), (128, 3)],
+                                                 check=_is(_fused=True, _vis_mode="gate")),
+    "tracker_fbcheck": _tracker_scenario("WOFT_fbcheck.py", check=_is(_fused=True, fb_check="gate")),
+    "tracker_nodraw": _tracker_scenario("WOFT.py", edit=_set(subsampler_fn=None), check=_is(_fused=True)),
+    "tracker_callables": _tracker_scenario("WOFT.py", edit=_set(device_solver=False), check=_is(_fused=False)),
+    "window_lost": _tracker_scenario("WOFT_window.py", edit=lambda conf: setattr(conf, "redet_success_fn", _never()),
+                                     check=_is(_fused=True)),
+    "chained": _chained_scenario(False),
+    "chained_multi_batched": _chained_scenario(True, route="batched"),
+    "chained_multi_select": lambda patch: _chained_scenario(True, route="select", estimator=_ransac())(patch),
+    "chained_multi_loop": _chained_scenario(True, route="loop", subsampler_fn=None),
 }
 
 

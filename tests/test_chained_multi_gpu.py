@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import chained_multi_util as U  # noqa: E402
+from launch_trace import d2h_copies  # noqa: E402
 from woft_amd import _lib, ops, presets, synth  # noqa: E402
 from woft_amd.chained import pack_target_bits  # noqa: E402
 
@@ -323,22 +324,7 @@ def _trace_one_track(monkeypatch, K):
     with pytest.MonkeyPatch.context() as patch:
         proxy = U.CountingLib(_lib.load())
         patch.setattr(_lib, "_lib", proxy)
-        T = torch.Tensor
-        real = {n: getattr(T, n) for n in ("cpu", "item", "tolist", "copy_", "to")}
-
-        def d2h(name, is_copy):
-            def wrapped(self, *a, **kw):
-                out = real[name](self, *a, **kw)
-                if is_copy(self, a, out):
-                    copies.append(name)
-                return out
-            return wrapped
-        from_dev = lambda self, a, out: self.is_cuda
-        patch.setattr(T, "cpu", d2h("cpu", from_dev))
-        patch.setattr(T, "item", d2h("item", from_dev))
-        patch.setattr(T, "tolist", d2h("tolist", from_dev))
-        patch.setattr(T, "to", d2h("to", lambda self, a, out: self.is_cuda and not out.is_cuda))
-        patch.setattr(T, "copy_", d2h("copy_", lambda self, a, out: not self.is_cuda and a[0].is_cuda))
+        d2h_copies(patch, copies.append)
         Hs, metas = trk.track(frames[1])
         torch.cuda.synchronize()
     assert Hs.shape == (K, 3, 3) and not any(m.lost for m in metas)

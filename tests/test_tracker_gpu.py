@@ -279,9 +279,9 @@ def test_weight_head_on_the_drawn_correspondences_only(cfg):
             res.append((Hm, meta.lost, meta.N_lost))
             assert trk.flower.weights_deferred == sparse          # (the last flow of the frame was the template's)
             if t == 1:
-                b = trk._fb
-                n = int(b["res"].view(torch.int32)[12])
-                sel[sparse] = (b["pa"][:n].clone(), b["pb"][:n].clone(), b["w"][:n].clone())
+                (b,) = trk._buffers.values()
+                n = int(b.block.selected[0])
+                sel[sparse] = (b.pa[:n].clone(), b.pb[:n].clone(), b.w[:n].clone())
         outs[sparse] = res
         if sparse:
             plan = trk.flower.engine.plan(*[(d + 7) // 8 * 8 for d in (H, W)])
@@ -496,7 +496,8 @@ def test_tracker_without_subsampler_fits_every_kept_correspondence(monkeypatch):
         trk.init(template, mask)
         outs[fused] = [trk.track(f) for f in frames]
         if fused:
-            assert trk._fb["fit_ws"] is not None and trk._fb["pa"].shape[0] == H * W
+            (b,) = trk._buffers.values()
+            assert b.fit_ws is not None and b.pa.shape[0] == H * W
     for (Ha, ma), (Hb, mb) in zip(outs[True], outs[False]):
         assert ma.lost == mb.lost and bool(ma.global_H_success) == bool(mb.global_H_success)
         assert np.array_equal(Ha, Hb), np.abs(Ha - Hb).max()

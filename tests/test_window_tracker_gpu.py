@@ -206,7 +206,7 @@ def test_forty_lost_frames_with_a_drifting_box_keep_the_plans_bounded(monkeypatc
     assert len(shapes) > trk.PLAN_BOUND + 2, shapes                            # (the sequence does what it is meant to do)
     assert peak == trk.PLAN_BOUND + 1, (peak, sorted(trk.flower.engine._plans))     # the pinned global window + the bound, reached
     assert first_key not in trk.flower.engine._plans and key in trk.flower.engine._plans     # eviction happened: oldest gone, newest kept
-    assert len(trk.flower._out) <= trk.PLAN_BOUND + 1 and len(trk._fb_cache) <= trk.PLAN_BOUND + 1
+    assert len(trk.flower._out) <= trk.PLAN_BOUND + 1 and len(trk._buffers) <= trk.PLAN_BOUND + 1
     assert (trk._rect[2] + 7) // 8 * 8 in [k[0] for k in trk.flower.engine._plans if len(k) == 2]     # the global plan survived
 
 

@@ -19,15 +19,16 @@ K planar targets on one dense track: the fold is shared, 
 (woft_chain_tc_multi, woft_tc_select_multi, woft_hfit_batched, woft_inlier_frac_batched, one read).
 """
 import logging
-import time
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import ops
+from .config import config_get, config_set
 from .multiflow import MultiFlowTracker, _check_constants, _dev32
-from .tracker import YAOFTrackerSingleControl, _count_components, _Fit
+from .planar import BoundedCache, PlanarBuffers, decode, fit_and_judge
+from .tracker import YAOFTrackerSingleControl, _count_components
 
 logger = logging.getLogger(__name__)
 
@@ -80,17 +81,6 @@ def chain_correspondences(result, mask=None, vis_thr=0.5, weights=True):
     return SimpleNamespace(dst=dst.to(dev), w=None if wts is None else wts.to(dev), ok=ok.to(dev), hist=hist.to(dev))
 
 
-def _set(config, key):
-    """Whether a config key is present and truthy (an absent key reads as an empty, falsy Config)."""
-    v = getattr(config, key)
-    return not isinstance(v, type(config)) and bool(v)
-
-
-def _get(config, key, default):
-    v = getattr(config, key)
-    return default if (isinstance(v, type(config)) or v is None) else v
-
-
 class WOFTChained(YAOFTrackerSingleControl):
     """YAOFTrackerSingleControl whose correspondences are MultiFlowTracker's chains (this project's own, no counterpart in the
     reference): per frame the K flows of `chain_deltas` are folded into the per-pixel most reliable chain template -> frame, one
@@ -111,6 +101,7 @@ class WOFTChained(YAOFTrackerSingleControl):
     chain_invalid, chain_occluded (mask pixels without a valid chain / with an occluded one)."""
     MASK_NEEDS_VISIBILITY_MODE = False            # ('weighted_masked' without a visibility_mode: the fold reads the mask)
 
+    REFUSED_BY = "chained tracker"
     REFUSED = (
         ("visibility_mode", "the fold consumes the visibility mask of a 'weighted_masked' flow config itself (chain_vis_thr)"),
         ("fb_check", "the solver's one visibility slot carries the chains' occlusion gate"),
@@ -120,19 +111,19 @@ class WOFTChained(YAOFTrackerSingleControl):
         ("post_hoc_weights_postprocessing_fn", "the fit weight is exp(-chain cost), not a weight map to post-process"),
     )
 
-    def __init__(self, config):
-        for key, why in self.REFUSED:
-            if _set(config, key):
-                raise NotImplementedError(f"{key} is not provided by the chained tracker: {why}")
-        if _set(config.flow_config, "weights_postprocessing_fn"):
+    def _refusals(self, config):
+        super()._refusals(config)
+        if config_set(config.flow_config, "weights_postprocessing_fn"):
             raise NotImplementedError("the chained tracker's chain cost is defined on the raw reliability logit; a flow config with "
                                       "a weights_postprocessing_fn is not supported")
-        self.chain_deltas = _get(config, "chain_deltas", DEFAULT_DELTAS)
-        self.chain_vis_thr = _get(config, "chain_vis_thr", 0.5)
-        self.chain_unit_cost = _get(config, "chain_unit_cost", 1.0)
-        self.chain_iters = _get(config, "chain_iters", None)
-        self.chain_weights = bool(_get(config, "chain_weights", True))
-        self.chain_share_features = bool(_get(config, "chain_share_features", False))
+
+    def __init__(self, config):
+        self.chain_deltas = config_get(config, "chain_deltas", DEFAULT_DELTAS)
+        self.chain_vis_thr = config_get(config, "chain_vis_thr", 0.5)
+        self.chain_unit_cost = config_get(config, "chain_unit_cost", 1.0)
+        self.chain_iters = config_get(config, "chain_iters", None)
+        self.chain_weights = bool(config_get(config, "chain_weights", True))
+        self.chain_share_features = bool(config_get(config, "chain_share_features", False))
         super().__init__(config)
         if not hasattr(self.flower, "pin_source"):
             raise NotImplementedError("the chained tracker needs this project's flow provider (pin_source, compute_flow(mode='flow', "
@@ -146,8 +137,8 @@ class WOFTChained(YAOFTrackerSingleControl):
             self._fused = dict(self._fused, weighted=False)
         # the solver's visibility slot carries the chains' 0 / 1 occlusion gate, the way fb_check hands its verdict
         self._vis_mode, self._vis_thr = "gate", 0.5
-        self._tc = {}                             # per grid size: the outputs of chain_tc, reused
-        self._grid = {}                           # per grid size: the (2, n) int64 source grid (callable back end only)
+        self._tc = BoundedCache()                 # grid size: the outputs of chain_tc, reused
+        self._grid = BoundedCache()               # grid size: the (2, n) int64 source grid (callable back end only)
 
     def _new_multi(self):
         return MultiFlowTracker(self.flower, deltas=self.chain_deltas, vis_thr=self.chain_vis_thr, unit_cost=self.chain_unit_cost,
@@ -175,61 +166,55 @@ class WOFTChained(YAOFTrackerSingleControl):
                                   "ring of stored frames the chains reach back to")
 
     def _source_grid(self, gh, gw):
-        if (gh, gw) not in self._grid:
+        def make():
             i = torch.arange(gh * gw, device=self.device)
-            self._grid = {(gh, gw): torch.stack([i % gw, torch.div(i, gw, rounding_mode="floor")])}
-        return self._grid[(gh, gw)]
+            return torch.stack([i % gw, torch.div(i, gw, rounding_mode="floor")])
+        return self._grid.lookup((gh, gw), make)
 
     _SOLVE_ERRORS = (AssertionError,)             # what the planar stage turns into "no usable fit" (too few correspondences)
 
     def track(self, input_img, debug=False, img_identifier=None):
         self._n_tracked += 1
         out = self.multi.track(input_img)                            # (uploads the frame: the ring keeps a copy of its own)
-        return self._planar_stage(out, input_img, img_identifier)
+        return self._planar_stage(self, out, input_img, img_identifier)
 
-    def _planar_stage(self, out, input_img, img_identifier):
-        """The fold result of one frame -> (H_cur2init, meta) for the template mask in `_template_mask_u8`: correspondences, the
-        fit, the state update."""
+    def _planar_stage(self, state, out, input_img, img_identifier):
+        """The fold result of one frame -> (H_cur2init, meta): correspondences, the fit, the update of `state` -- the holder of lost,
+        N_lost, prev_H2init, last_good_H2init, _announced, n_kept, _template_mask_u8: the tracker, or a target of WOFTChainedMulti."""
         Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
         gh, gw = int(out.flow.shape[1]), int(out.flow.shape[2])
-        dst, w, ok, hist = self._tc[(gh, gw)] = ops.chain_tc(out.flow, out.cost, out.vis, out.sel, self._template_mask_u8,
-                                                             self.chain_vis_thr, want_w=self._wants_weights(), mask_hw=(Hh, Ww),
-                                                             out=self._tc.get((gh, gw)))
+        mask = state._template_mask_u8
+        dst, w, ok, hist = self._tc.put((gh, gw), ops.chain_tc(out.flow, out.cost, out.vis, out.sel, mask, self.chain_vis_thr,
+                                                               want_w=self._wants_weights(), mask_hw=(Hh, Ww),
+                                                               out=self._tc.get((gh, gw))))
         src_xy = None if self._fused is not None else self._source_grid(gh, gw)
-        self.n_kept = None
+        self.n_kept = None                                           # (the channel by which _solve reports the kept count)
         try:
-            fit = self._solve(src_xy, dst, w, (gh, gw), (Hh, Ww), self._template_mask_u8, None, bounds=True, judge=True, vis=ok)
+            fit = self._solve(src_xy, dst, w, (gh, gw), (Hh, Ww), mask, None, bounds=True, judge=True, vis=ok)
         except self._SOLVE_ERRORS:                                   # (too few correspondences for the estimator)
             fit = None
-        return self._finish(fit, hist.cpu().numpy().astype(np.int64), input_img, img_identifier)
+        state.n_kept = self.n_kept
+        return self._finish(state, fit, hist.cpu().numpy().astype(np.int64), input_img, img_identifier)
 
-    def _decision_for_meta(self):
-        return self.solver_decision
-
-    def _finish(self, fit, counts, input_img, img_identifier):
-        """A frame's fit (None: there was none), `n_kept` and its histogram (int64 numpy) -> the state update, (H_cur2init, meta)."""
+    def _finish(self, state, fit, counts, input_img, img_identifier):
+        """A frame's fit (None: there was none), the target's `n_kept` and its histogram (int64 numpy) -> the update of `state`,
+        (H_cur2init, meta)."""
         meta = SimpleNamespace()
-        usable = (fit is not None and not (self.n_kept is not None and self.n_kept < 4) and bool(np.all(np.isfinite(fit.H))))
-        meta.n_kept = self.n_kept
+        n_kept = state.n_kept
+        usable = (fit is not None and not (n_kept is not None and n_kept < 4) and bool(np.all(np.isfinite(fit.H))))
+        meta.n_kept = n_kept
         meta.H_global_cur2init = fit.H.copy() if usable else None
         success = bool(usable and fit.success)
         logger.debug(f"global_H_success: {success}")
-        if success:
-            self.lost, self.N_lost = False, 0
-        else:
-            self.lost, self.N_lost = True, self.N_lost + 1
+        state.lost, state.N_lost = not success, (0 if success else state.N_lost + 1)
         # the fit maps current -> template; a rejected fit is still returned, no usable fit keeps the previous pose
-        H_cur2init = fit.H if usable else self.prev_H2init
+        H_cur2init = fit.H if usable else state.prev_H2init
         self.prev_img, self.prev_img_identifier = input_img, img_identifier
-        self._set_pose(H_cur2init.copy(), good=not self.lost)
-        meta.lost, meta.N_lost, meta.global_H_success = self.lost, self.N_lost, success
+        self._set_pose(H_cur2init.copy(), good=not state.lost, state=state)
+        meta.lost, meta.N_lost, meta.global_H_success = state.lost, state.N_lost, success
         meta.chain_hist = counts[:len(self.chain_deltas)].copy()
         meta.chain_invalid, meta.chain_occluded = int(counts[ops.CHAIN_HIST - 2]), int(counts[ops.CHAIN_HIST - 1])
-        if not self._announced:
-            self._announced = True
-            meta.precision = getattr(self.flower, "precision", None)
-            meta.precision_source = getattr(self.flower, "precision_source", None)
-            meta.solver_decision = self._decision_for_meta()
+        self._announce(meta, state)
         return H_cur2init.copy(), meta
 
 
@@ -266,14 +251,13 @@ class WOFTChainedMulti(WOFTChained):
     The planar stage, by back end (`solver_decision` names the one in use; `meta.solver_decision` stays WOFTChained's text):
       device solver, Sobol draw, least-squares / IRLS estimator (the presets): chain_tc_multi, tc_select_multi, hfit_batched,
           inlier_frac_batched and one pinned read of one result block -- H (K, 9) | inlier fraction (K) | status (K) | selected and
-          kept counts (2, K) | histograms (K, 130), 143 K words: the batched fit writes its H and status as planes, so the block
-          is planes, not rows of 16.  The number of launches and the one read do not depend on K.
+          kept counts (2, K) | histograms (K, 130), 143 K words (woft_amd.planar: the one block of every tracker).  The number of
+          launches and the one read do not depend on K.
       device solver with the RANSAC or the similarity (TRS) estimator: the same selection, then that estimator's single-element
           launch on each target's slices, inlier_frac_batched and the one read.
       device solver without a subsampler (counts can exceed the one-workgroup fit's 2048), or the config's own callables: a loop
-          of WOFTChained's single-target stage over per-target uint8 masks (K times its launches and reads)."""
+          of WOFTChained's single-target stage over the targets' states and uint8 masks (K times its launches and reads)."""
     _SOLVE_ERRORS = (Exception,)                  # (a target's failed fit keeps that target's previous pose; nothing escapes)
-    _TARGET_STATE = ("lost", "N_lost", "prev_H2init", "last_good_H2init", "_announced", "_template_mask_u8", "n_kept")
 
     def __init__(self, config):
         super().__init__(config)
@@ -292,7 +276,6 @@ class WOFTChainedMulti(WOFTChained):
         self.solver_decision += f"; multi-target planar stage: {how}"
         self._targets = []
         self._announced_targets = set()           # (as `_announced`: once per tracker, not once per init())
-        self._mb = {}                             # per (K, grid size): the buffers of the batched stage
 
     def _decision_for_meta(self):
         return self._single_decision
@@ -328,95 +311,36 @@ class WOFTChainedMulti(WOFTChained):
                          for t, m in enumerate(masks)]
         self._tbits = torch.from_numpy(pack_target_bits(masks).view(np.int32)).to(self.device)
 
-    # ---- per-target state: the single-target code runs with one target's state swapped in ---------------------------------------
-    def _as_target(self, t, fn):
-        T = self._targets[t]
-        for k in self._TARGET_STATE:
-            setattr(self, k, getattr(T, k))
-        try:
-            return fn()
-        finally:
-            for k in self._TARGET_STATE:
-                setattr(T, k, getattr(self, k))
-            if T._announced:
-                self._announced_targets.add(t)
-
     def track(self, input_img, debug=False, img_identifier=None):
         if not self._targets:
             raise RuntimeError("WOFTChainedMulti.track() before init()")
         self._n_tracked += 1
         out = self.multi.track(input_img)                            # (the one dense track every target shares)
-        K = len(self._targets)
         if self._route == "loop":
-            res = [self._as_target(t, lambda: self._planar_stage(out, input_img, img_identifier)) for t in range(K)]
+            res = [self._planar_stage(T, out, input_img, img_identifier) for T in self._targets]
         else:
-            fits = self._planar_batched(out, input_img)
-
-            def finish(fit, n_kept, counts):
-                self.n_kept = n_kept
-                return self._finish(fit, counts, input_img, img_identifier)
-            res = [self._as_target(t, lambda: finish(*fits[t])) for t in range(K)]
+            res = []
+            for T, (fit, _, kept, counts) in zip(self._targets, self._planar_batched(out, input_img)):
+                T.n_kept = self.n_kept = kept
+                res.append(self._finish(T, fit, counts, input_img, img_identifier))
+        self._announced_targets.update(t for t, T in enumerate(self._targets) if T._announced)
         return np.stack([H for H, _ in res]), [meta for _, meta in res]
 
-    def _multi_buffers(self, K, n_grid):
-        if (K, n_grid) not in self._mb:
-            F, cap = self._fused, 1024                               # (these routes have a Sobol draw: at most 1024 selected)
-            new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
-            blk = torch.zeros(K * (13 + ops.CHAIN_HIST), dtype=torch.float32, device=self.device)
-            iblk = blk.view(torch.int32)
-            host = torch.empty(blk.numel(), dtype=torch.float32).pin_memory()
-            b = dict(ws=ops.tc_select_multi_ws(n_grid, K), pa=new(K, cap, 2), pb=new(K, cap, 2), w=new(K, cap), blk=blk, host=host,
-                     H=blk[:9 * K].view(K, 9), frac=blk[9 * K:10 * K], status=iblk[10 * K:11 * K],
-                     count=iblk[11 * K:13 * K].view(2, K), hist=iblk[13 * K:].view(K, ops.CHAIN_HIST), fit_ws=None,
-                     event=torch.cuda.Event())
-            # chain_tc_multi's outputs, reused; its histograms land in the result block
-            b["tc"] = (new(2, n_grid), new(1, n_grid) if self._wants_weights() else None, new(1, n_grid), b["hist"])
-            if F.get("ransac") is not None:
-                b["fit_ws"] = ops.ransac_ws(cap, F["ransac"]["max_iters"], self.device)
-            if F.get("trs") is not None:
-                b["fit_ws"] = ops.trs_ws(cap, F["trs"]["max_iters"], self.device)
-            self._mb = {(K, n_grid): b}
-        return self._mb[(K, n_grid)]
-
     def _planar_batched(self, out, input_img):
-        """The planar stage of every target on one fold result -> [(fit | None, n_kept, histogram int64 numpy)] per target."""
+        """The planar stage of every target on one fold result -> [(fit | None, selected, kept, histogram int64 numpy)] per
+        target.  chain_tc_multi's histograms land in the result block: one read."""
         F, K = self._fused, len(self._targets)
         Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
         gh, gw = int(out.flow.shape[1]), int(out.flow.shape[2])
-        b = self._multi_buffers(K, gh * gw)
-        dst, w, ok, _ = ops.chain_tc_multi(out.flow, out.cost, out.vis, out.sel, self._tbits, K, self.chain_vis_thr,
-                                           want_w=self._wants_weights(), mask_hw=(Hh, Ww), out=b["tc"])
+        n_grid, cap, want_w = gh * gw, 1024, self._wants_weights()     # (these routes have a Sobol draw: at most 1024 selected)
+        blk = (b := self._buffers.lookup((K, n_grid, cap), lambda: PlanarBuffers(F, K, n_grid, cap, self.device, True, True))).block
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
+        tc = self._tc.lookup((K, n_grid), lambda: (new(2, n_grid), new(1, n_grid) if want_w else None, new(1, n_grid), blk.hist))
+        dst, w, ok, _ = ops.chain_tc_multi(out.flow, out.cost, out.vis, out.sel, self._tbits, K, self.chain_vis_thr, want_w=want_w,
+                                           mask_hw=(Hh, Ww), out=tc)
         weighted = F.get("weighted", True)
         ops.tc_select_multi(dst, w if weighted else None, self._tbits, K, Hh, Ww, True, F["sobol_u"], ok, self._vis_mode,
-                            self._vis_thr, b["ws"], b["pa"], b["pb"], b["w"], b["count"], grid=(gh, gw))
-        sel = b["count"][0]
-        R, T = F.get("ransac"), F.get("trs")
-        if R is not None or T is not None:
-            fn, P = (ops.ransac, R) if R is not None else (ops.trs, T)
-            for t in range(K):
-                fn(b["pa"][t], b["pb"][t], b["H"][t], b["status"][t:t + 1], count=sel[t:t + 1], max_iters=P["max_iters"],
-                   thr=P["thr"], conf=P["conf"], ws=b["fit_ws"])
-        else:
-            ops.hfit_batched(b["pa"], b["pb"], b["w"] if weighted else None, b["H"], b["status"], counts=sel,
-                             reweight=F["reweight"], huber_k=F["huber_k"], n_irls=F["n_irls"])
-        ops.inlier_frac_batched(b["pa"], b["pb"], b["H"], b["frac"], thr=F["thr"], counts=sel)
-        # the frame's single device->host read: the whole result block into a pinned buffer, then wait for it
-        host = b["host"]
-        host.copy_(b["blk"], non_blocking=True)
-        b["event"].record()
-        t0 = time.perf_counter()
-        b["event"].synchronize()
-        self.host_wait_s += time.perf_counter() - t0
-        ih = host.view(torch.int32).numpy()
-        fh = host.numpy()
-        hist = ih[13 * K:].reshape(K, ops.CHAIN_HIST)
-        fits = []
-        for t in range(K):
-            fit = None
-            if int(ih[10 * K + t]) != 1:                             # (1: too few points for the estimator -- no fit)
-                verdict = F.get("const_verdict")
-                if verdict is None:
-                    verdict = bool(np.float32(fh[9 * K + t]) > np.float32(F["min_frac"]))
-                fit = _Fit(H=fh[9 * t:9 * t + 9].astype(np.float64).reshape(3, 3), success=bool(verdict))
-            fits.append((fit, int(ih[12 * K + t]), hist[t].astype(np.int64)))
-        return fits
+                            self._vis_thr, b.ws, b.pa, b.pb, b.w, blk.count, grid=(gh, gw))
+        fit_and_judge(F, b, weighted)
+        self.host_wait_s += blk.read()
+        return decode(blk.host.numpy(), K, F, True)

@@ -32,6 +32,18 @@ class Config:
         return repr(self.__dict__)
 
 
+def config_get(C, key, default=None):
+    """The value of a config key, `default` when the key is absent or None.  An absent key reads as an empty instance of the
+    config's own class (above; any attribute bag with that behaviour, the reference's Config included)."""
+    v = getattr(C, key, None)
+    return default if (v is None or isinstance(v, type(C))) else v
+
+
+def config_set(C, key):
+    """Whether a config key is present and truthy."""
+    return bool(config_get(C, key, False))
+
+
 def load_config(path):
     spec = importlib.util.spec_from_file_location("tracker_config", str(path))
     module = importlib.util.module_from_spec(spec)

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, mh_train, ops, wh_train
+from .config import config_get
 from .engine import RaftEngine
 
 logger = logging.getLogger(__name__)
@@ -188,12 +189,11 @@ class RAFTWrapper:
         # flow config key `volume_storage` ("fp32" | "bf16"): element type of the correlation volume (corr = "volume")
         # flow config key `corr_band` ("auto" | True | False; env WOFT_CORR_BAND=0: off): the correlations around the identity
         # computed once per flow, the lookups sampling from them (engine.py: CORR_BAND) -- "auto": flows long enough for it to pay
-        v = getattr(self.C, "corr_band", None)
-        self.corr_band = "auto" if (v is None or isinstance(v, type(self.C))) else (v if v == "auto" else bool(v))
+        v = config_get(self.C, "corr_band", "auto")
+        self.corr_band = v if v == "auto" else bool(v)
         # flow config key `fuse_c1` (default True; env WOFT_FUSE_C1=0: off): on a band flow convc1 samples the band inside its
         # own launch (engine.py: FUSE_C1)
-        v = getattr(self.C, "fuse_c1", None)
-        self.fuse_c1 = True if (v is None or isinstance(v, type(self.C))) else bool(v)
+        self.fuse_c1 = bool(config_get(self.C, "fuse_c1", True))
         self.engine = RaftEngine(state_dict, small=small, weighted=weighted, precision=self.precision, corr=self.corr,
                                  volume_storage=getattr(self.C, "volume_storage", None), mask_head=self.masked,
                                  corr_band=self.corr_band, fuse_c1=self.fuse_c1)
@@ -205,8 +205,7 @@ class RAFTWrapper:
         self._mh_loaded = {k: v for k, v in state_dict.items() if k.startswith("mask_head.net.")}
         self._mh_params = None
         # restricted refinement iterations for callers that declare where they read the flow (pin_flow_region + flow_region=True)
-        v = getattr(self.C, "flow_region", None)
-        self.flow_region_on = (os.environ.get("WOFT_FLOW_REGION", "1") != "0") if (v is None or isinstance(v, type(self.C))) else bool(v)
+        self.flow_region_on = bool(config_get(self.C, "flow_region", os.environ.get("WOFT_FLOW_REGION", "1") != "0"))
         # opt-in (flow config key `graph`, env WOFT_GRAPH=1): the ~330 launches of a flow -- a static list per
         # resolution, fixed buffers, no allocation -- are captured once into a hipGraph and replayed per frame
         self.use_graph = (os.environ.get("WOFT_GRAPH") or str(int(bool(getattr(self.C, "graph", False))))) == "1"

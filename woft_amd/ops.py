@@ -1228,18 +1228,22 @@ def tc_flags_vis(dst, tmask_u8, pwmask_u8, h, wimg, check_dst, vis, vis_mode, vi
     return flags.view(torch.bool)
 
 
-_HFIT_WS = {}
+def _stream_scratch(cache, need, device):
+    """`need` bytes of estimator scratch out of `cache`: one buffer per device AND stream (its use is ordered by the stream it was
+    first used on -- two trackers on two streams of one process must not share it), reused, grown on demand."""
+    dev = torch.device(device or DEV)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr())
+    if key not in cache or cache[key].numel() < need:
+        cache[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return cache[key]
+
+
+_HFIT_WS, _RANSAC_WS, _TRS_WS = {}, {}, {}
 
 
 def hfit_ws(device=None):
     """Scratch of the streaming fit (woft_hfit_ws_bytes), one per device and stream, reused (stream-ordered)."""
-    dev = torch.device(device or DEV)
-    # (one per device AND stream: its use is ordered by the stream it was first used on -- two trackers on two streams of one
-    #  process must not share it)
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr())
-    if key not in _HFIT_WS:
-        _HFIT_WS[key] = torch.empty(int(_lib.load().woft_hfit_ws_bytes()), dtype=torch.uint8, device=dev)
-    return _HFIT_WS[key]
+    return _stream_scratch(_HFIT_WS, int(_lib.load().woft_hfit_ws_bytes()), device)
 
 
 HFIT_SINGLE_MAX = 2048
@@ -1292,19 +1296,12 @@ def hfit_step(pa, pb, w, rew, first, res, Hout, status, ws=None):
                                      ptr(res), ptr(Hout), ptr(status), stream_ptr()), "woft_hfit_step")
 
 
-_RANSAC_WS = {}
-
-
 def ransac_ws(n_max, max_iters, device=None):
     """Scratch of woft_ransac (woft_ransac_ws_bytes(n_max, max_iters)), one per device and stream like hfit_ws, grown on demand."""
-    dev = torch.device(device or DEV)
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr())
     need = int(_lib.load().woft_ransac_ws_bytes(int(n_max), int(max_iters)))
     if need < 0:
         raise _lib.WoftHipError(f"woft_ransac_ws_bytes({n_max}, {max_iters}) rejected its arguments")
-    if key not in _RANSAC_WS or _RANSAC_WS[key].numel() < need:
-        _RANSAC_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return _RANSAC_WS[key]
+    return _stream_scratch(_RANSAC_WS, need, device)
 
 
 def ransac(pa, pb, Hout, status, count=None, max_iters=10000, thr=1.4142, conf=0.995, seed=0, refine=True, info=None,
@@ -1318,19 +1315,12 @@ def ransac(pa, pb, Hout, status, count=None, max_iters=10000, thr=1.4142, conf=0
                                   ptr(inlier_mask), stream_ptr()), "woft_ransac")
 
 
-_TRS_WS = {}
-
-
 def trs_ws(n_max, max_iters, device=None):
     """Scratch of woft_trs (woft_trs_ws_bytes(n_max, max_iters)), one per device and stream like ransac_ws, grown on demand."""
-    dev = torch.device(device or DEV)
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr())
     need = int(_lib.load().woft_trs_ws_bytes(int(n_max), int(max_iters)))
     if need < 0:
         raise _lib.WoftHipError(f"woft_trs_ws_bytes({n_max}, {max_iters}) rejected its arguments")
-    if key not in _TRS_WS or _TRS_WS[key].numel() < need:
-        _TRS_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return _TRS_WS[key]
+    return _stream_scratch(_TRS_WS, need, device)
 
 
 def trs(pa, pb, Hout, status, count=None, max_iters=10000, thr=3.0, conf=0.999, seed=0, refine=True, info=None,

@@ -36,7 +36,6 @@ template's feature / context tensors are computed once (the flow provider pins t
 """
 import logging
 import os
-import time
 from inspect import signature
 from types import SimpleNamespace
 
@@ -44,7 +43,9 @@ import numpy as np
 import torch
 
 from . import ops
+from .config import config_get, config_set
 from .homography import compose_H
+from .planar import BoundedCache, PlanarBuffers, _Fit, decode, fit_and_judge
 
 logger = logging.getLogger(__name__)
 _EYE = np.eye(3)
@@ -132,8 +133,16 @@ class _FrameUploader:
         return self.dev[i]
 
 
-class _Fit(SimpleNamespace):
-    """Result of one solve: H (3x3 float64, cur -> src) and, for the global stage, the re-detection verdict."""
+def _float_key(C, key, default, ok, what):
+    """A config key as a float that satisfies ok() (NaN fails every compare), or ValueError naming `what` was expected."""
+    v = config_get(C, key, default)
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{key} {v!r}: not {what}") from None
+    if not ok(v):
+        raise ValueError(f"{key} {v!r}: not {what}")
+    return v
 
 
 class YAOFTrackerSingleControl:
@@ -148,22 +157,15 @@ class YAOFTrackerSingleControl:
         """-> (mode | None, threshold as the fp32 value the kernels compare with).  Config keys `visibility_mode` (absent / falsy:
         off) and `visibility_thr` (a float in (0, 1), default 0.5; read by 'gate' only)."""
         C = self.C
-        mode = C.visibility_mode
-        if isinstance(mode, type(C)) or not mode:           # (key absent: an empty, falsy Config)
+        mode = config_get(C, "visibility_mode")
+        if not mode:
             return None, 0.5
         if mode not in self.VISIBILITY_MODES:
             raise ValueError(f"visibility_mode {mode!r}: not one of {self.VISIBILITY_MODES} (or absent / None: the mask is not used)")
         if C.flow_config.raft_type != "weighted_masked":
             raise ValueError(f"visibility_mode {mode!r} needs a flow config with raft_type 'weighted_masked' (the MaskHead computes the "
                              f"visibility); this one has {C.flow_config.raft_type!r}")
-        thr = C.visibility_thr
-        thr = 0.5 if (isinstance(thr, type(C)) or thr is None) else thr
-        try:
-            thr = float(thr)
-        except (TypeError, ValueError):
-            raise ValueError(f"visibility_thr {thr!r}: not a float in (0, 1)") from None
-        if not 0.0 < thr < 1.0:                              # (NaN fails both compares)
-            raise ValueError(f"visibility_thr {thr!r}: not a float in (0, 1)")
+        thr = _float_key(C, "visibility_thr", 0.5, lambda v: 0.0 < v < 1.0, "a float in (0, 1)")
         return mode, float(np.float32(thr))                  # rounded to fp32 once, here
 
     FB_MODES = ("gate",)
@@ -173,42 +175,41 @@ class YAOFTrackerSingleControl:
         `fb_beta` (finite floats >= 0, defaults 0.01 and 0.5): a correspondence survives iff its flow lands inside the frame and
         |f + b|^2 <= fb_alpha * (|f|^2 + |b|^2) + fb_beta, b the reverse flow sampled where f lands."""
         C = self.C
-        mode = C.fb_check
-        if isinstance(mode, type(C)) or not mode:           # (key absent: an empty, falsy Config)
+        mode = config_get(C, "fb_check")
+        if not mode:
             return None, 0.01, 0.5
         if mode not in self.FB_MODES:
             raise ValueError(f"fb_check {mode!r}: not one of {self.FB_MODES} (or absent / None: no forward-backward check)")
-        vm = C.visibility_mode
-        if not isinstance(vm, type(C)) and vm:
+        vm = config_get(C, "visibility_mode")
+        if vm:
             raise ValueError(f"fb_check {mode!r} and visibility_mode {vm!r} are both set: the solver has one visibility slot, "
                              "choose one of the two")
-        vals = []
-        for key, default in (("fb_alpha", 0.01), ("fb_beta", 0.5)):
-            v = getattr(C, key)
-            v = default if (isinstance(v, type(C)) or v is None) else v
-            try:
-                v = float(v)
-            except (TypeError, ValueError):
-                raise ValueError(f"{key} {v!r}: not a finite float >= 0") from None
-            if not 0.0 <= v < float("inf"):                  # (NaN fails both compares)
-                raise ValueError(f"{key} {v!r}: not a finite float >= 0")
-            vals.append(v)
-        return mode, vals[0], vals[1]
+        ok = lambda v: 0.0 <= v < float("inf")
+        return (mode, _float_key(C, "fb_alpha", 0.01, ok, "a finite float >= 0"),
+                _float_key(C, "fb_beta", 0.5, ok, "a finite float >= 0"))
 
     def _warm_start_config(self):
         """-> (on, iterations of a warm-started flow | None = the flow config's).  Config keys `warm_start_local` (absent / falsy:
         off) and `warm_start_iters` (an integer >= 1; absent / None: the flow config's `iters`)."""
         C = self.C
-        on = C.warm_start_local
-        on = False if isinstance(on, type(C)) else bool(on)
-        n = C.warm_start_iters
-        if isinstance(n, type(C)) or n is None:
-            return on, None
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        on = config_set(C, "warm_start_local")
+        n = config_get(C, "warm_start_iters")
+        if n is not None and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1):
             raise ValueError(f"warm_start_iters {n!r}: not an integer >= 1")
-        return on, int(n)
+        return on, (None if n is None else int(n))
+
+    # config keys this tracker class does not provide: (key, why), refused by __init__ when set
+    REFUSED = ()
+    REFUSED_BY = "tracker"
+    BUFFER_SETS = 1                  # planar-stage buffer sets kept (a new grid size replaces the old one)
+
+    def _refusals(self, config):
+        for key, why in self.REFUSED:
+            if config_set(config, key):
+                raise NotImplementedError(f"{key} is not provided by the {self.REFUSED_BY}: {why}")
 
     def __init__(self, config):
+        self._refusals(config)
         self.C = config
         self.warm_start_local, self.warm_start_iters = self._warm_start_config()
         self.local_warm_started = False   # whether the last frame t-1 -> t flow started from a carried flow
@@ -240,6 +241,8 @@ class YAOFTrackerSingleControl:
         self._n_tracked = 0
         self._upload = _FrameUploader()
         self.host_wait_s = 0.0       # seconds this tracker's thread spent blocked on the per-flow result read (device back end)
+        self._buffers = BoundedCache(self.BUFFER_SETS)    # (K, grid size, cap) -> PlanarBuffers
+        self._prewarp = BoundedCache()                    # frame / window shape -> (pre-warped frame, its validity map)
 
     # ---- which solver back end ------------------------------------------------------------------
     def _fused_specs(self):
@@ -260,8 +263,7 @@ class YAOFTrackerSingleControl:
     def _fused_specs_plain(self):
         C = self.C
         self.solver_decision = "callable back end"
-        v = C.device_solver
-        if os.environ.get("WOFT_FUSED", "1") == "0" or (not isinstance(v, type(C)) and v is not None and not v):
+        if os.environ.get("WOFT_FUSED", "1") == "0" or not config_get(C, "device_solver", True):
             self.solver_decision += " (device back end switched off)"
             return None
         if C.post_hoc_weights_postprocessing_fn or C.flow_numpy_out:
@@ -291,23 +293,6 @@ class YAOFTrackerSingleControl:
     def _device_solver_reads(self, raft_type):
         """Whether the device back end can take its weights (and its visibility) from a provider of this raft_type."""
         return raft_type == ("weighted" if self.visibility_mode is None else "weighted_masked")
-
-    def _fused_buffers(self, n_grid):
-        # (WOFTWindow._fused_buffers swaps `_fb_key` / `_fb` from its own per-size cache: keep these two names)
-        if getattr(self, "_fb_key", None) != n_grid:
-            cap = 1024 if self._fused["n_draw"] else n_grid
-            self._fb = dict(ws=ops.tc_select_ws(n_grid), pa=torch.empty(cap, 2, device=self.device),
-                            pb=torch.empty(cap, 2, device=self.device), w=torch.empty(cap, device=self.device),
-                            res=torch.zeros(16, dtype=torch.float32, device=self.device),
-                            fit_ws=ops.hfit_ws(self.device) if cap > ops.HFIT_SINGLE_MAX else None)
-            R = self._fused.get("ransac")
-            if R is not None:
-                self._fb["fit_ws"] = ops.ransac_ws(cap, R["max_iters"], self.device)
-            T = self._fused.get("trs")
-            if T is not None:
-                self._fb["fit_ws"] = ops.trs_ws(cap, T["max_iters"], self.device)
-            self._fb_key = n_grid
-        return self._fb
 
     # ---- public surface (TRK:19-57) -----------------------------------------------------------------
     def init(self, img, mask, img_identifier=None):
@@ -348,8 +333,7 @@ class YAOFTrackerSingleControl:
             # of the DRAWN correspondences are read, and the draw does not depend on the weights: the head is evaluated after
             # the selection, on the windows under the drawn pixels' upsampling support (config key sparse_weight_head =
             # False / env WOFT_SPARSE_WH=0: on the whole mask region, as above).  Identical homographies (tested).
-            v = self.C.sparse_weight_head
-            on = (os.environ.get("WOFT_SPARSE_WH", "1") != "0") if (isinstance(v, type(self.C)) or v is None) else bool(v)
+            on = bool(config_get(self.C, "sparse_weight_head", os.environ.get("WOFT_SPARSE_WH", "1") != "0"))
             # (a visibility mode: the mask head runs on every pixel after the weight head and the provider defers nothing for a
             #  'weighted_masked' network -- the non-deferred path)
             self._sparse_weights = bool(on and self._fused is not None and self._fused["n_draw"] and self._mask_weight_head()
@@ -407,13 +391,12 @@ class YAOFTrackerSingleControl:
         H_global = compose_H(prewarp_H, fit.H)
         meta.H_global_cur2init = H_global.copy()
         logger.debug(f"global_H_success: {fit.success}")
+        H_cur2init = H_global
         if fit.success:
             self.lost, self.N_lost = False, 0
             self._warm = None                                        # (a re-detected frame ends the run: nothing to carry)
-            H_cur2init = H_global
         else:
             self.lost, self.N_lost = True, self.N_lost + 1
-            H_cur2init = H_global
             if not self.C.no_local_H:
                 H_cur2init = meta.H_local_cur2init = self._local_stage(frame)
                 meta.local_warm_started = self.local_warm_started    # (False without `warm_start_local`)
@@ -425,15 +408,7 @@ class YAOFTrackerSingleControl:
         self.prev_img, self.prev_img_identifier = frame, img_identifier
         self._set_pose(H_cur2init.copy(), good=not self.lost)
         meta.lost, meta.N_lost, meta.global_H_success = self.lost, self.N_lost, fit.success
-        if not self._announced:           # first tracked frame: which arithmetic and which solver produced these results
-            self._announced = True
-            meta.precision = getattr(self.flower, "precision", None)
-            meta.precision_source = getattr(self.flower, "precision_source", None)
-            meta.solver_decision = self.solver_decision
-            if self.visibility_mode is not None:      # (like n_kept: the field exists only with a mode)
-                meta.visibility_mode = self.visibility_mode
-            if self.fb_check:
-                meta.fb_check = self.fb_check
+        self._announce(meta, self)
         k = self.C.downscale_inputs
         if k:                                                        # TRK:280-283
             H_cur2init = compose_H(np.diag([1.0 / k, 1.0 / k, 1.0]), H_cur2init, np.diag([float(k), float(k), 1.0]))
@@ -442,18 +417,32 @@ class YAOFTrackerSingleControl:
     def _mask_weight_head(self):
         if self.C.post_hoc_weights_postprocessing_fn:     # (a spatial filter of the weight MAP would read outside the mask)
             return False
-        v = self.C.mask_weight_head
-        if isinstance(v, type(self.C)) or v is None:      # key absent (Config returns an empty, falsy Config): default on
-            return os.environ.get("WOFT_MASK_WEIGHT_HEAD", "1") != "0"
-        return bool(v)
+        return bool(config_get(self.C, "mask_weight_head", os.environ.get("WOFT_MASK_WEIGHT_HEAD", "1") != "0"))   # (absent: on)
 
     def _flow_region_on(self):
         return bool(self._mask_weight_head() and self.visibility_mode is None and not self.warm_start_local and not self.fb_check)
 
-    def _set_pose(self, H, good):
-        self.prev_H2init = H
+    def _decision_for_meta(self):
+        return self.solver_decision
+
+    def _announce(self, meta, state):
+        """On the first tracked frame of `state` (the tracker, or one target): which arithmetic and solver produced the results."""
+        if state._announced:
+            return
+        state._announced = True
+        meta.precision = getattr(self.flower, "precision", None)
+        meta.precision_source = getattr(self.flower, "precision_source", None)
+        meta.solver_decision = self._decision_for_meta()
+        if self.visibility_mode is not None:          # (like n_kept: the field exists only with a mode)
+            meta.visibility_mode = self.visibility_mode
+        if self.fb_check:
+            meta.fb_check = self.fb_check
+
+    def _set_pose(self, H, good, state=None):
+        state = state or self
+        state.prev_H2init = H
         if good:
-            self.last_good_H2init = H.copy()
+            state.last_good_H2init = H.copy()
 
     # ---- the two flow stages ------------------------------------------------------------------------
     def _flow(self, src, dst, src_is_previous_dst=False, flow_init=None, iters=None, flow_region=False):
@@ -514,11 +503,8 @@ class YAOFTrackerSingleControl:
         else:
             # (two per-size buffers, reused: consumed by the flow / the selection before the next frame's warp is enqueued on
             #  the same stream; allocating them per frame was ~15 us of host time in front of the frame's first kernel)
-            key = tuple(frame.shape)
-            if getattr(self, "_pw_key", None) != key:
-                self._pw_buf = (torch.empty_like(frame), torch.empty(frame.shape[:2], dtype=torch.uint8, device=self.device))
-                self._pw_key = key
-            prewarped, valid = self._pw_buf
+            prewarped, valid = self._prewarp.lookup(tuple(frame.shape), lambda: (
+                torch.empty_like(frame), torch.empty(frame.shape[:2], dtype=torch.uint8, device=self.device)))
             ops.warp_perspective_u8(frame, prewarp_H, prewarped, valid)
         if self.C.do_not_mask_TCs_by_prewarped:
             valid = None
@@ -555,11 +541,16 @@ class YAOFTrackerSingleControl:
             prev_mask = torch.empty_like(self._template_mask_u8)
             ops.warp_perspective_u8(self._template_mask_u8, np.linalg.inv(self.prev_H2init), prev_mask, None,
                                     nearest=True)
+        return self._local_fit(src_xy, dst_xy, w, grid, frame.shape[:2], prev_mask, p)
+
+    def _local_fit(self, src_xy, dst_xy, w, grid, hw, prev_mask, vis, undo=None):
+        """The tail of the local stage: the fit (no re-detection test), chained onto the previous pose; `undo` takes a window's
+        H back to frame coordinates.  A failed fit (the estimator only: anything else is an error) keeps the previous pose."""
         try:
-            fit = self._solve(src_xy, dst_xy, w, grid, frame.shape[:2], prev_mask, None, bounds=False, judge=False, vis=p)
+            fit = self._solve(src_xy, dst_xy, w, grid, hw, prev_mask, None, bounds=False, judge=False, vis=vis)
             if not np.all(np.isfinite(fit.H)):
                 raise FloatingPointError("singular homography system")
-            return compose_H(fit.H, self.prev_H2init)
+            return compose_H(fit.H if undo is None else undo(fit.H), self.prev_H2init)
         except Exception as ex:
             logger.warning(f"frame-to-frame homography failed ({type(ex).__name__}): pose of the previous frame kept")
             return self.prev_H2init
@@ -586,58 +577,31 @@ class YAOFTrackerSingleControl:
             return _Fit(H=_EYE.copy(), success=False)
 
     def _solve_device(self, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, vis=None):
-        F, b = self._fused, self._fused_buffers(grid[0] * grid[1])
-        res = b["res"]
-        ires = res.view(torch.int32)
+        F, n_grid = self._fused, grid[0] * grid[1]
+        cap = 1024 if F["n_draw"] else n_grid                        # (a Sobol draw selects at most 1024)
+        blk = (b := self._buffers.lookup((1, n_grid, cap), lambda: PlanarBuffers(F, 1, n_grid, cap, self.device, False))).block
         weighted = F.get("weighted", True)
         if vis is not None:
             # (an unweighted estimator under 'weight': the output weight is p itself and the fit is called weighted)
             ops.tc_select_vis(dst_xy, w if weighted else None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds,
-                              F["sobol_u"], vis, self._vis_mode, self._vis_thr, b["ws"], b["pa"], b["pb"], b["w"],
-                              ires[12:14], grid=grid)
+                              F["sobol_u"], vis, self._vis_mode, self._vis_thr, b.ws, b.pa, b.pb, b.w, blk.count, grid=grid)
             weighted = weighted or self._vis_mode == "weight"
-        elif w is None and getattr(self.flower, "weights_deferred", False):
-            # The correspondences the fit will read are decided by the flow alone (masks, bounds, Sobol draw): select them
-            # first, then let the provider evaluate the weight head on the windows under THEIR upsampling support only and
-            # hand back the weights of exactly these pixels (exact: the head has no cross-pixel terms) -- identical fit.
-            # An UNWEIGHTED estimator (the reference's "plainLSq" configs call the library with weights=None) reads no weight at
-            # all: the deferred head is then simply never evaluated.
-            ops.tc_select(dst_xy, None, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds, F["sobol_u"], b["ws"],
-                          b["pa"], b["pb"], b["w"], ires[12:14], grid=grid)
-            if weighted:
-                self.flower.finish_weights(b["pb"], ires[12:13], b["pb"].shape[0], out=b["w"])      # (pb: the source pixels)
         else:
-            ops.tc_select(dst_xy, w, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds, F["sobol_u"], b["ws"],
-                          b["pa"], b["pb"], b["w"], ires[12:14], grid=grid)
-        R, T = F.get("ransac"), F.get("trs")
-        if R is not None:                  # (status 1 / 2 in the same slot: fewer than 4 points / no model, H all NaN)
-            ops.ransac(b["pa"], b["pb"], res[0:9], ires[10:11], count=ires[12:13], max_iters=R["max_iters"], thr=R["thr"],
-                       conf=R["conf"], ws=b["fit_ws"])
-        elif T is not None:                # (the similarity estimator: status 1 is fewer than 2 points)
-            ops.trs(b["pa"], b["pb"], res[0:9], ires[10:11], count=ires[12:13], max_iters=T["max_iters"], thr=T["thr"],
-                    conf=T["conf"], ws=b["fit_ws"])
-        else:
-            ops.hfit(b["pa"], b["pb"], b["w"] if weighted else None, res[0:9], ires[10:11], count=ires[12:13],
-                     reweight=F["reweight"], huber_k=F["huber_k"], n_irls=F["n_irls"], ws=b["fit_ws"])
-        ops.inlier_frac(b["pa"], b["pb"], res[0:9], res[9:10], thr=F["thr"], count=ires[12:13])
-        # the flow's single device->host read: into a pinned buffer (no staging copy, no allocation), then wait for it
-        if getattr(self, "_host_res", None) is None:
-            self._host_res = torch.empty(16, dtype=torch.float32).pin_memory()
-            self._host_ev = torch.cuda.Event()
-        host = self._host_res
-        host.copy_(res, non_blocking=True)
-        self._host_ev.record()
-        t0 = time.perf_counter()
-        self._host_ev.synchronize()
-        self.host_wait_s += time.perf_counter() - t0      # (bench: wall time minus this = the launch loop's host time per frame)
-        ih = host.view(torch.int32)
-        self.n_kept = int(ih[13])                                    # (count[1] of the selection: part of the same read)
-        if int(ih[10]) == 1:
-            raise AssertionError(torch.Size([1, int(ih[12]), 2]))    # least_squares_H.py:162 (fewer than 4 points; TRS: than 2)
-        verdict = F.get("const_verdict")       # (a re-detection test that is `return True` / `return False`: the reference's ablations)
-        if verdict is None:
-            verdict = bool(np.float32(host[9]) > np.float32(F["min_frac"]))
-        return _Fit(H=host[0:9].numpy().astype(np.float64).reshape(3, 3), success=bool(verdict))   # (astype: a copy; the verdict in float32, as torch compares a float32 mean with a Python float)
+            ops.tc_select(dst_xy, w, src_mask_u8, dst_valid_u8, frame_hw[0], frame_hw[1], bounds, F["sobol_u"], b.ws,
+                          b.pa, b.pb, b.w, blk.count, grid=grid)
+            # Deferred weights (w is None): the correspondences the fit will read are decided by the flow alone (masks, bounds,
+            # Sobol draw), so they were selected first; now the provider evaluates the weight head on the windows under THEIR
+            # upsampling support only and hands back the weights of exactly these pixels (exact: the head has no cross-pixel
+            # terms) -- identical fit.  An UNWEIGHTED estimator (the reference's "plainLSq" configs call the library with
+            # weights=None) reads no weight at all: the deferred head is then simply never evaluated.
+            if w is None and weighted and getattr(self.flower, "weights_deferred", False):
+                self.flower.finish_weights(b.pb, blk.selected, b.cap, out=b.w)                     # (pb: the source pixels)
+        fit_and_judge(F, b, weighted)
+        self.host_wait_s += blk.read()                    # (bench: wall time minus this = the launch loop's host time per frame)
+        (fit, selected, self.n_kept, _), = decode(blk.host.numpy(), 1, F, False)
+        if fit is None:
+            raise AssertionError(torch.Size([1, selected, 2]))       # least_squares_H.py:162 (fewer than 4 points; TRS: than 2)
+        return fit
 
     def _solve_callables(self, src_xy, dst_xy, w, grid, frame_hw, src_mask_u8, dst_valid_u8, bounds, judge, vis=None):
         C = self.C
@@ -690,20 +654,18 @@ class WOFTWindow(YAOFTrackerSingleControl):
     PLAN_BOUND = 4                    # local-window shapes the flow provider keeps besides the pinned global window
     MIN_FLOW_SIDE = 16                # a local window cut smaller than this by the frame edge: no flow, previous pose kept
 
+    BUFFER_SETS = PLAN_BOUND + 1      # (the parent keeps ONE grid size; here the global and the local windows alternate)
+    REFUSED_BY = "search-window tracker"
+    REFUSED = (
+        # (not built: the window stages have their own _flow call sites and per-window plans)
+        ("fb_check", "only YAOFTrackerSingleControl runs the reverse flow"),
+        # (the local windows move with the object: the flow of one window is not on the grid of the next)
+        ("warm_start_local", "its frame t-1 -> t flows run on a window that follows the object, so consecutive flows do not share "
+                             "a grid"),
+    )
+
     def __init__(self, config):
-        v = config.fb_check
-        if not isinstance(v, type(config)) and v:
-            # (not built: the window stages have their own _flow call sites and per-window plans)
-            raise NotImplementedError("fb_check is not provided by the search-window tracker: only YAOFTrackerSingleControl runs "
-                                      "the reverse flow")
-        v = config.warm_start_local
-        if not isinstance(v, type(config)) and v:
-            # (the local windows move with the object: the flow of one window is not on the grid of the next)
-            raise NotImplementedError("warm_start_local is not provided by the search-window tracker: its frame t-1 -> t flows run "
-                                      "on a window that follows the object, so consecutive flows do not share a grid")
         super().__init__(config)
-        from collections import OrderedDict
-        self._fb_cache = OrderedDict()
         self.search_bbox = self.local_search_bbox = None
         if hasattr(self.flower, "bound_plans"):
             self.flower.bound_plans(self.PLAN_BOUND)
@@ -721,7 +683,6 @@ class WOFTWindow(YAOFTrackerSingleControl):
         y0, x0, rows, cols = rect
         self._template_crop = ops.crop_u8(_device_u8(self.template_img), rect)
         self._template_mask_crop = ops.crop_u8(self._template_mask_u8, rect)
-        self._gw_buf = None
         if hasattr(self.flower, "pin_source"):                       # the parent pinned the whole template: re-pin the crop
             self.flower.pin_source(self._template_crop)
             if hasattr(self.flower, "pin_weight_region"):
@@ -731,19 +692,6 @@ class WOFTWindow(YAOFTrackerSingleControl):
         self.local_search_bbox = None
         return super().track(input_img, debug=debug, img_identifier=img_identifier)
 
-    def _fused_buffers(self, n_grid):
-        # (the parent keeps the buffers of ONE grid size; here the global and the local window alternate on lost frames)
-        c = self._fb_cache
-        if n_grid in c:
-            c.move_to_end(n_grid)
-            self._fb_key, self._fb = n_grid, c[n_grid]
-            return self._fb
-        self._fb_key = None
-        c[n_grid] = super()._fused_buffers(n_grid)
-        while len(c) > self.PLAN_BOUND + 1:
-            c.popitem(last=False)
-        return c[n_grid]
-
     def _global_stage(self, frame, prewarp_H):
         """Template crop -> the search window of the frame pre-warped by the last good homography (WIN:101-193): the window's
         pixels of the pre-warp and of its validity map are all that is computed.  The keep rule runs in window coordinates with
@@ -751,10 +699,9 @@ class WOFTWindow(YAOFTrackerSingleControl):
         from . import window
         rect = self._rect
         rows, cols = rect[2], rect[3]
-        if self._gw_buf is None or self._gw_buf[0].shape[:2] != (rows, cols):
-            self._gw_buf = (torch.empty((rows, cols, frame.shape[2]), dtype=torch.uint8, device=self.device),
-                            torch.empty((rows, cols), dtype=torch.uint8, device=self.device))
-        prewarped, valid = self._gw_buf
+        prewarped, valid = self._prewarp.lookup((rows, cols), lambda: (
+            torch.empty((rows, cols, frame.shape[2]), dtype=torch.uint8, device=self.device),
+            torch.empty((rows, cols), dtype=torch.uint8, device=self.device)))
         if np.array_equal(prewarp_H, _EYE):
             ops.crop_u8(frame, rect, prewarped)                      # identity warp: the frame's own pixels, all of them filled
             valid = None
@@ -796,11 +743,4 @@ class WOFTWindow(YAOFTrackerSingleControl):
         cur_win = ops.crop_u8(frame, rect)
         mask_win = ops.crop_u8(prev_mask, rect)
         src_xy, dst_xy, w, p, grid = self._flow(prev_win, cur_win)
-        try:                                                         # (the estimator only, as in the parent: anything else is an error)
-            fit = self._solve(src_xy, dst_xy, w, grid, (rect[2], rect[3]), mask_win, None, bounds=False, judge=False, vis=p)
-            if not np.all(np.isfinite(fit.H)):
-                raise FloatingPointError("singular homography system")
-            return compose_H(window.H_undo_crop(box, fit.H), self.prev_H2init)
-        except Exception as ex:
-            logger.warning(f"frame-to-frame homography failed ({type(ex).__name__}): pose of the previous frame kept")
-            return self.prev_H2init
+        return self._local_fit(src_xy, dst_xy, w, grid, (rect[2], rect[3]), mask_win, p, undo=lambda H: window.H_undo_crop(box, H))

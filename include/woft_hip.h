@@ -459,6 +459,26 @@ int woft_flow_chain_fold(const float* prev_flow, const float* prev_cost, const f
                          float vis_thr, int32_t k, int32_t first, float* best_flow, float* best_cost, float* best_vis,
                          int32_t* best_sel, void* stream);
 
+/* woft_flow_chain_fold on two rectangles, with an optional closing homography (csrc/flow_multi.hip).  DESIGN.md section 26.
+ * prev_* and best_* are [th][tw] planes (flows [2][th][tw]): plane pixel (x, y) is template pixel P = (tx0 + x, ty0 + y).
+ * step_* are [sh][sw] planes (step_flow [2][sh][sw]) covering the rectangle with origin (sx0, sy0) of frames s and t.  Flows are
+ * displacements in frame coordinates.  Per template pixel, in the expression tree of woft_flow_chain_fold:
+ *   q    = (float)P + prev_flow                                     fp32 (P itself for the NULL prev triple)
+ *   u    = q - (float)(sx0, sy0)                                    fp32; exact wherever the tap is valid (Sterbenz / integers)
+ *   valid iff u in [0, sw-1] x [0, sh-1]; the taps, their addresses (from clamped floats) and weights are those of u in [sh][sw]
+ *   flow = prev_flow + s(step_flow, u); cost, vis, finiteness rules, key, tie rule and the `first` rule: woft_flow_chain_fold's.
+ * post_H (host, 9 doubles row-major, or NULL): r = (double)P + (double)flow, den = h6 rx + h7 ry + h8; the candidate is invalid
+ * unless den > 0 and the mapped point is finite; flow = (float)(H r / den - (double)P), in fp64 with one final rounding.
+ * With both origins 0, th == sh, tw == sw and no post_H the bytes are woft_flow_chain_fold's.  No LDS, no atomics, no workspace;
+ * no input, finite or not, produces an address outside a plane.
+ * -1 (before any launch) on everything woft_flow_chain_fold rejects (the overlap rule with each plane's own size), a side <= 0,
+ * a negative origin, origin + side > 2^24, a non-finite post_H, post_H[8] != 1 (the host normalises the matrix). */
+int woft_flow_chain_fold_window(const float* prev_flow, const float* prev_cost, const float* prev_vis, int32_t th, int32_t tw,
+                                int32_t ty0, int32_t tx0, const float* step_flow, const float* step_wlogit,
+                                const float* step_mlogit, int32_t sh, int32_t sw, int32_t sy0, int32_t sx0, const double* post_H,
+                                float unit_cost, float vis_thr, int32_t k, int32_t first, float* best_flow, float* best_cost,
+                                float* best_vis, int32_t* best_sel, void* stream);
+
 /* A fold result as correspondences for the planar fit (csrc/flow_multi.hip).  DESIGN.md section 19.  flow [2][gh][gw], cost, vis
  * [gh][gw] fp32 and sel [gh][gw] int32 are what woft_flow_chain_fold leaves; tmask is the frame-sized template mask of
  * woft_tc_select, uint8 [mh][mw] with gh <= mh, gw <= mw, pixel (x, y) of the grid at tmask[y * mw + x] (NULL: every pixel counts;
@@ -481,6 +501,17 @@ int woft_flow_chain_fold(const float* prev_flow, const float* prev_cost, const f
 #define WOFT_CHAIN_HIST 130
 int woft_chain_tc(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask, int32_t gh,
                   int32_t gw, int32_t mh, int32_t mw, float vis_thr, float* dst, float* w, float* ok, int32_t* hist, void* stream);
+/* woft_chain_tc on a template rectangle (csrc/flow_multi.hip).  DESIGN.md section 26.  The [gh][gw] planes are those of
+ * woft_flow_chain_fold_window: pixel (x, y) is template pixel (tx0 + x, ty0 + y) of a frame_h x frame_w frame; tmask is the
+ * CROPPED mask, pixel (x, y) of the window at tmask[y * mw + x].  dst (window coordinates, (float)x + flow_x), w and hist: the
+ * bytes woft_chain_tc writes for the same planes and mask.  ok is woft_chain_tc's, and additionally 0 where the landing in frame
+ * coordinates X = (float)(tx0 + x) + flow_x, Y = (float)(ty0 + y) + flow_y fails the selection kernels' rule:
+ * X < 0 or Y < 0 or rintf(X) >= frame_w or rintf(Y) >= frame_h.  (hist counts by woft_chain_tc's `seen`, not by this rule.)
+ * -1 (before any launch) on everything woft_chain_tc rejects, a negative origin, origin + side > 2^24, frame_h or frame_w <= 0
+ * or > 2^24. */
+int woft_chain_tc_window(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask,
+                         int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t ty0, int32_t tx0, int32_t frame_h,
+                         int32_t frame_w, float vis_thr, float* dst, float* w, float* ok, int32_t* hist, void* stream);
 /* woft_chain_tc for several template masks at once (csrc/flow_multi.hip).  DESIGN.md section 25.  The masks are one bit plane:
  * tbits, uint32 [mh][mw] with gh <= mh, gw <= mw, bit t of tbits[y * mw + x] set where pixel (x, y) lies in target t's mask,
  * 1 <= n_targets <= 32, masks may overlap; bits at and above n_targets are ignored.  dst, w (may be NULL) and ok do not depend on

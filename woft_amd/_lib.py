@@ -103,6 +103,9 @@ _SIGS = {
     "woft_flow_fb": (i32, [vp, vp, i32, i32, f32, f32, vp, vp, vp]),
     "woft_flow_chain_fold": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp]),
     "woft_chain_tc": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "woft_flow_chain_fold_window": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), f32, f32,
+                                          i32, i32, vp, vp, vp, vp, vp]),
+    "woft_chain_tc_window": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
     "woft_chain_tc_multi": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
     "woft_features_pack": (i32, [vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, vp, vp]),
     "woft_features_unpack": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp]),

@@ -153,13 +153,16 @@ class WOFTChained(YAOFTrackerSingleControl):
     def init(self, img, mask, img_identifier=None):
         super().init(img, mask, img_identifier)                      # (single-contour check, mask tensors, state: the parent's)
         self.multi = self._new_multi()
-        self.multi.init(img)
+        self._init_multi(img)
         # the chains read every pixel of every flow: no weight region, no flow region, no deferred weights
         if hasattr(self.flower, "pin_weight_region"):
             self.flower.pin_weight_region(None)
         if hasattr(self.flower, "pin_flow_region"):
             self.flower.pin_flow_region(None)
         self._sparse_weights = False
+
+    def _init_multi(self, img):
+        self.multi.init(img)                      # (the windowed tracker also names the template's rectangle here)
 
     def set_fast_meta(self, meta):
         raise NotImplementedError("Fastforward is not provided by the chained tracker: a replayed frame would leave a hole in the "

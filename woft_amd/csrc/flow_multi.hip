@@ -3,6 +3,7 @@
 // DESIGN.md section 18.  One streaming kernel with a local gather, one template pixel per lane: no LDS, no atomics, no workspace.
 // Below it, the step from a fold result to the planar fit's correspondences (woft_chain_tc): streaming, no
 // gather, the 130 integer counters of its histogram in LDS.
+// Both have a form on rectangles (woft_flow_chain_fold_window, woft_chain_tc_window): flows on search windows.
 //
 // The sampler, its address rule and the launch geometry are those of flow_chain.hip (flow_sample.h): every tap address derives
 // from a clamped float, so no input, finite or not, addresses outside a plane; the pixel's own planes are read at (x, y) of the
@@ -66,6 +67,75 @@ __global__ __launch_bounds__(FC_T) void flow_chain_fold_kernel(const float* __re
     }
 }
 
+// The closing homography of flow_chain_fold_window_kernel: nine host doubles passed by value (no device buffer, no workspace).
+struct PostH {
+    double h[9];
+};
+
+// flow_chain_fold_kernel on two rectangles: the prev / best planes are the [th][tw] rectangle of the template
+// with origin (tx0, ty0), the step planes the [sh][sw] rectangle with origin (sx0, sy0) of frames s and t; flows stay displacements
+// in frame coordinates.  q is formed in frame coordinates, u = q - (step origin) is exact wherever the tap is valid, and the taps are
+// those of u in the step planes: every address still derives from a float clamped into [0, sw-1] x [0, sh-1].  POST: the candidate's
+// landing goes through a homography in fp64 (den <= 0 or a non-finite image: invalid), one rounding back to the fp32 flow.
+template <bool POST>
+__global__ __launch_bounds__(FC_T) void flow_chain_fold_window_kernel(
+    const float* __restrict__ prev_flow, const float* __restrict__ prev_cost, const float* __restrict__ prev_vis, int th, int tw, int ty0,
+    int tx0, const float* __restrict__ step_flow, const float* __restrict__ step_wlogit, const float* __restrict__ step_mlogit, int sh,
+    int sw, int sy0, int sx0, PostH H, float unit_cost, float vis_thr, int k, int first, float* __restrict__ best_flow,
+    float* __restrict__ best_cost, float* __restrict__ best_vis, int32_t* __restrict__ best_sel) {
+    const int64_t plane = (int64_t)th * tw, splane = (int64_t)sh * sw;
+    const int x = (int)blockIdx.x * FC_TX + (int)threadIdx.x;
+    if (x >= tw) return;
+    const float px = (float)(tx0 + x), ox = (float)sx0, oy = (float)sy0;
+    for (int y = (int)blockIdx.y * FC_TY + (int)threadIdx.y; y < th; y += (int)gridDim.y * FC_TY) {
+        const int64_t i = (int64_t)y * tw + x;
+        const float py = (float)(ty0 + y);
+        float pfx = 0.f, pfy = 0.f, pc = 0.f, pv = 1.f;
+        if (prev_flow != nullptr) {
+            pfx = prev_flow[i], pfy = prev_flow[plane + i];
+            pc = prev_cost[i], pv = prev_vis[i];
+        }
+        const float qx = px + pfx, qy = py + pfy;
+        const TapAt t = tap_at(sh, sw, qx - ox, qy - oy);
+        float fx = pfx + tap_plane(step_flow, t), fy = pfy + tap_plane(step_flow + splane, t);
+        bool ok = t.valid;
+        float cost = pc + unit_cost, vis = pv;
+        if (step_wlogit != nullptr) {
+            const float l = tap_plane(step_wlogit, t);
+            ok = ok && isfinite(l);
+            cost = pc + softplus_neg(l);
+        }
+        if (step_mlogit != nullptr) {
+            const float m = tap_plane(step_mlogit, t);
+            ok = ok && isfinite(m);
+            vis = pv * sigmoidf_(m);
+        }
+        if constexpr (POST) {
+            const double Px = (double)px, Py = (double)py;
+            const double rx = Px + (double)fx, ry = Py + (double)fy;
+            const double den = H.h[6] * rx + H.h[7] * ry + H.h[8];
+            const double mx = (H.h[0] * rx + H.h[1] * ry + H.h[2]) / den, my = (H.h[3] * rx + H.h[4] * ry + H.h[5]) / den;
+            ok = ok && den > 0.0 && isfinite(mx) && isfinite(my);                  // (a NaN fails)
+            fx = (float)(mx - Px), fy = (float)(my - Py);
+        }
+        ok = ok && isfinite(fx) && isfinite(fy) && isfinite(cost) && isfinite(vis);
+        // key (occluded, cost), lexicographic; an equal key keeps the earlier fold
+        bool replace = ok;
+        if (ok && !first && best_sel[i] >= 0) {
+            const float bc = best_cost[i];
+            const bool bocc = best_vis[i] < vis_thr, occ = vis < vis_thr;
+            replace = (bocc && !occ) || (bocc == occ && cost < bc);
+        }
+        if (replace) {
+            best_flow[i] = fx, best_flow[plane + i] = fy;
+            best_cost[i] = cost, best_vis[i] = vis, best_sel[i] = k;
+        } else if (first) {
+            best_flow[i] = NAN, best_flow[plane + i] = NAN;
+            best_cost[i] = INFINITY, best_vis[i] = 0.f, best_sel[i] = -1;
+        }
+    }
+}
+
 constexpr unsigned CHAIN_TC_BLOCKS = 2048;        // blocks of a launch with a histogram: 256 CUs x 8 blocks of 4 waves
 
 // A fold result turned into what the planar fit reads: target coordinates, the fit weight exp(-cost), the
@@ -73,11 +143,15 @@ constexpr unsigned CHAIN_TC_BLOCKS = 2048;        // blocks of a launch with a h
 // comes from the launch geometry and addresses everything; `sel` is the only input value used as an index, range-checked first,
 // and it indexes the LDS counters alone.  A wave is one row segment (FC_TX = 64 lanes), so y and the loop's trip count are
 // wave-uniform and every lane of a wave reaches the ballots below.
+// WINDOW (woft_chain_tc_window): the planes are the rectangle with origin (tx0, ty0) of a frame_h x frame_w
+// frame and tmask is the cropped mask; dst (window coordinates), w and hist are unchanged, ok is additionally 0 where the landing in
+// FRAME coordinates fails the selection kernels' in-frame rule, so the planar stage needs no bounds check of its own.
+template <bool WINDOW>
 __global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict__ flow, const float* __restrict__ cost,
                                                         const float* __restrict__ vis, const int32_t* __restrict__ sel,
-                                                        const uint8_t* __restrict__ tmask, int gh, int gw, int mw, float vis_thr,
-                                                        float* __restrict__ dst, float* __restrict__ w, float* __restrict__ ok,
-                                                        int32_t* __restrict__ hist) {
+                                                        const uint8_t* __restrict__ tmask, int gh, int gw, int mw, int ty0, int tx0,
+                                                        float frame_h, float frame_w, float vis_thr, float* __restrict__ dst,
+                                                        float* __restrict__ w, float* __restrict__ ok, int32_t* __restrict__ hist) {
     __shared__ int32_t bins[WOFT_CHAIN_HIST];
     const int tid = (int)threadIdx.y * FC_TX + (int)threadIdx.x;
     if (hist != nullptr) {
@@ -95,10 +169,15 @@ __global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict_
             const int32_t s = sel[i];
             const bool valid = s >= 0 && s < WOFT_CHAIN_HIST - 2 && isfinite(fx) && isfinite(fy) && isfinite(c) && isfinite(v);
             const bool seen = valid && !(v < vis_thr);                    // the fold's occlusion rule
+            bool gate = seen;
+            if constexpr (WINDOW) {
+                const float X = (float)(tx0 + x) + fx, Y = (float)(ty0 + y) + fy;
+                gate = seen && !(X < 0.f || Y < 0.f || rintf(X) >= frame_w || rintf(Y) >= frame_h);
+            }
             dst[i] = valid ? (float)x + fx : NAN;
             dst[plane + i] = valid ? (float)y + fy : NAN;
             if (w != nullptr) w[i] = valid ? expf(-c) : 0.f;
-            ok[i] = seen ? 1.f : 0.f;
+            ok[i] = gate ? 1.f : 0.f;
             if (hist != nullptr && (tmask == nullptr || tmask[(int64_t)y * mw + x] != 0))
                 bin = !valid ? WOFT_CHAIN_HIST - 2 : (seen ? s : WOFT_CHAIN_HIST - 1);
         }
@@ -207,10 +286,18 @@ extern "C" int woft_flow_chain_fold(const float* prev_flow, const float* prev_co
     return woft_launch_status();
 }
 
-extern "C" int woft_chain_tc(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask,
-                             int32_t gh, int32_t gw, int32_t mh, int32_t mw, float vis_thr, float* dst, float* w, float* ok,
-                             int32_t* hist, void* stream) {
+namespace {
+
+// a rectangle's origin and side on one axis: origin >= 0, side >= 1, origin + side <= 2^24 (every coordinate is exact in fp32)
+inline bool bad_span(int32_t origin, int32_t side) { return origin < 0 || side <= 0 || (int64_t)origin + side > FC_MAX_SIDE; }
+
+// the checks and the launch of woft_chain_tc and woft_chain_tc_window (WINDOW: the rectangle's origin and the frame's size)
+template <bool WINDOW>
+int chain_tc_launch(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask, int32_t gh,
+                    int32_t gw, int32_t mh, int32_t mw, int32_t ty0, int32_t tx0, int32_t frame_h, int32_t frame_w, float vis_thr,
+                    float* dst, float* w, float* ok, int32_t* hist, void* stream) {
     if (!flow || !cost || !vis || !sel || !dst || !ok || bad_side(gh, gw)) return WOFT_EINVAL;
+    if (WINDOW && (bad_span(ty0, gh) || bad_span(tx0, gw) || bad_side(frame_h, frame_w))) return WOFT_EINVAL;
     if (tmask != nullptr && (mh < gh || mw < gw)) return WOFT_EINVAL;
     if (!(vis_thr >= 0.f && vis_thr <= 1.f)) return WOFT_EINVAL;                                                  // (NaN fails)
     // every pixel's outputs are written while other pixels' inputs are still unread: an output may share no byte with an input or
@@ -236,9 +323,24 @@ extern "C" int woft_chain_tc(const float* flow, const float* cost, const float* 
         const unsigned rows = CHAIN_TC_BLOCKS / grid.x;
         grid.y = grid.y < rows ? grid.y : (rows > 0 ? rows : 1u);
     }
-    hipLaunchKernelGGL(chain_tc_kernel, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tmask, gh, gw,
-                       tmask ? mw : gw, vis_thr, dst, w, ok, hist);
+    hipLaunchKernelGGL(chain_tc_kernel<WINDOW>, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tmask, gh, gw,
+                       tmask ? mw : gw, ty0, tx0, (float)frame_h, (float)frame_w, vis_thr, dst, w, ok, hist);
     return woft_launch_status();
+}
+
+}  // namespace
+
+extern "C" int woft_chain_tc(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask,
+                             int32_t gh, int32_t gw, int32_t mh, int32_t mw, float vis_thr, float* dst, float* w, float* ok,
+                             int32_t* hist, void* stream) {
+    return chain_tc_launch<false>(flow, cost, vis, sel, tmask, gh, gw, mh, mw, 0, 0, 0, 0, vis_thr, dst, w, ok, hist, stream);
+}
+
+extern "C" int woft_chain_tc_window(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint8_t* tmask,
+                                    int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t ty0, int32_t tx0, int32_t frame_h,
+                                    int32_t frame_w, float vis_thr, float* dst, float* w, float* ok, int32_t* hist, void* stream) {
+    return chain_tc_launch<true>(flow, cost, vis, sel, tmask, gh, gw, mh, mw, ty0, tx0, frame_h, frame_w, vis_thr, dst, w, ok, hist,
+                                 stream);
 }
 
 extern "C" int woft_chain_tc_multi(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits,
@@ -267,5 +369,43 @@ extern "C" int woft_chain_tc_multi(const float* flow, const float* cost, const f
     grid.y = grid.y < rows ? grid.y : (rows > 0 ? rows : 1u);
     hipLaunchKernelGGL(chain_tc_multi_kernel, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tbits, gh, gw,
                        mw, n_targets, vis_thr, dst, w, ok, hist);
+    return woft_launch_status();
+}
+
+extern "C" int woft_flow_chain_fold_window(const float* prev_flow, const float* prev_cost, const float* prev_vis, int32_t th, int32_t tw,
+                                           int32_t ty0, int32_t tx0, const float* step_flow, const float* step_wlogit,
+                                           const float* step_mlogit, int32_t sh, int32_t sw, int32_t sy0, int32_t sx0,
+                                           const double* post_H, float unit_cost, float vis_thr, int32_t k, int32_t first,
+                                           float* best_flow, float* best_cost, float* best_vis, int32_t* best_sel, void* stream) {
+    if (!step_flow || !best_flow || !best_cost || !best_vis || !best_sel) return WOFT_EINVAL;
+    if (bad_span(ty0, th) || bad_span(tx0, tw) || bad_span(sy0, sh) || bad_span(sx0, sw)) return WOFT_EINVAL;
+    const int n_prev = (prev_flow != nullptr) + (prev_cost != nullptr) + (prev_vis != nullptr);
+    if (n_prev != 0 && n_prev != 3) return WOFT_EINVAL;
+    if (!(unit_cost >= 0.f) || !(vis_thr >= 0.f && vis_thr <= 1.f) || k < 0 || k > 127) return WOFT_EINVAL;    // (NaN fails)
+    PostH H = {};
+    if (post_H != nullptr) {
+        for (int j = 0; j < 9; ++j) {
+            if (!std::isfinite(post_H[j])) return WOFT_EINVAL;
+            H.h[j] = post_H[j];
+        }
+        if (post_H[8] != 1.0) return WOFT_EINVAL;
+    }
+    // as woft_flow_chain_fold: the running best may share no byte with an input or with itself (each plane with its own size)
+    const uint64_t tb = (uint64_t)th * (uint64_t)tw * 4u, sb = (uint64_t)sh * (uint64_t)sw * 4u;
+    const void* outs[4] = {best_flow, best_cost, best_vis, best_sel};
+    const void* ins[6] = {prev_flow, prev_cost, prev_vis, step_flow, step_wlogit, step_mlogit};
+    const uint64_t nin[6] = {2 * tb, tb, tb, 2 * sb, sb, sb};
+    for (int a = 0; a < 4; ++a) {
+        const uint64_t na = a == 0 ? 2 * tb : tb;
+        for (int b = 0; b < 6; ++b)
+            if (overlap(outs[a], na, ins[b], nin[b])) return WOFT_EINVAL;
+        for (int b = a + 1; b < 4; ++b)
+            if (overlap(outs[a], na, outs[b], tb)) return WOFT_EINVAL;
+    }
+    // two instantiations: the chained candidates (no post_H) carry no fp64 code
+    auto kernel = post_H != nullptr ? flow_chain_fold_window_kernel<true> : flow_chain_fold_window_kernel<false>;
+    hipLaunchKernelGGL(kernel, pixel_grid(th, tw), dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, prev_flow, prev_cost, prev_vis, th, tw,
+                       ty0, tx0, step_flow, step_wlogit, step_mlogit, sh, sw, sy0, sx0, H, unit_cost, vis_thr, k, first != 0, best_flow,
+                       best_cost, best_vis, best_sel);
     return woft_launch_status();
 }

@@ -778,6 +778,87 @@ def chain_tc(flow, cost, vis, sel, tmask_u8, vis_thr, want_w=True, mask_hw=None,
     return dst, wout, ok, hist
 
 
+def _post_h9(post_H):
+    """A closing homography -> the 9 doubles woft_flow_chain_fold_window takes (h8 = 1: normalised here); None -> NULL."""
+    if post_H is None:
+        return None
+    Hm = np.asarray(post_H, dtype=np.float64)
+    if Hm.shape != (3, 3) or not np.all(np.isfinite(Hm)) or Hm[2, 2] == 0.0:
+        raise ValueError(f"flow_chain_fold_window: post_H must be a finite 3 x 3 matrix with a non-zero last entry, got {post_H!r}")
+    Hm = Hm / Hm[2, 2]
+    Hm[2, 2] = 1.0
+    if not np.all(np.isfinite(Hm)):
+        raise ValueError(f"flow_chain_fold_window: post_H does not normalise to a finite matrix, got {post_H!r}")
+    return (C.c_double * 9)(*Hm.ravel().tolist())
+
+
+def flow_chain_fold_window(best, prev, step_flow, step_wlogit=None, step_mlogit=None, k=0, template_rect=None, step_rect=None,
+                           post_H=None, vis_thr=0.5, unit_cost=1.0, first=False):
+    """flow_chain_fold on two rectangles (woft_flow_chain_fold_window).  template_rect = (y0, x0, rows, cols):
+    the template rectangle of the best / prev planes ((2, rows, cols) flows, rows * cols elements per plane); step_rect likewise
+    for step_flow (2, rows, cols) and the step's logits, the same rectangle of frames s and t.  Flows are displacements in frame
+    coordinates.  post_H (3 x 3, optional): the candidate's landing is mapped through it in fp64 (normalised to h8 = 1 here).
+    best = None allocates the running best (then `first` must be set); it is updated in place and returned."""
+    assert step_flow.dim() == 3 and step_flow.shape[0] == 2 and _f32c(step_flow)
+    sy0, sx0, sh, sw = (int(v) for v in step_rect)
+    ty0, tx0, th, tw = (int(v) for v in template_rect)
+    assert tuple(step_flow.shape[1:]) == (sh, sw), f"step flow {tuple(step_flow.shape)} is not on the step rect {(sh, sw)}"
+    n, ns = th * tw, sh * sw
+    plane = lambda t, m: t is None or (_f32c(t) and t.numel() == m)
+    assert plane(step_wlogit, ns) and plane(step_mlogit, ns)
+    if prev is not None:
+        assert len(prev) == 3 and _f32c(prev[0], 2, th, tw) and prev[1] is not None and prev[2] is not None \
+            and plane(prev[1], n) and plane(prev[2], n)
+    k, vis_thr, unit_cost = int(k), float(vis_thr), float(unit_cost)
+    if not 0 <= k <= 127:
+        raise ValueError(f"flow_chain_fold_window: k must be in [0, 127], got {k}")
+    if not (0.0 <= vis_thr <= 1.0) or not (unit_cost >= 0.0):
+        raise ValueError(f"flow_chain_fold_window: vis_thr must be in [0, 1] and unit_cost >= 0, got {vis_thr!r}, {unit_cost!r}")
+    h9 = _post_h9(post_H)
+    if best is None:
+        assert first, "flow_chain_fold_window: without a running best the fold must be the first"
+        new = lambda dtype, *s: torch.empty(s, dtype=dtype, device=step_flow.device)
+        best = (new(torch.float32, 2, th, tw), new(torch.float32, th, tw), new(torch.float32, th, tw), new(torch.int32, th, tw))
+    bf, bc, bv, bs = best
+    assert _f32c(bf, 2, th, tw) and bc is not None and bv is not None and plane(bc, n) and plane(bv, n)
+    assert bs.dtype == torch.int32 and bs.is_contiguous() and bs.is_cuda and bs.numel() == n
+    pf, pc, pv = prev if prev is not None else (None, None, None)
+    check(_lib.load().woft_flow_chain_fold_window(ptr(pf), ptr(pc), ptr(pv), th, tw, ty0, tx0, ptr(step_flow), ptr(step_wlogit),
+                                                  ptr(step_mlogit), sh, sw, sy0, sx0, h9, unit_cost, vis_thr, k, int(bool(first)),
+                                                  ptr(bf), ptr(bc), ptr(bv), ptr(bs), stream_ptr()), "woft_flow_chain_fold_window")
+    return best
+
+
+def chain_tc_window(flow, cost, vis, sel, tmask_u8, vis_thr, origin, frame_hw, want_w=True, mask_hw=None, out=None):
+    """chain_tc on a template rectangle (woft_chain_tc_window): flow (2, H, W) etc. are the planes of the
+    rectangle with origin = (y0, x0) in a frame of frame_hw = (frame_h, frame_w); tmask_u8 is the CROPPED mask (mask_hw >= (H, W),
+    default the grid's size).  dst (window coordinates), w and hist are chain_tc's bytes; ok is additionally 0 where the landing
+    leaves the frame (the selection kernels' rule in frame coordinates)."""
+    assert flow.dim() == 3 and flow.shape[0] == 2 and _f32c(flow)
+    h, w = flow.shape[1:]
+    n = h * w
+    assert all(_f32c(t) and t.numel() == n for t in (cost, vis))
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.is_cuda and sel.numel() == n
+    vis_thr = float(vis_thr)
+    if not (0.0 <= vis_thr <= 1.0):
+        raise ValueError(f"chain_tc_window: vis_thr must be in [0, 1], got {vis_thr!r}")
+    mh, mw = mask_hw or (h, w)
+    if tmask_u8 is not None:
+        assert tmask_u8.dtype == torch.uint8 and tmask_u8.is_contiguous() and tmask_u8.is_cuda and tmask_u8.numel() == mh * mw
+    if out is None:
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=flow.device)
+        out = (new(2, n), new(1, n) if want_w else None, new(1, n), torch.empty(CHAIN_HIST, dtype=torch.int32, device=flow.device))
+    dst, wout, ok, hist = out
+    if not want_w:
+        wout = None
+    assert _f32c(dst, 2, n) and _f32c(ok, 1, n) and (wout is None or _f32c(wout, 1, n))
+    assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda and hist.numel() == CHAIN_HIST)
+    check(_lib.load().woft_chain_tc_window(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tmask_u8), h, w, mh, mw, int(origin[0]),
+                                           int(origin[1]), int(frame_hw[0]), int(frame_hw[1]), vis_thr, ptr(dst), ptr(wout),
+                                           ptr(ok), ptr(hist), stream_ptr()), "woft_chain_tc_window")
+    return dst, wout, ok, hist
+
+
 MULTI_MAX_TARGETS = 32  # WOFT_MULTI_MAX_TARGETS: the targets of one bit plane (uint32 per pixel)
 
 

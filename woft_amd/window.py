@@ -105,6 +105,35 @@ def search_box(mask_box, margin, width, height, min_size=MIN_WINDOW, clip=True):
     return box.intersection(frame) if clip else box
 
 
+def check_quantum(quantum):
+    """A window quantum -> the int; ValueError unless it is a positive multiple of 8 (the flow provider's feature stride)."""
+    if isinstance(quantum, bool) or not isinstance(quantum, (int, np.integer)) or quantum <= 0 or quantum % 8:
+        raise ValueError(f"chain_rect: quantum must be a positive multiple of 8, got {quantum!r}")
+    return int(quantum)
+
+
+def chain_rect(mask_box, margin, width, height, quantum=64, min_size=MIN_WINDOW):
+    """The rectangle (y0, x0, rows, cols) the windowed chained tracker (woft_amd.chained_window) runs a flow on: the crop of
+    search_box(mask_box, margin, ...), with each side grown to a multiple of `quantum` around its centre and pushed back inside
+    the frame; a side that would reach the frame's takes the whole side.  A falsy margin: the whole frame, (0, 0, height, width)
+    -- every row and column, unlike Box.frame(..).crop_rect(), so that the whole-frame case is WOFTChained's.
+    Quantised sides repeat from frame to frame while the box follows the object: the flow provider keeps one plan per padded
+    size, so the sizes it meets stay few.  quantum: a positive multiple of 8 (the provider's feature stride)."""
+    quantum = check_quantum(quantum)
+    width, height = int(width), int(height)
+    if not margin:
+        return 0, 0, height, width
+    y0, x0, rows, cols = search_box(mask_box, margin, width, height, min_size).crop_rect()
+
+    def axis(origin, size, side):
+        n = -(-int(size) // quantum) * quantum
+        if n >= side:
+            return 0, side
+        return min(max(int(origin) - (n - int(size)) // 2, 0), side - n), n
+    (y0, rows), (x0, cols) = axis(y0, rows, height), axis(x0, cols, width)
+    return y0, x0, rows, cols
+
+
 def H_undo_crop(box, H_window):
     """A homography between two crops by `box` -> the same map in frame coordinates: T(+tl) H T(-tl) for column vectors."""
     to_window = np.array([[1, 0, -box.tl_x], [0, 1, -box.tl_y], [0, 0, 1.0]])

@@ -794,6 +794,50 @@ int woft_hsynth_render_bg(const uint8_t* base, int32_t hs, int32_t ws, const dou
 int woft_hsynth_augment(const float* in_f32, int32_t h, int32_t w, const float* taps, int32_t radius, const float* colour,
                         float noise_sigma, uint32_t seed, uint8_t* out_u8, float* out_f32, void* stream);
 
+/* Photometric refinement of a homography (csrc/photo.hip; DESIGN.md section 27, this project's own semantics): inverse-compositional
+ * Gauss-Newton of a template (h, w, 3) against a frame (hf, wf, 3), each uint8 or float32 (tmpl_f32 / frame_f32), on the pixels
+ * Omega of the uint8 mask (h, w): mask > 0, 1 <= x <= w - 2, 1 <= y <= h - 2, (x - x0) % stride == 0 and (y - y0) % stride == 0 with
+ * box = {x0, y0, x1, y1} (HOST, inclusive, inside the template: the mask's bounding box).  S = c0 + c1 + c2; template gradient by
+ * central differences; normalised coordinates x~ = (x - cx) / s with cx = (x0 + x1) / 2, cy = (y0 + y1) / 2, s = max(x1 - x0,
+ * y1 - y0, 1) / 2.  At a state (M = W N^-1, gain g, bias b in units of S) a pixel is valid iff q = M (x~, y~, 1) has qz > 0 and
+ * u = qx / qz in [0, wf - 1), v = qy / qz in [0, hf - 1); I = the bilinear sample of S_frame, (1 - fy) ((1 - fx) s00 + fx s01) +
+ * fy ((1 - fx) s10 + fx s11); e = I - g T - b; omega = weight (weights (h, w) float32 or NULL: 1) times the Huber factor
+ * (huber_k > 0, in grey levels: k = 3 huber_k; huber_k < 0: none); row a = g [gx~ x~, gx~ y~, gx~, gy~ x~, gy~ y~, gy~, -x~ d,
+ * -y~ d], d = gx~ x~ + gy~ y~, and with gain_bias: T, 1.  Everything fp64.
+ * woft_photo_eval: out (device) = upper triangle of G = sum omega a a^T row-major (nu (nu + 1) / 2, nu = 10 with gain_bias else 8),
+ *   r = sum omega a e (nu), sum weight * rho, sum weight, n_valid, at the state (W HOST 3x3 template -> frame pixels, gain, bias).
+ *   Two launches: one partial per workgroup of WOFT_PHOTO_CHUNK candidates, then their sum in index order.
+ * woft_photo_refine: iters + 1 (accumulate, step) launch pairs from W0 (HOST), g = 1, b = 0; the step launch records iterate k,
+ *   applies the control rules of DESIGN.md section 27 (n_need = the valid-pixel threshold, eps the step in frame pixels of the
+ *   box's corners below which the next iterate is the last), solves by Cholesky without a ridge and steps M <- M Delta^-1.
+ *   Launches after a stop return at once.  result (device, WOFT_PHOTO_REC * (iters + 2) doubles): [0] status, [1] best iterate or
+ *   -1, [2] iterates evaluated, [3..11] the best iterate's W; then per iterate k at WOFT_PHOTO_REC * (1 + k): W_k (9, h33 = 1),
+ *   g_k, b_k / 3, sqrt(cost_k) / 3, n_k, step_k (NaN when no step was taken).  Only the first [2] records are written.
+ * ws: woft_photo_ws_bytes(x1 - x0 + 1, y1 - y0 + 1, stride) bytes (-1 on a non-positive argument), 8-byte aligned.  No atomics:
+ * two calls give equal bytes.  WOFT_EINVAL before any launch on a NULL tmpl / mask / frame / box / W / ws / out / result, h or
+ * w < 3, hf or wf < 1, an image of 2^31 pixels or more, a box outside the template or empty, stride < 1, huber_k zero or NaN, a
+ * non-finite W / gain / bias / eps, eps < 0, iters outside 0 .. WOFT_PHOTO_MAX_ITERS, n_need < 0. */
+#define WOFT_PHOTO_NACC 68
+#define WOFT_PHOTO_CHUNK 2048
+#define WOFT_PHOTO_REC 16
+#define WOFT_PHOTO_MAX_ITERS 64
+enum woft_photo_status {
+    WOFT_PHOTO_CONVERGED = 0,
+    WOFT_PHOTO_MAX_ITERS_REACHED = 1,
+    WOFT_PHOTO_TOO_FEW = 2,
+    WOFT_PHOTO_SINGULAR = 3,
+    WOFT_PHOTO_NONFINITE = 4
+};
+int64_t woft_photo_ws_bytes(int32_t box_w, int32_t box_h, int32_t stride);
+int woft_photo_eval(const void* tmpl, int32_t tmpl_f32, const uint8_t* mask, int32_t h, int32_t w, const float* weights,
+                    const void* frame, int32_t frame_f32, int32_t hf, int32_t wf, const int32_t* box, int32_t stride,
+                    const double* W, double gain, double bias, int32_t gain_bias, double huber_k, void* ws, double* out,
+                    void* stream);
+int woft_photo_refine(const void* tmpl, int32_t tmpl_f32, const uint8_t* mask, int32_t h, int32_t w, const float* weights,
+                      const void* frame, int32_t frame_f32, int32_t hf, int32_t wf, const int32_t* box, int32_t stride,
+                      const double* W0, int32_t iters, int32_t gain_bias, double huber_k, int32_t n_need, double eps, void* ws,
+                      double* result, void* stream);
+
 /* cv2.resize(img, None, fx, fy) with INTER_LINEAR geometry (tracker/YAOF_tracker_single_control.py:27-30,60-61,
  * `downscale_inputs`): src = (dst + 0.5) * scale - 0.5, edge clamped; scale = 1 / fx. */
 int woft_resize_linear_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, uint8_t* out, int32_t ho, int32_t wo,

@@ -22,6 +22,9 @@ def __getattr__(name):
                 "augment", "blur_taps", "colour_matrix"):
         from . import hsynth
         return getattr(hsynth, name)
+    if name in ("PhotoTemplate", "refine_homography"):
+        from . import photo
+        return getattr(photo, name)
     if name == "FrameFeatures":
         from .flow_provider import FrameFeatures
         return FrameFeatures

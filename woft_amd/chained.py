@@ -109,6 +109,8 @@ class WOFTChained(YAOFTrackerSingleControl):
         ("downscale_inputs", "the stored frames and results of the chains are kept at the input's size"),
         ("search_window_margin", "the chains read every pixel of every flow; the search-window tracker is WOFTWindow"),
         ("post_hoc_weights_postprocessing_fn", "the fit weight is exp(-chain cost), not a weight map to post-process"),
+        ("photo_refine", "the chained trackers' pose has no per-frame template-to-frame stage to refine from (no pre-warp: the "
+                         "chains carry the motion); the photometric refinement runs in YAOFTrackerSingleControl and WOFTWindow"),
     )
 
     def _refusals(self, config):

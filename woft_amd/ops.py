@@ -1429,3 +1429,54 @@ def inlier_frac_batched(pa, pb, Hm, frac, thr=5.0, counts=None):
                                                                               and counts.is_contiguous()))
     check(_lib.load().woft_inlier_frac_batched(ptr(pa), ptr(pb), B, n, ptr(counts), ptr(Hm), float(thr), ptr(frac), stream_ptr()),
           "woft_inlier_frac_batched")
+
+
+_PHOTO_WS = {}
+PHOTO_NACC, PHOTO_REC, PHOTO_MAX_ITERS, PHOTO_CHUNK = 68, 16, 64, 2048       # the WOFT_PHOTO_* constants of include/woft_hip.h
+PHOTO_STATUS = ("CONVERGED", "MAX_ITERS", "TOO_FEW", "SINGULAR", "NONFINITE")      # enum woft_photo_status
+
+
+def photo_ws(box, stride, device=None):
+    """Scratch of woft_photo_eval / woft_photo_refine for the inclusive box (x0, y0, x1, y1), one per device and stream like
+    hfit_ws, grown on demand."""
+    need = int(_lib.load().woft_photo_ws_bytes(box[2] - box[0] + 1, box[3] - box[1] + 1, int(stride)))
+    if need < 0:
+        raise _lib.WoftHipError(f"woft_photo_ws_bytes rejected box {tuple(box)!r}, stride {stride!r}")
+    return _stream_scratch(_PHOTO_WS, need, device)
+
+
+def _photo_images(tmpl, mask, weights, frame):
+    for t, what in ((tmpl, "template"), (frame, "frame")):
+        assert t.dtype in (torch.uint8, torch.float32) and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous(), what
+    h, w = tmpl.shape[:2]
+    assert mask.dtype == torch.uint8 and tuple(mask.shape) == (h, w) and mask.is_contiguous()
+    assert weights is None or (_f32c(weights) and tuple(weights.shape) == (h, w))
+    return (ptr(tmpl), int(tmpl.dtype == torch.float32), ptr(mask), h, w, ptr(weights), ptr(frame),
+            int(frame.dtype == torch.float32), frame.shape[0], frame.shape[1])
+
+
+def _photo_huber(huber_k):
+    return -1.0 if huber_k is None else float(huber_k)
+
+
+def photo_eval(tmpl, mask, weights, frame, box, stride, W, gain, bias, gain_bias, huber_k, out, ws=None):
+    """woft_photo_eval: the normal equations of the photometric refinement at one state -> out (PHOTO_NACC float64 on the device):
+    the upper triangle of G row-major, r, sum weight * rho, sum weight, n_valid.  W: 3x3 template -> frame pixels; bias in units
+    of the three-channel sum."""
+    ws = ws if ws is not None else photo_ws(box, stride, tmpl.device)
+    assert out.dtype == torch.float64 and out.numel() >= PHOTO_NACC and out.is_contiguous()
+    check(_lib.load().woft_photo_eval(*_photo_images(tmpl, mask, weights, frame), (C.c_int32 * 4)(*[int(v) for v in box]),
+                                      int(stride), (C.c_double * 9)(*np.asarray(W, dtype=np.float64).ravel().tolist()),
+                                      float(gain), float(bias), int(bool(gain_bias)), _photo_huber(huber_k), ptr(ws), ptr(out),
+                                      stream_ptr()), "woft_photo_eval")
+
+
+def photo_refine(tmpl, mask, weights, frame, box, stride, W0, iters, gain_bias, huber_k, n_need, eps, result, ws=None):
+    """woft_photo_refine: iters + 1 (accumulate, step) launch pairs from W0 -> result (PHOTO_REC * (iters + 2) float64 on the
+    device; layout in include/woft_hip.h)."""
+    ws = ws if ws is not None else photo_ws(box, stride, tmpl.device)
+    assert result.dtype == torch.float64 and result.numel() >= PHOTO_REC * (iters + 2) and result.is_contiguous()
+    check(_lib.load().woft_photo_refine(*_photo_images(tmpl, mask, weights, frame), (C.c_int32 * 4)(*[int(v) for v in box]),
+                                        int(stride), (C.c_double * 9)(*np.asarray(W0, dtype=np.float64).ravel().tolist()),
+                                        int(iters), int(bool(gain_bias)), _photo_huber(huber_k), int(n_need), float(eps), ptr(ws),
+                                        ptr(result), stream_ptr()), "woft_photo_refine")

@@ -31,6 +31,11 @@ frame t-1 -> t flow of the second and later frames of a run of lost frames start
 flow of the previous one (RAFT's video warm start, raft_core/utils/utils.py:28-56) instead of from zero; `warm_start_iters`
 sets the iteration count of those flows.  `meta.local_warm_started` says which kind a lost frame's flow was.
 
+Photometric refinement (this project's own, no counterpart in TRK): with the config key `photo_refine` = N
+the pose of every frame that is not lost is aligned to the frame's pixels by N Gauss-Newton iterations on the device
+(woft_amd.photo) after the correspondence fit and before it becomes the tracker's pose; `meta.H_flow_cur2init` keeps the fit's
+pose, `meta.photo` says what the refinement did.
+
 Frames live on the GPU (the two cv2.warpPerspective calls of TRK:89-95 are one HIP kernel) and the
 template's feature / context tensors are computed once (the flow provider pins the template).
 """
@@ -198,6 +203,54 @@ class YAOFTrackerSingleControl:
             raise ValueError(f"warm_start_iters {n!r}: not an integer >= 1")
         return on, (None if n is None else int(n))
 
+    def _photo_config(self):
+        """-> None (off: `photo_refine` absent, None or 0) or the options of the photometric refinement (woft_amd.photo; DESIGN.md
+        section 27): dict(iters, gain_bias, huber_k, min_valid, eps, stride, blur_sigma) from the config keys `photo_refine` (the
+        iteration count), `photo_gain_bias` (True), `photo_huber_k` (None), `photo_min_valid` (0.5), `photo_eps` (1e-3),
+        `photo_stride` (1), `photo_blur_sigma` (0)."""
+        C = self.C
+        iters = config_get(C, "photo_refine")
+        if iters is None or (not isinstance(iters, bool) and isinstance(iters, (int, np.integer)) and iters == 0):
+            return None
+        from . import photo
+        D = photo.DEFAULTS
+        iters, gain_bias, huber_k, min_valid, eps = photo.check_options(
+            iters, config_get(C, "photo_gain_bias", D["gain_bias"]), config_get(C, "photo_huber_k", D["huber_k"]),
+            config_get(C, "photo_min_valid", D["min_valid"]), config_get(C, "photo_eps", D["eps"]), prefix="photo_refine / photo_")
+        stride = config_get(C, "photo_stride", 1)
+        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+            raise ValueError(f"photo_stride {stride!r}: not an integer >= 1")
+        sigma = _float_key(C, "photo_blur_sigma", 0.0, lambda v: 0.0 <= v < float("inf"), "a finite float >= 0")
+        return dict(iters=iters, gain_bias=gain_bias, huber_k=huber_k, min_valid=min_valid, eps=eps, stride=int(stride),
+                    blur_sigma=sigma)
+
+    def _photo_image(self, img):
+        """The image the photometric stage reads: the uint8 device frame, or with `photo_blur_sigma` its blurred float32 version."""
+        img = _device_u8(img)
+        if not self._photo["blur_sigma"]:
+            return img
+        from . import hsynth
+        return hsynth.augment(img, blur_sigma=self._photo["blur_sigma"], want_f32=True)[1]
+
+    def _photo_stage(self, frame, H_cur2init, meta):
+        """Align the fitted pose to the pixels: W0 = inv(H_cur2init) (template -> frame) refined against the template and its mask;
+        -> inv(W), normalised as compose_H normalises.  meta.photo says what happened; a refinement without an eligible iterate
+        returns the pose it was given."""
+        P = self._photo
+        if not np.all(np.isfinite(H_cur2init)):                      # (nothing to start from: the pose stays what the fit gave)
+            meta.photo = None
+            return H_cur2init
+        W, info = self._photo_template.refine(self._photo_image(frame), np.linalg.inv(H_cur2init), iters=P["iters"],
+                                              gain_bias=P["gain_bias"], huber_k=P["huber_k"], min_valid=P["min_valid"], eps=P["eps"])
+        self.host_wait_s += info.host_wait_s
+        b = info.best
+        meta.photo = SimpleNamespace(status=info.status, best=b, iterates=len(info.cost), rms_before=info.rms_before,
+                                     rms_after=info.rms_after, n_valid=int(info.n_valid[b]) if b >= 0 else 0,
+                                     gain=float(info.gain[b]) if b >= 0 else 1.0, bias=float(info.bias[b]) if b >= 0 else 0.0)
+        if b < 0:
+            return H_cur2init
+        return compose_H(np.linalg.inv(W))
+
     # config keys this tracker class does not provide: (key, why), refused by __init__ when set
     REFUSED = ()
     REFUSED_BY = "tracker"
@@ -211,6 +264,8 @@ class YAOFTrackerSingleControl:
     def __init__(self, config):
         self._refusals(config)
         self.C = config
+        self._photo = self._photo_config()    # (read once: None = off, and the frame's code path is what it is without the key)
+        self._photo_template = None
         self.warm_start_local, self.warm_start_iters = self._warm_start_config()
         self.local_warm_started = False   # whether the last frame t-1 -> t flow started from a carried flow
         self._warm = None                 # (flow_low of the last frame t-1 -> t flow, its provider flow key): the carried flow
@@ -258,6 +313,13 @@ class YAOFTrackerSingleControl:
         if self.fb_check:
             self.solver_decision += (f"; forward-backward check {self.fb_check} (|f + b|^2 <= {self.fb_alpha:.9g} * (|f|^2 + |b|^2) "
                                      f"+ {self.fb_beta:.9g})")
+        if self._photo is not None:
+            P = self._photo
+            self.solver_decision += (f"; photometric refinement of re-detected frames ({P['iters']} iterations, "
+                                     + ("gain and bias" if P["gain_bias"] else "no gain / bias")
+                                     + (f", Huber {P['huber_k']:.9g}" if P["huber_k"] is not None else "")
+                                     + (f", stride {P['stride']}" if P["stride"] != 1 else "")
+                                     + (f", blur {P['blur_sigma']:.9g}" if P["blur_sigma"] else "") + ")")
         return spec
 
     def _fused_specs_plain(self):
@@ -339,6 +401,9 @@ class YAOFTrackerSingleControl:
             self._sparse_weights = bool(on and self._fused is not None and self._fused["n_draw"] and self._mask_weight_head()
                                         and hasattr(self.flower, "finish_weights") and self.visibility_mode is None
                                         and not self.fb_check)
+        if self._photo is not None:
+            from .photo import PhotoTemplate
+            self._photo_template = PhotoTemplate(self._photo_image(self.template_img), inside, stride=self._photo["stride"])
         self._set_pose(_EYE.copy(), good=True)
         self.prev_img, self.prev_img_identifier = img, img_identifier
         self.lost, self.N_lost = False, 0
@@ -402,6 +467,9 @@ class YAOFTrackerSingleControl:
                 meta.local_warm_started = self.local_warm_started    # (False without `warm_start_local`)
                 if self._vis_mode is not None:
                     meta.n_kept_local = self.n_kept                  # ... frame t-1 -> t flow (None: no flow ran)
+        if self._photo is not None and not self.lost:
+            meta.H_flow_cur2init = H_cur2init.copy()                 # (the correspondence fit's pose, un-refined)
+            H_cur2init = self._photo_stage(frame, H_cur2init, meta)
         if debug:
             logger.debug("debug visualisation (TRK:210-264) needs the OpenCV GUI and is not part of the HIP path")
 

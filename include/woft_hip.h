@@ -525,6 +525,19 @@ int woft_chain_tc_window(const float* flow, const float* cost, const float* vis,
 int woft_chain_tc_multi(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits,
                         int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t n_targets, float vis_thr, float* dst, float* w,
                         float* ok, int32_t* hist, void* stream);
+/* woft_chain_tc_multi on a template rectangle (csrc/flow_multi.hip).  DESIGN.md section 28.  What woft_chain_tc_window is to
+ * woft_chain_tc: the [gh][gw] planes are the rectangle with origin (tx0, ty0) of a frame_h x frame_w frame, tbits is the bit plane
+ * CROPPED to the rectangle (uint32 [mh][mw], gh <= mh, gw <= mw).  dst (window coordinates), w and hist[t]: the bytes
+ * woft_chain_tc_multi writes for the same planes and bit plane.  ok is additionally 0 where the landing in frame coordinates
+ * X = (float)(tx0 + x) + flow_x, Y = (float)(ty0 + y) + flow_y fails X < 0 or Y < 0 or rintf(X) >= frame_w or rintf(Y) >= frame_h:
+ * woft_chain_tc_window's expression, so dst, w, ok are its bytes and hist[t] its histogram for a uint8 mask equal to bit t.
+ * One kernel with woft_chain_tc_multi (two instantiations), the same geometry, ballots and LDS counters.
+ * -1 (before any launch) on everything woft_chain_tc_multi rejects, a negative origin, origin + side > 2^24, frame_h or frame_w <= 0
+ * or > 2^24. */
+int woft_chain_tc_multi_window(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits,
+                               int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t n_targets, int32_t ty0, int32_t tx0,
+                               int32_t frame_h, int32_t frame_w, float vis_thr, float* dst, float* w, float* ok, int32_t* hist,
+                               void* stream);
 
 /* Frame-features record (csrc/features.hip).  DESIGN.md section 20.  What the encoders produce for one image at one padded
  * geometry, P = (hp / 8) * (wp / 8) pixels, as one contiguous fp32 block: record = [P][fdim] fnet map | [P][hdim] net (after
@@ -721,6 +734,19 @@ int woft_crop_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, int32_t y0
 int64_t woft_mask_bbox_ws_bytes(void);
 int woft_mask_bbox(const uint8_t* mask, int32_t h, int32_t w, const double* hinv, uint8_t* warped, void* ws, int32_t* bbox,
                    void* stream);
+/* woft_mask_bbox with a homography for n_targets masks at once, ONE launch whatever n_targets is.  DESIGN.md section 28.  tbits: the
+ * bit plane of woft_chain_tc_multi, uint32 [h][w] (device), 1 <= n_targets <= WOFT_MULTI_MAX_TARGETS; hinv: n_targets x 9 doubles
+ * on the HOST, copied by value; bbox: int32 [n_targets][5] (device).  Row t is, integer for integer, what
+ * woft_mask_bbox(mask_t, h, w, hinv + 9 t, NULL, ...) writes for mask_t = (bit t of tbits): the same nearest-neighbour warp per
+ * frame pixel (csrc/warp_pixel.h), integer maxima; {0, 0, 0, 0, 0} where nothing of the carried mask is set.  Bit t of `skip` set:
+ * target t is not measured, its hinv is not read and its row is {0, 0, 0, 0, 0}.  Deterministic: two calls give equal bytes.
+ * ws: woft_mask_bbox_multi_ws_bytes(n_targets) bytes (-1 for an n_targets outside [1, 32]) of device scratch under woft_mask_bbox's
+ * contract: ZEROED ONCE by the caller, left zeroed by every call.
+ * -1 (before any launch) on a NULL tbits / hinv / ws / bbox, h or w <= 0, n_targets outside [1, 32], a non-finite entry of the hinv
+ * of a target that is not skipped. */
+int64_t woft_mask_bbox_multi_ws_bytes(int32_t n_targets);
+int woft_mask_bbox_multi(const uint32_t* tbits, int32_t h, int32_t w, int32_t n_targets, const double* hinv, uint32_t skip, void* ws,
+                         int32_t* bbox, void* stream);
 
 /* ---- Synthetic-homography training pairs (csrc/hsynth.hip) ------------------------------------------------
  * This project's own semantics for what the reference's training configs call COCOHSynth (an image, the same image through a known

@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("chain_fold_window", "WindowedMultiFlowTracker", "WOFTChainedWindow"):
         from . import chained_window
         return getattr(chained_window, name)
+    if name == "WOFTChainedMultiWindow":
+        from .chained_multi_window import WOFTChainedMultiWindow
+        return WOFTChainedMultiWindow
     if name in ("HSynth", "HSynthSample", "HSynthAugment", "render_pair", "pair_labels", "random_homography", "make_occluder",
                 "augment", "blur_taps", "colour_matrix"):
         from . import hsynth

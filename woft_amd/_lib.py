@@ -107,6 +107,7 @@ _SIGS = {
                                           i32, i32, vp, vp, vp, vp, vp]),
     "woft_chain_tc_window": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
     "woft_chain_tc_multi": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "woft_chain_tc_multi_window": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
     "woft_features_pack": (i32, [vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, vp, vp]),
     "woft_features_unpack": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp]),
     "woft_colsum":(i32, [vp, i64, i32, vp, i32, vp, vp]),
@@ -146,6 +147,8 @@ _SIGS = {
     "woft_crop_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "woft_mask_bbox_ws_bytes": (i64, []),
     "woft_mask_bbox": (i32, [vp, i32, i32, C.POINTER(C.c_double), vp, vp, vp, vp]),
+    "woft_mask_bbox_multi_ws_bytes": (i64, [i32]),
+    "woft_mask_bbox_multi": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), C.c_uint32, vp, vp, vp]),
     "woft_tc_select_ws_bytes": (i64, [i64]),
     "woft_tc_select": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]),
     "woft_tc_flags": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),

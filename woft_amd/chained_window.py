@@ -223,12 +223,13 @@ class WOFTChainedWindow(WOFTChained):
     REFUSED = tuple(r for r in WOFTChained.REFUSED if r[0] != "search_window_margin") + (
         ("chain_share_features", "the crops of one frame differ per flow: there is no one encoding of a frame to share"),
     )
+    PREWARP_DEFAULT = True                        # (chain_prewarp when the config does not name it)
 
     def __init__(self, config):
         self._margin = config_get(config, "search_window_margin", None) or None       # (absent key: an empty, falsy Config)
         self.chain_window_quantum = window.check_quantum(config_get(config, "chain_window_quantum", 64))
         self.chain_window_min = config_get(config, "chain_window_min", window.MIN_WINDOW)
-        self.chain_prewarp = bool(config_get(config, "chain_prewarp", True))
+        self.chain_prewarp = bool(config_get(config, "chain_prewarp", self.PREWARP_DEFAULT))
         super().__init__(config)
         self.solver_decision += (f"; chained flows on search windows (margin {self._margin}, quantum {self.chain_window_quantum}, "
                                  f"pre-warped direct flow {'on' if self.chain_prewarp else 'off'})")
@@ -266,10 +267,11 @@ class WOFTChainedWindow(WOFTChained):
 
     def _planar_stage(self, state, out, input_img, img_identifier):
         """WOFTChained's stage in R0's coordinates: woft_chain_tc_window's gate holds the in-frame rule, so the selection checks
-        no bounds; the fit is un-cropped where R0 does not start at the frame's origin."""
+        no bounds; the fit is un-cropped where R0 does not start at the frame's origin.  `state` also holds _mask_crop: the
+        tracker, or a target of WOFTChainedMultiWindow."""
         Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
         y0, x0, gh, gw = out.rect
-        mask, mask_hw = self._mask_crop, tuple(int(v) for v in self._mask_crop.shape)
+        mask, mask_hw = state._mask_crop, tuple(int(v) for v in state._mask_crop.shape)
         dst, w, ok, hist = self._tc.put((gh, gw), ops.chain_tc_window(out.flow, out.cost, out.vis, out.sel, mask, self.chain_vis_thr,
                                                                       (y0, x0), (Hh, Ww), want_w=self._wants_weights(),
                                                                       mask_hw=mask_hw, out=self._tc.get((gh, gw))))

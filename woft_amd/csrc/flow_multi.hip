@@ -3,7 +3,8 @@
 // DESIGN.md section 18.  One streaming kernel with a local gather, one template pixel per lane: no LDS, no atomics, no workspace.
 // Below it, the step from a fold result to the planar fit's correspondences (woft_chain_tc): streaming, no
 // gather, the 130 integer counters of its histogram in LDS.
-// Both have a form on rectangles (woft_flow_chain_fold_window, woft_chain_tc_window): flows on search windows.
+// Both have a form on rectangles (woft_flow_chain_fold_window, woft_chain_tc_window): flows on search windows;
+// so has the multi-target form of the second (woft_chain_tc_multi_window).
 //
 // The sampler, its address rule and the launch geometry are those of flow_chain.hip (flow_sample.h): every tap address derives
 // from a clamped float, so no input, finite or not, addresses outside a plane; the pixel's own planes are read at (x, y) of the
@@ -203,12 +204,16 @@ __global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict_
 // the pixel's counter is the same for every target, its mask bits say which targets count it.  Per distinct counter of the wave,
 // one ballot per target gives that target's number of lanes; lane t keeps target t's, so the wave ends in ONE LDS atomic
 // instruction per distinct counter (lanes 0 .. n_targets-1, one counter each).  LDS: n_targets * 130 counters, 16 640 B at 32.
+// WINDOW (woft_chain_tc_multi_window): chain_tc_kernel<true>'s gate on ok, in its own expression; the planes
+// are the rectangle with origin (tx0, ty0) and tbits is the cropped bit plane.  The counter of a pixel is chosen by `seen`, not by
+// the gate, so the ballots and the LDS atomics below see the same lanes and values in both instantiations.
+template <bool WINDOW>
 __global__ __launch_bounds__(FC_T) void chain_tc_multi_kernel(const float* __restrict__ flow, const float* __restrict__ cost,
                                                               const float* __restrict__ vis, const int32_t* __restrict__ sel,
                                                               const uint32_t* __restrict__ tbits, int gh, int gw, int mw,
-                                                              int n_targets, float vis_thr, float* __restrict__ dst,
-                                                              float* __restrict__ w, float* __restrict__ ok,
-                                                              int32_t* __restrict__ hist) {
+                                                              int n_targets, int ty0, int tx0, float frame_h, float frame_w,
+                                                              float vis_thr, float* __restrict__ dst, float* __restrict__ w,
+                                                              float* __restrict__ ok, int32_t* __restrict__ hist) {
     __shared__ int32_t bins[WOFT_MULTI_MAX_TARGETS * WOFT_CHAIN_HIST];
     const int tid = (int)threadIdx.y * FC_TX + (int)threadIdx.x;
     const int n_bins = n_targets * WOFT_CHAIN_HIST;
@@ -230,7 +235,12 @@ __global__ __launch_bounds__(FC_T) void chain_tc_multi_kernel(const float* __res
             dst[i] = valid ? (float)x + fx : NAN;
             dst[plane + i] = valid ? (float)y + fy : NAN;
             if (w != nullptr) w[i] = valid ? expf(-c) : 0.f;
-            ok[i] = seen ? 1.f : 0.f;
+            bool gate = seen;
+            if constexpr (WINDOW) {
+                const float X = (float)(tx0 + x) + fx, Y = (float)(ty0 + y) + fy;
+                gate = seen && !(X < 0.f || Y < 0.f || rintf(X) >= frame_w || rintf(Y) >= frame_h);
+            }
+            ok[i] = gate ? 1.f : 0.f;
             bits = tbits[(int64_t)y * mw + x] & live;
             if (bits != 0) bin = !valid ? WOFT_CHAIN_HIST - 2 : (seen ? s : WOFT_CHAIN_HIST - 1);
         }
@@ -343,10 +353,15 @@ extern "C" int woft_chain_tc_window(const float* flow, const float* cost, const 
                                  stream);
 }
 
-extern "C" int woft_chain_tc_multi(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits,
-                                   int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t n_targets, float vis_thr, float* dst,
-                                   float* w, float* ok, int32_t* hist, void* stream) {
+namespace {
+
+// the checks and the launch of woft_chain_tc_multi and woft_chain_tc_multi_window (WINDOW: the rectangle's origin and the frame's size)
+template <bool WINDOW>
+int chain_tc_multi_launch(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits, int32_t gh,
+                          int32_t gw, int32_t mh, int32_t mw, int32_t n_targets, int32_t ty0, int32_t tx0, int32_t frame_h,
+                          int32_t frame_w, float vis_thr, float* dst, float* w, float* ok, int32_t* hist, void* stream) {
     if (!flow || !cost || !vis || !sel || !tbits || !dst || !ok || !hist || bad_side(gh, gw)) return WOFT_EINVAL;
+    if (WINDOW && (bad_span(ty0, gh) || bad_span(tx0, gw) || bad_side(frame_h, frame_w))) return WOFT_EINVAL;
     if (mh < gh || mw < gw || n_targets < 1 || n_targets > WOFT_MULTI_MAX_TARGETS) return WOFT_EINVAL;
     if (!(vis_thr >= 0.f && vis_thr <= 1.f)) return WOFT_EINVAL;                                                  // (NaN fails)
     // as woft_chain_tc: an output may share no byte with an input or with another output (overlap() lets a NULL through)
@@ -367,9 +382,26 @@ extern "C" int woft_chain_tc_multi(const float* flow, const float* cost, const f
     dim3 grid = pixel_grid(gh, gw);
     const unsigned rows = CHAIN_TC_BLOCKS / grid.x;
     grid.y = grid.y < rows ? grid.y : (rows > 0 ? rows : 1u);
-    hipLaunchKernelGGL(chain_tc_multi_kernel, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tbits, gh, gw,
-                       mw, n_targets, vis_thr, dst, w, ok, hist);
+    hipLaunchKernelGGL(chain_tc_multi_kernel<WINDOW>, grid, dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, flow, cost, vis, sel, tbits, gh,
+                       gw, mw, n_targets, ty0, tx0, (float)frame_h, (float)frame_w, vis_thr, dst, w, ok, hist);
     return woft_launch_status();
+}
+
+}  // namespace
+
+extern "C" int woft_chain_tc_multi(const float* flow, const float* cost, const float* vis, const int32_t* sel, const uint32_t* tbits,
+                                   int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t n_targets, float vis_thr, float* dst,
+                                   float* w, float* ok, int32_t* hist, void* stream) {
+    return chain_tc_multi_launch<false>(flow, cost, vis, sel, tbits, gh, gw, mh, mw, n_targets, 0, 0, 0, 0, vis_thr, dst, w, ok, hist,
+                                        stream);
+}
+
+extern "C" int woft_chain_tc_multi_window(const float* flow, const float* cost, const float* vis, const int32_t* sel,
+                                          const uint32_t* tbits, int32_t gh, int32_t gw, int32_t mh, int32_t mw, int32_t n_targets,
+                                          int32_t ty0, int32_t tx0, int32_t frame_h, int32_t frame_w, float vis_thr, float* dst,
+                                          float* w, float* ok, int32_t* hist, void* stream) {
+    return chain_tc_multi_launch<true>(flow, cost, vis, sel, tbits, gh, gw, mh, mw, n_targets, ty0, tx0, frame_h, frame_w, vis_thr, dst,
+                                       w, ok, hist, stream);
 }
 
 extern "C" int woft_flow_chain_fold_window(const float* prev_flow, const float* prev_cost, const float* prev_vis, int32_t th, int32_t tw,

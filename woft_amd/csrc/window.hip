@@ -6,6 +6,7 @@
 //     previous frame by a nearest-neighbour warp, produced and measured in one launch.
 // Bandwidth-trivial: what counts is launches and bytes touched.
 #include <limits.h>
+#include <cmath>
 #include "common.h"
 #include "warp_pixel.h"
 
@@ -120,6 +121,64 @@ __global__ __launch_bounds__(256) void warp_mask_bbox_kernel(const uint8_t* __re
     bbox_finish(e, h, w, ws, bbox);
 }
 
+// ---- the boxes of K carried masks (woft_mask_bbox_multi) ----------------------------------------------------
+// The K inverse homographies travel by value in the kernel's arguments (2 304 B at 32 targets), as the occluders of hsynth.hip do.
+struct H9Set {
+    H9 h[WOFT_MULTI_MAX_TARGETS];
+};
+
+// ws: e[t][0..3] of every target, then the ticket and 3 spare ints
+inline int64_t bbox_multi_ws_ints(int n_targets) { return 4 * (int64_t)n_targets + 4; }
+
+// warp_mask_bbox_kernel for n_targets masks held as one bit plane: the same pixel loop, the same warp_nearest_index and the same
+// codes, once per target that is not skipped (t is block-uniform: every lane reaches the shuffles).  One ticket for all targets;
+// the workgroup that draws the last one decodes every row -- a skipped target's scratch was never touched: {0, 0, 0, 0, 0}.
+__global__ __launch_bounds__(256) void mask_bbox_multi_kernel(const uint32_t* __restrict__ tbits, int h, int w, int n_targets,
+                                                              uint32_t skip, H9Set hs, int* __restrict__ ws,
+                                                              int32_t* __restrict__ bbox) {
+    const int64_t n = (int64_t)h * w;
+    int* const ticket = ws + 4 * n_targets;
+    for (int t = 0; t < n_targets; ++t) {
+        if ((skip >> t) & 1u) continue;
+        const H9 hi = hs.h[t];
+        int e[4] = {0, 0, 0, 0};
+        for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+            const int y = (int)(p / w), x = (int)(p - (int64_t)y * w);
+            const int64_t s = warp_nearest_index(h, w, hi, x, y);
+            if (s >= 0 && ((tbits[s] >> t) & 1u)) bbox_fold(e, h, w, y, x);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) e[q] = max(e[q], __shfl_xor(e[q], off, 64));
+        }
+        if ((threadIdx.x & 63) == 0 && e[1] > 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) atomicMax(&ws[4 * t + q], e[q]);
+        }
+    }
+    __threadfence();
+    __syncthreads();
+    __shared__ int last;
+    if (threadIdx.x == 0) last = (unsigned)atomicAdd(ticket, 1) == gridDim.x - 1;
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    const int t = (int)threadIdx.x;
+    if (t < n_targets) {
+        int r[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r[q] = atomicExch(&ws[4 * t + q], 0);   // (read at the L2, where the atomics landed; and reset)
+        const bool any = r[1] > 0;
+        bbox[5 * t + 0] = any ? h - r[0] : 0;
+        bbox[5 * t + 1] = any ? r[1] - 1 : 0;
+        bbox[5 * t + 2] = any ? w - r[2] : 0;
+        bbox[5 * t + 3] = any ? r[3] - 1 : 0;
+        bbox[5 * t + 4] = any ? 1 : 0;
+    }
+    if (t == 0) atomicExch(ticket, 0);
+}
+
 bool rect_ok(int32_t h, int32_t w, int32_t y0, int32_t x0, int32_t hw, int32_t ww) {
     return h > 0 && w > 0 && hw > 0 && ww > 0 && y0 >= 0 && x0 >= 0 && (int64_t)y0 + hw <= h && (int64_t)x0 + ww <= w;
 }
@@ -166,5 +225,28 @@ extern "C" int woft_mask_bbox(const uint8_t* mask, int32_t h, int32_t w, const d
         hipLaunchKernelGGL(mask_bbox_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0,
                            (hipStream_t)stream, mask, h, w, (int*)ws, bbox);
     }
+    return woft_launch_status();
+}
+
+extern "C" int64_t woft_mask_bbox_multi_ws_bytes(int32_t n_targets) {
+    if (n_targets < 1 || n_targets > WOFT_MULTI_MAX_TARGETS) return -1;
+    return bbox_multi_ws_ints(n_targets) * (int64_t)sizeof(int);
+}
+
+extern "C" int woft_mask_bbox_multi(const uint32_t* tbits, int32_t h, int32_t w, int32_t n_targets, const double* hinv, uint32_t skip,
+                                    void* ws, int32_t* bbox, void* stream) {
+    if (!tbits || !hinv || !ws || !bbox || h <= 0 || w <= 0 || n_targets < 1 || n_targets > WOFT_MULTI_MAX_TARGETS) return WOFT_EINVAL;
+    H9Set hs = {};
+    for (int t = 0; t < n_targets; ++t) {
+        if ((skip >> t) & 1u) continue;
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(hinv[9 * t + i])) return WOFT_EINVAL;
+            hs.h[t].v[i] = hinv[9 * t + i];
+        }
+    }
+    // the grid of woft_mask_bbox's warp form; every block walks the targets in turn
+    const int64_t blocks = ceil_div64((int64_t)h * w, 256);
+    hipLaunchKernelGGL(mask_bbox_multi_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream,
+                       tbits, h, w, n_targets, skip, hs, (int*)ws, bbox);
     return woft_launch_status();
 }

@@ -869,12 +869,12 @@ def _check_tbits(tbits, mh, mw, n_targets):
     assert tbits.dtype == torch.int32 and tbits.is_contiguous() and tbits.is_cuda and tbits.numel() == mh * mw
 
 
-def chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=True, mask_hw=None, out=None):
+def chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=True, mask_hw=None, out=None, _window=None):
     """chain_tc for n_targets template masks at once (woft_chain_tc_multi) -> (dst (2, n), w (1, n) | None,
     ok (1, n), hist (n_targets, 130) int32).  tbits: the masks as one bit plane, an int32 device tensor of mask_hw = (mh, mw) >=
     (H, W) elements (default the grid's size), bit t set where the pixel lies in target t's mask.  dst, w, ok: chain_tc's bytes;
     hist[t]: chain_tc's for a uint8 mask equal to bit t.  out: the tuple of an earlier call at this size, reused (its hist may
-    be a view into a larger result block)."""
+    be a view into a larger result block).  (_window: chain_tc_multi_window's (y0, x0, frame_h, frame_w), below.)"""
     assert flow.dim() == 3 and flow.shape[0] == 2 and _f32c(flow)
     h, w = flow.shape[1:]
     n = h * w
@@ -894,9 +894,23 @@ def chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=True,
         wout = None
     assert _f32c(dst, 2, n) and _f32c(ok, 1, n) and (wout is None or _f32c(wout, 1, n))
     assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda and hist.numel() == n_targets * CHAIN_HIST
+    if _window is not None:
+        check(_lib.load().woft_chain_tc_multi_window(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tbits), h, w, mh, mw, int(n_targets),
+                                                     *_window, vis_thr, ptr(dst), ptr(wout), ptr(ok), ptr(hist), stream_ptr()),
+              "woft_chain_tc_multi_window")
+        return dst, wout, ok, hist
     check(_lib.load().woft_chain_tc_multi(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tbits), h, w, mh, mw, int(n_targets), vis_thr,
                                           ptr(dst), ptr(wout), ptr(ok), ptr(hist), stream_ptr()), "woft_chain_tc_multi")
     return dst, wout, ok, hist
+
+
+def chain_tc_multi_window(flow, cost, vis, sel, tbits, n_targets, vis_thr, origin, frame_hw, want_w=True, mask_hw=None, out=None):
+    """chain_tc_multi on a template rectangle (woft_chain_tc_multi_window): the planes are those of the
+    rectangle with origin = (y0, x0) in a frame of frame_hw = (frame_h, frame_w); tbits is the bit plane CROPPED to the rectangle
+    (mask_hw >= (H, W), default the grid's size).  dst (window coordinates), w and hist are chain_tc_multi's bytes; ok is
+    additionally 0 where the landing leaves the frame: dst, w, ok are chain_tc_window's bytes, hist[t] its histogram for bit t."""
+    return chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=want_w, mask_hw=mask_hw, out=out,
+                          _window=(int(origin[0]), int(origin[1]), int(frame_hw[0]), int(frame_hw[1])))
 
 
 def coords_update(coords, delta, ld_delta, wf, flow4=None, flow_cat=None, ld_cat=0):
@@ -1213,6 +1227,43 @@ def mask_bbox(mask, bbox=None, Hmat=None, warped=None, ws=None):
     ws = ws if ws is not None else mask_bbox_ws(mask.device)
     check(_lib.load().woft_mask_bbox(ptr(mask), h, w, None if Hmat is None else _hinv9(Hmat), ptr(warped), ptr(ws), ptr(bbox),
                                      stream_ptr()), "woft_mask_bbox")
+    return bbox
+
+
+def mask_bbox_multi_ws(n_targets, device=None):
+    """Scratch of woft_mask_bbox_multi for n_targets, zeroed once (every call leaves it zeroed); one per device, stream and count."""
+    dev = torch.device(device or DEV)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr(), int(n_targets))
+    if key not in _BBOX_WS:
+        need = int(_lib.load().woft_mask_bbox_multi_ws_bytes(int(n_targets)))
+        if need < 0:
+            raise _lib.WoftHipError(f"woft_mask_bbox_multi_ws_bytes({n_targets}) rejected its argument")
+        _BBOX_WS[key] = torch.zeros(need, dtype=torch.uint8, device=dev)
+    return _BBOX_WS[key]
+
+
+def mask_bbox_multi(tbits, n_targets, Hmats, bbox=None, ws=None):
+    """mask_bbox(mask_t, Hmat=Hmats[t]) for the n_targets masks of a bit plane in ONE launch (woft_mask_bbox_multi; DESIGN.md
+    section 28) -> bbox (n_targets, 5) int32 on the device, row t = {rmin, rmax, cmin, cmax, any} of mask t carried by Hmats[t]
+    (3 x 3, mask -> frame; inverted in fp64 on the host, as mask_bbox does).  Hmats[t] None: target t is skipped, its row is zeros.
+    tbits: the (H, W) int32 bit plane of chain_tc_multi."""
+    assert tbits.dim() == 2
+    h, w = tbits.shape
+    _check_tbits(tbits, h, w, n_targets)
+    if len(Hmats) != n_targets:
+        raise ValueError(f"mask_bbox_multi: {n_targets} targets, {len(Hmats)} homographies")
+    hinv, skip = (C.c_double * (9 * n_targets))(), 0
+    for t, Hm in enumerate(Hmats):
+        if Hm is None:
+            skip |= 1 << t
+        else:
+            hinv[9 * t:9 * t + 9] = np.linalg.inv(np.asarray(Hm, dtype=np.float64)).ravel().tolist()
+    if bbox is None:
+        bbox = torch.empty(n_targets, 5, dtype=torch.int32, device=tbits.device)
+    assert bbox.dtype == torch.int32 and bbox.is_contiguous() and bbox.numel() == 5 * n_targets
+    ws = ws if ws is not None else mask_bbox_multi_ws(n_targets, tbits.device)
+    check(_lib.load().woft_mask_bbox_multi(ptr(tbits), h, w, int(n_targets), hinv, skip, ptr(ws), ptr(bbox), stream_ptr()),
+          "woft_mask_bbox_multi")
     return bbox
 
 

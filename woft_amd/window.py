@@ -93,6 +93,15 @@ class Box:
         return img[y0:y0 + rows, x0:x0 + cols, ...]
 
 
+def union_box(boxes):
+    """The smallest Box that contains every Box of `boxes` (an iterable; None entries contribute nothing); None when nothing
+    contributes.  The one window of the multi-target windowed tracker (woft_amd.chained_multi_window) is chain_rect of this."""
+    boxes = [b for b in boxes if b is not None]
+    if not boxes:
+        return None
+    return Box.from_xyxy(min(b.tl_x for b in boxes), min(b.tl_y for b in boxes), max(b.br_x for b in boxes), max(b.br_y for b in boxes))
+
+
 def search_box(mask_box, margin, width, height, min_size=MIN_WINDOW, clip=True):
     """The window around `mask_box` in a width x height frame (WOFT_window.py:37-44, 215-221): margins, cut to the frame,
     grown to the minimum size.  A falsy margin: the whole frame.

@@ -852,7 +852,8 @@ enum woft_photo_status {
     WOFT_PHOTO_MAX_ITERS_REACHED = 1,
     WOFT_PHOTO_TOO_FEW = 2,
     WOFT_PHOTO_SINGULAR = 3,
-    WOFT_PHOTO_NONFINITE = 4
+    WOFT_PHOTO_NONFINITE = 4,
+    WOFT_PHOTO_SKIPPED = 5          /* (multi-target forms only: the target was not active) */
 };
 int64_t woft_photo_ws_bytes(int32_t box_w, int32_t box_h, int32_t stride);
 int woft_photo_eval(const void* tmpl, int32_t tmpl_f32, const uint8_t* mask, int32_t h, int32_t w, const float* weights,
@@ -863,6 +864,34 @@ int woft_photo_refine(const void* tmpl, int32_t tmpl_f32, const uint8_t* mask, i
                       const void* frame, int32_t frame_f32, int32_t hf, int32_t wf, const int32_t* box, int32_t stride,
                       const double* W0, int32_t iters, int32_t gain_bias, double huber_k, int32_t n_need, double eps, void* ws,
                       double* result, void* stream);
+
+/* The photometric refinement of K targets (1 .. WOFT_MULTI_MAX_TARGETS) of ONE template against ONE frame.
+ * Per target the semantics, and the bytes written, are those of woft_photo_eval / woft_photo_refine on that target's mask.
+ * bits: the (h, w) uint32 plane of pack_target_bits / woft_chain_tc_multi, bit t of a pixel set where it is in target t (masks may
+ * overlap; the words are unsigned, target 31 is the top bit).  weights, stride, iters, gain_bias, huber_k, eps are shared.  HOST
+ * arrays: boxes (K, 4) int32 {x0, y0, x1, y1} inclusive, W / W0 (K, 9), gains, biases (K; in units of S), n_need (K), active (K)
+ * int32.  A target with active == 0 takes no part: its workgroups return on a uniform branch, its row of `out` is not written and
+ * its result block is {WOFT_PHOTO_SKIPPED, -1, 0} with nothing else written; its box, W and n_need are still checked.  When no
+ * target is active there is no launch and nothing is written.
+ * woft_photo_eval_multi: the accumulate launch on the grid (P_max, K) -- P_t = ceil(nx_t ny_t / WOFT_PHOTO_CHUNK) partials of target
+ *   t, P_max the largest over all K boxes; workgroup (p, t) with p >= P_t returns at once -- then one workgroup per target sums its
+ *   partials in index order -> out (device, K rows of WOFT_PHOTO_NACC doubles, the first nu (nu + 1) / 2 + nu + 3 of a row written).
+ * woft_photo_refine_multi: iters + 1 (accumulate on (P_max, K), step on K) launch pairs whatever K; every target carries its own
+ *   state, stop, best and last iterate in its slice of the workspace and stops on its own.  result (device): K blocks of
+ *   WOFT_PHOTO_REC * (iters + 2) doubles, each laid out as woft_photo_refine's.
+ * ws: woft_photo_multi_ws_bytes(K, P_max) = K (P_max * WOFT_PHOTO_NACC + 18) * 8 bytes (-1 on a non-positive argument).  No atomics:
+ * two calls give equal bytes.  WOFT_EINVAL before any launch on everything the single forms reject, K outside 1 ..
+ * WOFT_MULTI_MAX_TARGETS, a NULL bits / boxes / W / gains / biases / n_need / active, any box outside the template or empty, any
+ * non-finite W / gain / bias entry, any n_need < 0. */
+int64_t woft_photo_multi_ws_bytes(int32_t n_targets, int32_t p_max);
+int woft_photo_eval_multi(const void* tmpl, int32_t tmpl_f32, const uint32_t* bits, int32_t h, int32_t w, const float* weights,
+                          const void* frame, int32_t frame_f32, int32_t hf, int32_t wf, int32_t n_targets, const int32_t* boxes,
+                          int32_t stride, const double* W, const double* gains, const double* biases, const int32_t* active,
+                          int32_t gain_bias, double huber_k, void* ws, double* out, void* stream);
+int woft_photo_refine_multi(const void* tmpl, int32_t tmpl_f32, const uint32_t* bits, int32_t h, int32_t w, const float* weights,
+                            const void* frame, int32_t frame_f32, int32_t hf, int32_t wf, int32_t n_targets, const int32_t* boxes,
+                            int32_t stride, const double* W0, const int32_t* n_need, const int32_t* active, int32_t iters,
+                            int32_t gain_bias, double huber_k, double eps, void* ws, double* result, void* stream);
 
 /* cv2.resize(img, None, fx, fy) with INTER_LINEAR geometry (tracker/YAOF_tracker_single_control.py:27-30,60-61,
  * `downscale_inputs`): src = (dst + 0.5) * scale - 0.5, edge clamped; scale = 1 / fx. */

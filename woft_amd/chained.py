@@ -95,6 +95,13 @@ class WOFTChained(YAOFTrackerSingleControl):
     'weighted' on the reliability logit, 'weighted_masked' also on the visibility logit -- without a `visibility_mode`: the fold
     consumes the mask.  `pw_mask`, `no_prewarp_after_N`, `no_local_H` and `do_not_mask_TCs_by_prewarped` are not used.
 
+    chain_photo_refine = N (absent, None or 0: off) runs the photometric refinement (woft_amd.photo; DESIGN.md sections 27, 29) on
+    the pose of every frame that is not lost: W0 = inv(H_cur2init) against the template frame and the template mask on the whole
+    current frame, N iterations at most; the pose becomes compose_H(inv(W)), meta.H_flow_cur2init keeps the fit's pose and
+    meta.photo says what the refinement did (a lost frame has neither).  Its options: chain_photo_gain_bias, chain_photo_huber_k,
+    chain_photo_stride, chain_photo_min_valid, chain_photo_eps, chain_photo_blur_sigma -- the parent's photo_* keys by meaning,
+    default and error.
+
     A frame is lost when the fit is rejected (its H is still returned, the parent's `no_local_H` behaviour) or when fewer than
     4 correspondences survive or H is not finite (the previous pose is returned).  meta: lost, N_lost, global_H_success,
     H_global_cur2init (None when there was no usable fit), n_kept, chain_hist (int64 numpy, visible mask pixels per delta),
@@ -110,7 +117,8 @@ class WOFTChained(YAOFTrackerSingleControl):
         ("search_window_margin", "the chains read every pixel of every flow; the search-window tracker is WOFTWindow"),
         ("post_hoc_weights_postprocessing_fn", "the fit weight is exp(-chain cost), not a weight map to post-process"),
         ("photo_refine", "the chained trackers' pose has no per-frame template-to-frame stage to refine from (no pre-warp: the "
-                         "chains carry the motion); the photometric refinement runs in YAOFTrackerSingleControl and WOFTWindow"),
+                         "chains carry the motion); the photometric refinement runs in YAOFTrackerSingleControl and WOFTWindow -- the chained "
+                         "trackers refine their fitted pose under their own key, chain_photo_refine"),
     )
 
     def _refusals(self, config):
@@ -132,9 +140,13 @@ class WOFTChained(YAOFTrackerSingleControl):
                                       f"borrow=True)); {type(self.flower).__name__} has no pin_source")
         self.multi = self._new_multi()            # (validates the chain keys)
         self.chain_deltas = self.multi.deltas
+        self._photo = self._photo_config("chain_")    # (read once: None = off, and the frame's code path is what it is without it)
+        self._photo_frame_of = (None, None)       # (frame number, the image the refinement reads of it)
         self.solver_decision += (f"; chained deltas {self.chain_deltas}; chain_share_features "
                                  f"{'on: every frame encoded once' if self.chain_share_features else 'off'}; pw_mask, no_prewarp_after_N, no_local_H and "
                                  "do_not_mask_TCs_by_prewarped are not used")
+        if self._photo is not None:
+            self.solver_decision += self._photo_decision("fitted")
         if self._fused is not None and not self.chain_weights:
             self._fused = dict(self._fused, weighted=False)
         # the solver's visibility slot carries the chains' 0 / 1 occlusion gate, the way fb_check hands its verdict
@@ -156,6 +168,7 @@ class WOFTChained(YAOFTrackerSingleControl):
         super().init(img, mask, img_identifier)                      # (single-contour check, mask tensors, state: the parent's)
         self.multi = self._new_multi()
         self._init_multi(img)
+        self._photo_frame_of = (None, None)
         # the chains read every pixel of every flow: no weight region, no flow region, no deferred weights
         if hasattr(self.flower, "pin_weight_region"):
             self.flower.pin_weight_region(None)
@@ -201,19 +214,51 @@ class WOFTChained(YAOFTrackerSingleControl):
         state.n_kept = self.n_kept
         return self._finish(state, fit, hist.cpu().numpy().astype(np.int64), input_img, img_identifier)
 
-    def _finish(self, state, fit, counts, input_img, img_identifier):
+    @staticmethod
+    def _verdict(fit, n_kept):
+        """-> (usable, success) of a frame's fit (None: there was none) with `n_kept` surviving correspondences."""
+        usable = (fit is not None and not (n_kept is not None and n_kept < 4) and bool(np.all(np.isfinite(fit.H))))
+        return usable, bool(usable and fit.success)
+
+    @staticmethod
+    def _photo_start(H_cur2init):
+        """The refinement's start inv(H_cur2init), template -> frame; None where the pose has no finite inverse."""
+        try:
+            W0 = np.linalg.inv(H_cur2init)
+        except np.linalg.LinAlgError:
+            return None
+        return W0 if np.all(np.isfinite(W0)) else None
+
+    def _photo_frame(self, input_img):
+        """The image the refinement reads of the frame being tracked, made once per frame whatever the number of targets."""
+        if self._photo_frame_of[0] != self._n_tracked:
+            self._photo_frame_of = (self._n_tracked, self._photo_image(input_img))
+        return self._photo_frame_of[1]
+
+    def _finish(self, state, fit, counts, input_img, img_identifier, photo=None):
         """A frame's fit (None: there was none), the target's `n_kept` and its histogram (int64 numpy) -> the update of `state`,
-        (H_cur2init, meta)."""
+        (H_cur2init, meta).  photo: with chain_photo_refine, what a batched refinement returned for this target, (W, info) --
+        (None, None) where it had no start; None: the refinement of `state`'s own template runs here."""
         meta = SimpleNamespace()
         n_kept = state.n_kept
-        usable = (fit is not None and not (n_kept is not None and n_kept < 4) and bool(np.all(np.isfinite(fit.H))))
+        usable, success = self._verdict(fit, n_kept)
         meta.n_kept = n_kept
         meta.H_global_cur2init = fit.H.copy() if usable else None
-        success = bool(usable and fit.success)
         logger.debug(f"global_H_success: {success}")
         state.lost, state.N_lost = not success, (0 if success else state.N_lost + 1)
         # the fit maps current -> template; a rejected fit is still returned, no usable fit keeps the previous pose
         H_cur2init = fit.H if usable else state.prev_H2init
+        if self._photo is not None and not state.lost:
+            meta.H_flow_cur2init = H_cur2init.copy()                 # (the correspondence fit's pose, un-refined)
+            if photo is None:
+                W0 = self._photo_start(H_cur2init)
+                photo = (None, None)
+                if W0 is not None:
+                    photo = state._photo_template.refine(self._photo_frame(input_img), W0, **self._photo_options())
+                    self.host_wait_s += photo[1].host_wait_s
+            meta.photo = None                                        # (no start: the pose stays what the fit gave)
+            if photo[1] is not None:
+                H_cur2init = self._photo_result(H_cur2init, photo[0], photo[1], meta)
         self.prev_img, self.prev_img_identifier = input_img, img_identifier
         self._set_pose(H_cur2init.copy(), good=not state.lost, state=state)
         meta.lost, meta.N_lost, meta.global_H_success = state.lost, state.N_lost, success
@@ -251,7 +296,9 @@ class WOFTChainedMulti(WOFTChained):
     the same frames, bit for bit.  Each target has its own lost / N_lost / previous pose / last good pose: a target with fewer
     than 4 surviving correspondences or a non-finite fit keeps its previous pose and is lost, the others are not affected, and no
     exception of a target's fit leaves track().  Config keys and refusals are WOFTChained's.  Not provided: adding or removing a
-    target after init(), autograd.
+    target after init(), autograd.  With chain_photo_refine the batched and select routes refine every target that is not lost in
+    one PhotoTemplateMulti.refine call after the planar block's read (one call and one read more per frame, whatever K); the
+    loop route refines per target with PhotoTemplate.
 
     The planar stage, by back end (`solver_decision` names the one in use; `meta.solver_decision` stays WOFTChained's text):
       device solver, Sobol draw, least-squares / IRLS estimator (the presets): chain_tc_multi, tc_select_multi, hfit_batched,
@@ -315,6 +362,35 @@ class WOFTChainedMulti(WOFTChained):
                                          _template_mask_u8=torch.from_numpy((m > 0).astype(np.uint8) * 255).to(self.device))
                          for t, m in enumerate(masks)]
         self._tbits = torch.from_numpy(pack_target_bits(masks).view(np.int32)).to(self.device)
+        if self._photo is not None:
+            from .photo import PhotoTemplate, PhotoTemplateMulti
+            image, self._photo_template, self._photo_multi = self._photo_image(self.template_img), None, None
+            if self._route == "loop":
+                for T, m in zip(self._targets, masks):
+                    T._photo_template = PhotoTemplate(image, m > 0, stride=self._photo["stride"])
+            else:
+                self._photo_multi = PhotoTemplateMulti(image, [m > 0 for m in masks], stride=self._photo["stride"])
+
+    def _finish_batched(self, rows, input_img, img_identifier):
+        """_finish for every target of a batched planar stage's rows; with chain_photo_refine the targets that are not lost go
+        through ONE PhotoTemplateMulti.refine call (one launch sequence and one read whatever K) first."""
+        photos = [None] * len(rows)
+        if self._photo is not None:
+            starts = [self._photo_start(fit.H) if self._verdict(fit, kept)[1] else None for fit, _, kept, _ in rows]
+            active = [W0 is not None for W0 in starts]
+            photos = [(None, None)] * len(rows)
+            if any(active):
+                Ws, infos = self._photo_multi.refine(self._photo_frame(input_img),
+                                                     np.stack([W0 if W0 is not None else np.eye(3) for W0 in starts]),
+                                                     active=active, **self._photo_options())
+                waits = [i.host_wait_s for i in infos if i is not None]
+                self.host_wait_s += max(waits) if waits else 0.0
+                photos = [(W, info) if info is not None else (None, None) for W, info in zip(Ws, infos)]
+        res = []
+        for T, (fit, _, kept, counts), photo in zip(self._targets, rows, photos):
+            T.n_kept = self.n_kept = kept
+            res.append(self._finish(T, fit, counts, input_img, img_identifier, photo=photo))
+        return res
 
     def track(self, input_img, debug=False, img_identifier=None):
         if not self._targets:
@@ -324,10 +400,7 @@ class WOFTChainedMulti(WOFTChained):
         if self._route == "loop":
             res = [self._planar_stage(T, out, input_img, img_identifier) for T in self._targets]
         else:
-            res = []
-            for T, (fit, _, kept, counts) in zip(self._targets, self._planar_batched(out, input_img)):
-                T.n_kept = self.n_kept = kept
-                res.append(self._finish(T, fit, counts, input_img, img_identifier))
+            res = self._finish_batched(self._planar_batched(out, input_img), input_img, img_identifier)
         self._announced_targets.update(t for t, T in enumerate(self._targets) if T._announced)
         return np.stack([H for H, _ in res]), [meta for _, meta in res]
 

@@ -94,10 +94,7 @@ class WOFTChainedMultiWindow(WOFTChainedMulti, WOFTChainedWindow):
         if self._route == "loop":
             res = [self._planar_stage(T, out, input_img, img_identifier) for T in self._targets]
         else:
-            res = []
-            for T, (fit, _, kept, counts) in zip(self._targets, self._planar_batched(out, input_img)):
-                T.n_kept = self.n_kept = kept
-                res.append(self._finish(T, fit, counts, input_img, img_identifier))
+            res = self._finish_batched(self._planar_batched(out, input_img), input_img, img_identifier)
         self._announced_targets.update(t for t, T in enumerate(self._targets) if T._announced)
         self._follow()
         for _, meta in res:

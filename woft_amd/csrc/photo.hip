@@ -4,6 +4,8 @@
 // control rules, solves and steps the state on the device.  A refinement is iters + 1 pairs of them enqueued back to back; after
 // a stop the remaining launches return on a uniform branch.  Coordinates, the sample, every per-pixel term and every sum are
 // fp64; every product is followed by its add (the build passes -ffp-contract=off); no atomics: two calls give equal bytes.
+// The multi-target forms run K targets of one template and one frame through the same two device
+// functions on a (partials, K) and a K grid: the same chunks summed in the same order, so a target's bytes are the single form's.
 #include <math.h>
 #include "common.h"
 
@@ -40,13 +42,17 @@ __device__ __forceinline__ State load_state(const double* st) {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
+// The mask test: a uint8 mask, or bit t of the multi-target bit plane (unsigned words: target 31 is the top bit).
+__device__ __forceinline__ bool in_mask(const uint8_t* m, int64_t o, int) { return m[o] != 0; }
+__device__ __forceinline__ bool in_mask(const uint32_t* m, int64_t o, int t) { return ((m[o] >> t) & 1u) != 0u; }
+
 // Candidate idx of the strided grid (row-major) -> its row x of the 16-column system whose Gram matrix carries every sum:
 //   x[0 .. NU) = sqrt(omega) a,  x[NU] = sqrt(omega) e,  x[NU + 1] = sqrt(weight rho),  x[NU + 2] = sqrt(weight),  x[NU + 3] = 1,
 // so that G = X^T X restricted to NU x NU, r = its column NU, sum weight rho, sum weight and n = the last three diagonal
 // entries.  false (x untouched): the candidate is outside the grid, the template's interior, the mask or the frame.
 // k3 = 3 * huber_k, < 0: no Huber.
-template <typename TT, typename TF, int NU>
-__device__ __forceinline__ bool pixel_row(const TT* __restrict__ tmpl, const uint8_t* __restrict__ mask,
+template <typename TT, typename TF, typename TM, int NU>
+__device__ __forceinline__ bool pixel_row(const TT* __restrict__ tmpl, const TM* __restrict__ mask, int tbit,
                                           const float* __restrict__ weights, const TF* __restrict__ frame, const Geom& gm,
                                           const State& st, double k3, int64_t idx, double* x_out) {
     {
@@ -55,7 +61,7 @@ __device__ __forceinline__ bool pixel_row(const TT* __restrict__ tmpl, const uin
         const int x = gm.x0 + ix * gm.stride, y = gm.y0 + iy * gm.stride;
         if (x < 1 || x > gm.w - 2 || y < 1 || y > gm.h - 2) return false;
         const int64_t o = (int64_t)y * gm.w + x;
-        if (mask[o] == 0) return false;
+        if (!in_mask(mask, o, tbit)) return false;
         const double xn = ((double)x - gm.cx) / gm.s, yn = ((double)y - gm.cy) / gm.s;
         const double qx = st.m[0] * xn + st.m[1] * yn + st.m[2];
         const double qy = st.m[3] * xn + st.m[4] * yn + st.m[5];
@@ -99,15 +105,13 @@ __device__ __forceinline__ bool pixel_row(const TT* __restrict__ tmpl, const uin
 // accumulator registers per lane where one accumulator per entry and lane took 2 x 68, and no cross-lane reduction at the end.
 // Rows are ROW_LD = 17 doubles apart: the 32 lanes of a half wave write their rows to distinct banks.
 constexpr int ROW_LD = 17;
-template <typename TT, typename TF, int NU>
-__global__ __launch_bounds__(THREADS) void photo_accum_kernel(const TT* __restrict__ tmpl, const uint8_t* __restrict__ mask,
-                                                              const float* __restrict__ weights, const TF* __restrict__ frame,
-                                                              Geom gm, State init, const double* st_dev, const int* stop,
-                                                              double k3, double* __restrict__ part) {
-    if (stop != nullptr && *stop != 0) return;                   // (uniform: the refinement has stopped)
+// The partial of chunk `chunk` of the pixel set (gm, mask -- bit tbit of it when it is a bit plane) at the state st -> part[0 .. NACC).
+template <typename TT, typename TF, typename TM, int NU>
+__device__ __forceinline__ void accum_chunk(const TT* __restrict__ tmpl, const TM* __restrict__ mask, int tbit,
+                                            const float* __restrict__ weights, const TF* __restrict__ frame, const Geom& gm,
+                                            const State& st, double k3, int chunk, double* __restrict__ part) {
     constexpr int TRI = NU * (NU + 1) / 2, LIVE = NU + 4;
     static_assert(LIVE <= 16, "the system's columns fit one MFMA tile");
-    const State st = st_dev != nullptr ? load_state(st_dev) : init;
     __shared__ double rows[THREADS * ROW_LD];
     __shared__ double red[THREADS / 64][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(THREADS) void photo_accum_kernel(const TT* __restri
         double x[LIVE];
 #pragma unroll
         for (int c = 0; c < LIVE; ++c) x[c] = 0.0;
-        pixel_row<TT, TF, NU>(tmpl, mask, weights, frame, gm, st, k3, (int64_t)blockIdx.x * WOFT_PHOTO_CHUNK + j * THREADS + tid, x);
+        pixel_row<TT, TF, TM, NU>(tmpl, mask, tbit, weights, frame, gm, st, k3, (int64_t)chunk * WOFT_PHOTO_CHUNK + j * THREADS + tid, x);
 #pragma unroll
         for (int c = 0; c < LIVE; ++c) mine[c] = x[c];
         __syncthreads();
@@ -145,8 +149,68 @@ __global__ __launch_bounds__(THREADS) void photo_accum_kernel(const TT* __restri
         double v = red[0][tid];
 #pragma unroll
         for (int q = 1; q < THREADS / 64; ++q) v = v + red[q][tid];
-        part[(int64_t)blockIdx.x * NACC + slot] = v;
+        part[slot] = v;
     }
+}
+
+template <typename TT, typename TF, int NU>
+__global__ __launch_bounds__(THREADS) void photo_accum_kernel(const TT* __restrict__ tmpl, const uint8_t* __restrict__ mask,
+                                                              const float* __restrict__ weights, const TF* __restrict__ frame,
+                                                              Geom gm, State init, const double* st_dev, const int* stop,
+                                                              double k3, double* __restrict__ part) {
+    if (stop != nullptr && *stop != 0) return;                   // (uniform: the refinement has stopped)
+    const State st = st_dev != nullptr ? load_state(st_dev) : init;
+    accum_chunk<TT, TF, uint8_t, NU>(tmpl, mask, 0, weights, frame, gm, st, k3, (int)blockIdx.x, part + (int64_t)blockIdx.x * NACC);
+}
+
+// ---- K targets of one template and one frame ---------------------------------------------------------------
+// What differs per target travels by value in the kernels' arguments (3 584 B at 32 targets, as the homographies of
+// mask_bbox_multi_kernel do): the box, the threshold, the number of partials (0: the target is inactive) and the starting state.
+struct Tgt {
+    int x0, y0, x1, y1, n_need, n_part;
+    double m[9], g, b;
+};
+struct TgtSet {
+    Tgt t[WOFT_MULTI_MAX_TARGETS];
+};
+static_assert(sizeof(TgtSet) == 112 * WOFT_MULTI_MAX_TARGETS, "the targets fit the kernel arguments");
+
+// Target t's slice of the workspace: p_max partials, then the 16 + 2 doubles of its device state (the single form's layout).
+__device__ __host__ __forceinline__ int64_t slice_doubles(int p_max) { return (int64_t)p_max * NACC + ST_DOUBLES + 2; }
+
+// `shared` (the image sizes and the stride) completed with a target's box: the arithmetic of prepare(), every value exact.
+__device__ __forceinline__ Geom target_geom(const Geom& shared, int x0, int y0, int x1, int y1) {
+    Geom gm = shared;
+    gm.x0 = x0, gm.y0 = y0;
+    gm.nx = (x1 - x0) / gm.stride + 1, gm.ny = (y1 - y0) / gm.stride + 1;
+    gm.cx = (x0 + x1) / 2.0, gm.cy = (y0 + y1) / 2.0;
+    const int ext = (x1 - x0) > (y1 - y0) ? (x1 - x0) : (y1 - y0);
+    gm.s = (ext > 1 ? ext : 1) / 2.0;
+    return gm;
+}
+
+// Workgroup (p, t): partial p of target t, by accum_chunk on bit t of the plane; p past the target's partials, an inactive or a
+// stopped target: a uniform return.  first: the state is the arguments' (iterate 0, or an evaluation), else the slice's.
+template <typename TT, typename TF, int NU>
+__global__ __launch_bounds__(THREADS) void photo_accum_multi_kernel(const TT* __restrict__ tmpl, const uint32_t* __restrict__ bits,
+                                                                    const float* __restrict__ weights,
+                                                                    const TF* __restrict__ frame, Geom shared, TgtSet ts, int p_max,
+                                                                    int first, double k3, double* __restrict__ ws) {
+    const int t = (int)blockIdx.y, p = (int)blockIdx.x;
+    if (p >= ts.t[t].n_part) return;
+    double* part = ws + (int64_t)t * slice_doubles(p_max);
+    const double* st_dev = part + (int64_t)p_max * NACC;
+    if (!first && *reinterpret_cast<const int*>(st_dev + ST_DOUBLES) != 0) return;
+    State st;
+    if (first) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) st.m[i] = ts.t[t].m[i];
+        st.g = ts.t[t].g, st.b = ts.t[t].b;
+    } else {
+        st = load_state(st_dev);
+    }
+    const Geom gm = target_geom(shared, ts.t[t].x0, ts.t[t].y0, ts.t[t].x1, ts.t[t].y1);
+    accum_chunk<TT, TF, uint32_t, NU>(tmpl, bits, t, weights, frame, gm, st, k3, p, part + (int64_t)p * NACC);
 }
 
 // acc[t] = the sum over the n_part partials of value t, in index order.  One lane per value adding n_part numbers straight from
@@ -192,6 +256,17 @@ __global__ __launch_bounds__(SUM_THREADS) void photo_sum_kernel(const double* __
     if ((int)threadIdx.x < nacc) out[threadIdx.x] = acc[threadIdx.x];
 }
 
+// The batched evaluation's second launch, one workgroup per target: out[t * NACC ..] = the sum of target t's partials.
+__global__ __launch_bounds__(SUM_THREADS) void photo_sum_multi_kernel(TgtSet ts, int p_max, int nacc, const double* __restrict__ ws,
+                                                                      double* out) {
+    const int t = (int)blockIdx.x, n_part = ts.t[t].n_part;
+    if (n_part == 0) return;
+    __shared__ double acc[NACC];
+    __shared__ double tile[SUM_TILE * NACC];
+    sum_partials(ws + (int64_t)t * slice_doubles(p_max), n_part, nacc, tile, acc);
+    if ((int)threadIdx.x < nacc) out[(int64_t)t * NACC + threadIdx.x] = acc[threadIdx.x];
+}
+
 // (x, y) in normalised template coordinates through m, de-homogenised.
 __device__ __forceinline__ void project(const double* m, double xn, double yn, double& u, double& v) {
     const double z = m[6] * xn + m[7] * yn + m[8];
@@ -204,9 +279,9 @@ __device__ __forceinline__ void project(const double* m, double xn, double yn, d
 // The solve runs on one lane with the system in registers (NU is a template argument, every loop unrolled): with run-time
 // indices into LDS the factorisation alone took 27 us of dependent LDS round trips.
 template <int NU>
-__global__ __launch_bounds__(SUM_THREADS) void photo_step_kernel(const double* __restrict__ part, int n_part, int k, int iters,
-                                                                 Geom gm, State init, int x1, int y1, int n_need, double eps,
-                                                                 double* st, double* result) {
+__device__ __forceinline__ void step_iterate(const double* __restrict__ part, int n_part, int k, int iters, const Geom& gm,
+                                             const State& init, int x1, int y1, int n_need, double eps, double* st,
+                                             double* result) {
     constexpr int nu = NU;
     int* ctl = reinterpret_cast<int*>(st + ST_DOUBLES);
     if (k > 0 && ctl[0] != 0) return;                            // (uniform: the refinement has stopped)
@@ -332,6 +407,33 @@ __global__ __launch_bounds__(SUM_THREADS) void photo_step_kernel(const double* _
     ctl[0] = stop >= 0 ? 1 : 0;
 }
 
+template <int NU>
+__global__ __launch_bounds__(SUM_THREADS) void photo_step_kernel(const double* __restrict__ part, int n_part, int k, int iters,
+                                                                 Geom gm, State init, int x1, int y1, int n_need, double eps,
+                                                                 double* st, double* result) {
+    step_iterate<NU>(part, n_part, k, iters, gm, init, x1, y1, n_need, eps, st, result);
+}
+
+// Workgroup t: iterate k of target t on its own slice and result block -- its own state, stop, best and rule-6 iterate.  An
+// inactive target's block gets {WOFT_PHOTO_SKIPPED, -1, 0} at iterate 0 and nothing else.
+template <int NU>
+__global__ __launch_bounds__(SUM_THREADS) void photo_step_multi_kernel(TgtSet ts, Geom shared, int p_max, int k, int iters,
+                                                                       double eps, double* ws, double* result) {
+    const int t = (int)blockIdx.x, n_part = ts.t[t].n_part;
+    double* res = result + (int64_t)t * (REC * (iters + 2));
+    if (n_part == 0) {
+        if (k == 0 && threadIdx.x == 0) res[0] = (double)WOFT_PHOTO_SKIPPED, res[1] = -1.0, res[2] = 0.0;
+        return;
+    }
+    double* part = ws + (int64_t)t * slice_doubles(p_max);
+    State init;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) init.m[i] = ts.t[t].m[i];
+    init.g = ts.t[t].g, init.b = ts.t[t].b;
+    const Geom gm = target_geom(shared, ts.t[t].x0, ts.t[t].y0, ts.t[t].x1, ts.t[t].y1);
+    step_iterate<NU>(part, n_part, k, iters, gm, init, ts.t[t].x1, ts.t[t].y1, ts.t[t].n_need, eps, part + (int64_t)p_max * NACC, res);
+}
+
 int64_t n_partials(int32_t box_w, int32_t box_h, int32_t stride) {
     const int64_t nx = (box_w - 1) / stride + 1, ny = (box_h - 1) / stride + 1;
     return ceil_div64(nx * ny, WOFT_PHOTO_CHUNK);
@@ -387,6 +489,65 @@ bool prepare(const void* tmpl, const uint8_t* mask, int32_t h, int32_t w, const 
     return true;
 }
 
+template <typename TT, typename TF>
+void launch_accum_multi(int nu, const void* tmpl, const uint32_t* bits, const float* weights, const void* frame, const Geom& shared,
+                        const TgtSet& ts, int n_targets, int p_max, int first, double k3, double* ws, hipStream_t s) {
+    const TT* t = static_cast<const TT*>(tmpl);
+    const TF* f = static_cast<const TF*>(frame);
+    const dim3 grid((unsigned)p_max, (unsigned)n_targets);
+    if (nu == 10)
+        hipLaunchKernelGGL((photo_accum_multi_kernel<TT, TF, 10>), grid, dim3(THREADS), 0, s, t, bits, weights, f, shared, ts, p_max,
+                           first, k3, ws);
+    else
+        hipLaunchKernelGGL((photo_accum_multi_kernel<TT, TF, 8>), grid, dim3(THREADS), 0, s, t, bits, weights, f, shared, ts, p_max,
+                           first, k3, ws);
+}
+
+void accum_multi(int tmpl_f32, int frame_f32, int nu, const void* tmpl, const uint32_t* bits, const float* weights,
+                 const void* frame, const Geom& shared, const TgtSet& ts, int n_targets, int p_max, int first, double k3, double* ws,
+                 hipStream_t s) {
+    if (tmpl_f32 && frame_f32)
+        launch_accum_multi<float, float>(nu, tmpl, bits, weights, frame, shared, ts, n_targets, p_max, first, k3, ws, s);
+    else if (tmpl_f32)
+        launch_accum_multi<float, uint8_t>(nu, tmpl, bits, weights, frame, shared, ts, n_targets, p_max, first, k3, ws, s);
+    else if (frame_f32)
+        launch_accum_multi<uint8_t, float>(nu, tmpl, bits, weights, frame, shared, ts, n_targets, p_max, first, k3, ws, s);
+    else
+        launch_accum_multi<uint8_t, uint8_t>(nu, tmpl, bits, weights, frame, shared, ts, n_targets, p_max, first, k3, ws, s);
+}
+
+// prepare() for K targets: every target's box, state and threshold checked -- active or not -- and laid out for the kernels;
+// p_max = the largest number of partials of any of the K boxes (the workspace's layout), any = some target is active.
+// gains, biases, n_need: NULL = 1, 0, 0 for every target.  false: WOFT_EINVAL.
+bool prepare_multi(const void* tmpl, const uint32_t* bits, int32_t h, int32_t w, const void* frame, int32_t hf, int32_t wf,
+                   int32_t n_targets, const int32_t* boxes, int32_t stride, const double* W, const double* gains,
+                   const double* biases, const int32_t* n_need, const int32_t* active, double huber_k, const void* ws, Geom& shared,
+                   TgtSet& ts, int& p_max, bool& any) {
+    if (!tmpl || !bits || !frame || !boxes || !W || !active || !ws) return false;
+    if (n_targets < 1 || n_targets > WOFT_MULTI_MAX_TARGETS) return false;
+    p_max = 0, any = false;
+    for (int t = 0; t < n_targets; ++t) {
+        Geom gm;
+        State st;
+        int n_part = 0;
+        // (the mask argument of the single form's checks is only tested against NULL)
+        if (!prepare(tmpl, reinterpret_cast<const uint8_t*>(bits), h, w, frame, hf, wf, boxes + 4 * t, stride, W + 9 * t,
+                     gains ? gains[t] : 1.0, biases ? biases[t] : 0.0, huber_k, ws, gm, st, n_part))
+            return false;
+        if (n_need && n_need[t] < 0) return false;
+        Tgt& tg = ts.t[t];
+        tg.x0 = boxes[4 * t], tg.y0 = boxes[4 * t + 1], tg.x1 = boxes[4 * t + 2], tg.y1 = boxes[4 * t + 3];
+        tg.n_need = n_need ? n_need[t] : 0;
+        tg.n_part = active[t] != 0 ? n_part : 0;
+        for (int i = 0; i < 9; ++i) tg.m[i] = st.m[i];
+        tg.g = st.g, tg.b = st.b;
+        p_max = n_part > p_max ? n_part : p_max;
+        any = any || active[t] != 0;
+        if (t == 0) shared = gm;                                                  // (h, w, hf, wf, stride: the shared fields)
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" int64_t woft_photo_ws_bytes(int32_t box_w, int32_t box_h, int32_t stride) {
@@ -438,6 +599,64 @@ extern "C" int woft_photo_refine(const void* tmpl, int32_t tmpl_f32, const uint8
         else
             hipLaunchKernelGGL(photo_step_kernel<8>, dim3(1), dim3(SUM_THREADS), 0, s, part, n_part, k, iters, gm, st, box[2], box[3],
                                n_need, eps, st_dev, result);
+    }
+    return woft_launch_status();
+}
+
+extern "C" int64_t woft_photo_multi_ws_bytes(int32_t n_targets, int32_t p_max) {
+    if (n_targets < 1 || p_max < 1) return -1;
+    return (int64_t)n_targets * slice_doubles(p_max) * (int64_t)sizeof(double);
+}
+
+extern "C" int woft_photo_eval_multi(const void* tmpl, int32_t tmpl_f32, const uint32_t* bits, int32_t h, int32_t w,
+                                     const float* weights, const void* frame, int32_t frame_f32, int32_t hf, int32_t wf,
+                                     int32_t n_targets, const int32_t* boxes, int32_t stride, const double* W, const double* gains,
+                                     const double* biases, const int32_t* active, int32_t gain_bias, double huber_k, void* ws,
+                                     double* out, void* stream) {
+    Geom shared;
+    TgtSet ts = {};
+    int p_max = 0;
+    bool any = false;
+    if (!out || !gains || !biases) return WOFT_EINVAL;
+    if (!prepare_multi(tmpl, bits, h, w, frame, hf, wf, n_targets, boxes, stride, W, gains, biases, nullptr, active, huber_k, ws,
+                       shared, ts, p_max, any))
+        return WOFT_EINVAL;
+    if (!any) return 0;
+    const int nu = gain_bias ? 10 : 8;
+    hipStream_t s = (hipStream_t)stream;
+    accum_multi(tmpl_f32, frame_f32, nu, tmpl, bits, weights, frame, shared, ts, n_targets, p_max, 1,
+                huber_k > 0.0 ? 3.0 * huber_k : -1.0, static_cast<double*>(ws), s);
+    hipLaunchKernelGGL(photo_sum_multi_kernel, dim3((unsigned)n_targets), dim3(SUM_THREADS), 0, s, ts, p_max,
+                       nu * (nu + 1) / 2 + nu + 3, static_cast<const double*>(ws), out);
+    return woft_launch_status();
+}
+
+extern "C" int woft_photo_refine_multi(const void* tmpl, int32_t tmpl_f32, const uint32_t* bits, int32_t h, int32_t w,
+                                       const float* weights, const void* frame, int32_t frame_f32, int32_t hf, int32_t wf,
+                                       int32_t n_targets, const int32_t* boxes, int32_t stride, const double* W0,
+                                       const int32_t* n_need, const int32_t* active, int32_t iters, int32_t gain_bias, double huber_k,
+                                       double eps, void* ws, double* result, void* stream) {
+    Geom shared;
+    TgtSet ts = {};
+    int p_max = 0;
+    bool any = false;
+    if (!result || !n_need || iters < 0 || iters > WOFT_PHOTO_MAX_ITERS || !(eps >= 0.0) || !isfinite(eps)) return WOFT_EINVAL;
+    if (!prepare_multi(tmpl, bits, h, w, frame, hf, wf, n_targets, boxes, stride, W0, nullptr, nullptr, n_need, active, huber_k, ws,
+                       shared, ts, p_max, any))
+        return WOFT_EINVAL;
+    if (!any) return 0;
+    const int nu = gain_bias ? 10 : 8;
+    const double k3 = huber_k > 0.0 ? 3.0 * huber_k : -1.0;
+    double* wsd = static_cast<double*>(ws);
+    hipStream_t s = (hipStream_t)stream;
+    for (int k = 0; k <= iters; ++k) {
+        accum_multi(tmpl_f32, frame_f32, nu, tmpl, bits, weights, frame, shared, ts, n_targets, p_max, k == 0, k3, wsd, s);
+        if (nu == 10)
+            hipLaunchKernelGGL(photo_step_multi_kernel<10>, dim3((unsigned)n_targets), dim3(SUM_THREADS), 0, s, ts, shared, p_max, k,
+                               iters, eps, wsd, result);
+        else
+            hipLaunchKernelGGL(photo_step_multi_kernel<8>, dim3((unsigned)n_targets), dim3(SUM_THREADS), 0, s, ts, shared, p_max, k,
+                               iters, eps, wsd, result);
     }
     return woft_launch_status();
 }

@@ -1531,3 +1531,66 @@ def photo_refine(tmpl, mask, weights, frame, box, stride, W0, iters, gain_bias, 
                                         int(stride), (C.c_double * 9)(*np.asarray(W0, dtype=np.float64).ravel().tolist()),
                                         int(iters), int(bool(gain_bias)), _photo_huber(huber_k), int(n_need), float(eps), ptr(ws),
                                         ptr(result), stream_ptr()), "woft_photo_refine")
+
+
+PHOTO_STATUS_MULTI = PHOTO_STATUS + ("SKIPPED",)    # (WOFT_PHOTO_SKIPPED: an inactive target of the multi-target forms)
+
+
+def photo_multi_partials(boxes, stride):
+    """P_max of woft_photo_*_multi: the largest number of WOFT_PHOTO_CHUNK partials of any of the K inclusive boxes."""
+    s = int(stride)
+    return max(-(-(((int(b[2]) - int(b[0])) // s + 1) * ((int(b[3]) - int(b[1])) // s + 1)) // PHOTO_CHUNK) for b in boxes)
+
+
+def photo_multi_ws(boxes, stride, device=None):
+    """Scratch of woft_photo_eval_multi / woft_photo_refine_multi for K inclusive boxes, shared with the single forms' (one per
+    device and stream, grown on demand)."""
+    need = int(_lib.load().woft_photo_multi_ws_bytes(len(boxes), photo_multi_partials(boxes, stride)))
+    if need < 0:
+        raise _lib.WoftHipError(f"woft_photo_multi_ws_bytes rejected {len(boxes)} boxes, stride {stride!r}")
+    return _stream_scratch(_PHOTO_WS, need, device)
+
+
+def _photo_multi_args(tmpl, bits, weights, frame, boxes, W):
+    K = len(boxes)
+    for t, what in ((tmpl, "template"), (frame, "frame")):
+        assert t.dtype in (torch.uint8, torch.float32) and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous(), what
+    h, w = tmpl.shape[:2]
+    assert bits.dtype == torch.int32 and tuple(bits.shape) == (h, w) and bits.is_contiguous()
+    assert weights is None or (_f32c(weights) and tuple(weights.shape) == (h, w))
+    W = np.asarray(W, dtype=np.float64).reshape(K, 9)
+    return ((ptr(tmpl), int(tmpl.dtype == torch.float32), ptr(bits), h, w, ptr(weights), ptr(frame),
+             int(frame.dtype == torch.float32), frame.shape[0], frame.shape[1], K,
+             (C.c_int32 * (4 * K))(*[int(v) for b in boxes for v in b])), (C.c_double * (9 * K))(*W.ravel().tolist()))
+
+
+def _i32s(values, K):
+    assert len(values) == K
+    return (C.c_int32 * K)(*[int(v) for v in values])
+
+
+def photo_eval_multi(tmpl, bits, weights, frame, boxes, stride, W, gains, biases, active, gain_bias, huber_k, out, ws=None):
+    """woft_photo_eval_multi: the normal equations of K targets of one template and one frame at K states -> out ((K, PHOTO_NACC)
+    float64 on the device; row t as photo_eval writes it on target t's mask, untouched where active[t] is 0).  bits: the (h, w)
+    int32 view of the targets' bit plane; boxes (K, 4), W (K, 3, 3), gains, biases, active (K) on the host."""
+    K = len(boxes)
+    ws = ws if ws is not None else photo_multi_ws(boxes, stride, tmpl.device)
+    assert out.dtype == torch.float64 and out.numel() >= K * PHOTO_NACC and out.is_contiguous()
+    head, Wc = _photo_multi_args(tmpl, bits, weights, frame, boxes, W)
+    dbl = lambda v: (C.c_double * K)(*[float(x) for x in v])
+    assert len(gains) == K and len(biases) == K
+    check(_lib.load().woft_photo_eval_multi(*head, int(stride), Wc, dbl(gains), dbl(biases), _i32s(active, K), int(bool(gain_bias)),
+                                            _photo_huber(huber_k), ptr(ws), ptr(out), stream_ptr()), "woft_photo_eval_multi")
+
+
+def photo_refine_multi(tmpl, bits, weights, frame, boxes, stride, W0, n_need, active, iters, gain_bias, huber_k, eps, result,
+                       ws=None):
+    """woft_photo_refine_multi: iters + 1 (accumulate, step) launch pairs for K targets of one template and one frame -> result
+    (K blocks of PHOTO_REC * (iters + 2) float64 on the device, each photo_refine's block of that target)."""
+    K = len(boxes)
+    ws = ws if ws is not None else photo_multi_ws(boxes, stride, tmpl.device)
+    assert result.dtype == torch.float64 and result.numel() >= K * PHOTO_REC * (iters + 2) and result.is_contiguous()
+    head, Wc = _photo_multi_args(tmpl, bits, weights, frame, boxes, W0)
+    check(_lib.load().woft_photo_refine_multi(*head, int(stride), Wc, _i32s(n_need, K), _i32s(active, K), int(iters),
+                                              int(bool(gain_bias)), _photo_huber(huber_k), float(eps), ptr(ws), ptr(result),
+                                              stream_ptr()), "woft_photo_refine_multi")

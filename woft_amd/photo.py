@@ -9,6 +9,9 @@ host decision inside the loop.
     pt = PhotoTemplate(template, mask)                     # once per template
     H, info = pt.refine(frame, H_t2f)                      # per frame: H_t2f maps template pixels to frame pixels
     H, info = refine_homography(template, mask, frame, H_t2f)
+
+    pm = PhotoTemplateMulti(template, [mask_a, mask_b])   # K targets of one template
+    Hs, infos = pm.refine(frame, Hs_t2f, active=[True, True])     # one batched call and one read whatever K
 """
 import math
 import time
@@ -71,11 +74,35 @@ def check_options(iters, gain_bias, huber_k, min_valid, eps, prefix=""):
     return int(iters), bool(gain_bias), huber_k, mv, ep
 
 
-class _Result:
-    """The device result block of a refinement of `iters` iterations, its pinned host mirror and the event of its one read."""
+def _device_weights(weights, h, w, device):
+    """The optional (h, w) float32 weight map, checked -> contiguous device tensor or None."""
+    if weights is None:
+        return None
+    wt = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
+    if tuple(wt.shape) != (h, w) or wt.dtype != torch.float32:
+        raise ValueError(f"weights: float32 of shape {(h, w)} is expected, got {wt.dtype} {tuple(wt.shape)}")
+    if bool((wt < 0).any()) or not bool(torch.isfinite(wt).all()):
+        raise ValueError("weights: finite values >= 0 are expected")
+    return wt.to(device).contiguous()
 
-    def __init__(self, iters, device):
-        n = ops.PHOTO_REC * (iters + 2)
+
+def _pixel_set(inside, h, w, stride):
+    """A boolean mask -> (box (x0, y0, x1, y1) inclusive, n_set, centre, scale) of its pixel set; (None, 0, None, None) when the
+    mask is empty."""
+    ys, xs = np.nonzero(inside)
+    if not len(xs):
+        return None, 0, None, None
+    x0, x1, y0, y1 = int(xs.min()), int(xs.max()), int(ys.min()), int(ys.max())
+    keep = ((xs >= 1) & (xs <= w - 2) & (ys >= 1) & (ys <= h - 2) & ((xs - x0) % stride == 0) & ((ys - y0) % stride == 0))
+    return (x0, y0, x1, y1), int(keep.sum()), ((x0 + x1) / 2.0, (y0 + y1) / 2.0), max(x1 - x0, y1 - y0, 1) / 2.0
+
+
+class _Result:
+    """The device result block(s) of a refinement of `iters` iterations (one per target), the pinned host mirror and the event of
+    the one read."""
+
+    def __init__(self, iters, device, n_targets=1):
+        n = n_targets * ops.PHOTO_REC * (iters + 2)
         self.dev = torch.zeros(n, dtype=torch.float64, device=device)
         self.host = torch.empty(n, dtype=torch.float64).pin_memory()
         self.event = torch.cuda.Event()
@@ -104,24 +131,10 @@ class PhotoTemplate:
             raise ValueError(f"mask: a uint8 or bool array of shape {(self.h, self.w)} is expected, got {m.dtype} {m.shape}")
         inside = m > 0
         self.mask = torch.from_numpy(np.ascontiguousarray(inside.astype(np.uint8))).to(self.template.device)
-        self.weights = None
-        if weights is not None:
-            wt = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights))
-            if tuple(wt.shape) != (self.h, self.w) or wt.dtype != torch.float32:
-                raise ValueError(f"weights: float32 of shape {(self.h, self.w)} is expected, got {wt.dtype} {tuple(wt.shape)}")
-            if bool((wt < 0).any()) or not bool(torch.isfinite(wt).all()):
-                raise ValueError("weights: finite values >= 0 are expected")
-            self.weights = wt.to(self.template.device).contiguous()
-        ys, xs = np.nonzero(inside)
-        self.box, self.n_set = None, 0
-        if len(xs):
-            x0, x1, y0, y1 = int(xs.min()), int(xs.max()), int(ys.min()), int(ys.max())
-            self.box = (x0, y0, x1, y1)
-            keep = ((xs >= 1) & (xs <= self.w - 2) & (ys >= 1) & (ys <= self.h - 2)
-                    & ((xs - x0) % self.stride == 0) & ((ys - y0) % self.stride == 0))
-            self.n_set = int(keep.sum())
-            self.centre = ((x0 + x1) / 2.0, (y0 + y1) / 2.0)
-            self.scale = max(x1 - x0, y1 - y0, 1) / 2.0
+        self.weights = _device_weights(weights, self.h, self.w, self.template.device)
+        self.box, self.n_set, centre, scale = _pixel_set(inside, self.h, self.w, self.stride)
+        if self.box is not None:
+            self.centre, self.scale = centre, scale
         self._results = {}
 
     def _launchable(self, nu):
@@ -165,6 +178,110 @@ class PhotoTemplate:
                      .reshape(n_eval, ops.PHOTO_REC).copy(), self.n_set, waited)
         H = H0.copy() if info.best < 0 else blk[3:12].reshape(3, 3).copy()
         return H, info
+
+
+class PhotoTemplateMulti:
+    """K targets (1 .. 32) of ONE template for batched refinements against one frame: `masks` is a list of K
+    (h, w) uint8 / bool masks or a (K, h, w) array, and may overlap.  Holds the targets' bit plane on the device (pack_target_bits'
+    layout), per target the box, centre, scale and n_set by PhotoTemplate's rule, and one pinned result mirror per `iters`.
+    Target t's results are PhotoTemplate(template, masks[t], stride, weights)'s, byte for byte."""
+
+    def __init__(self, template, masks, stride=1, weights=None):
+        from .chained import MAX_TARGETS, pack_target_bits
+        if isinstance(masks, torch.Tensor):
+            masks = masks.detach().cpu().numpy()
+        if isinstance(masks, np.ndarray):
+            if masks.ndim != 3:
+                raise ValueError(f"masks: a list of (h, w) masks or a (K, h, w) array is expected, got shape {masks.shape}")
+            masks = list(masks)
+        masks = [m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in masks]
+        if not 1 <= len(masks) <= MAX_TARGETS:
+            raise ValueError(f"1 to {MAX_TARGETS} masks are expected, got {len(masks)}")
+        if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+            raise ValueError(f"stride {stride!r}: not an integer >= 1")
+        self.stride = int(stride)
+        self.template = _device_image(template, "template")
+        self.h, self.w = self.template.shape[:2]
+        for t, m in enumerate(masks):
+            if m.shape != (self.h, self.w) or m.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"mask {t}: a uint8 or bool array of shape {(self.h, self.w)} is expected, got {m.dtype} {m.shape}")
+        self.K = len(masks)
+        self.weights = _device_weights(weights, self.h, self.w, self.template.device)
+        self.bits = torch.from_numpy(pack_target_bits(masks).view(np.int32)).to(self.template.device)
+        self.boxes, self.n_sets, self.centres, self.scales = [], [], [], []
+        for m in masks:
+            box, n_set, centre, scale = _pixel_set(m > 0, self.h, self.w, self.stride)
+            self.boxes.append(box), self.n_sets.append(n_set), self.centres.append(centre), self.scales.append(scale)
+        # (a target without a box never takes part; the entry points still check a box per target)
+        self._call_boxes = [b if b is not None else (0, 0, 0, 0) for b in self.boxes]
+        self._results = {}
+
+    def _launchable(self, t, nu):
+        return self.boxes[t] is not None and self.n_sets[t] >= nu and self.h >= 3 and self.w >= 3
+
+    def _states(self, Hs):
+        Hs = np.asarray(Hs, dtype=np.float64)
+        if Hs.shape != (self.K, 3, 3) or not np.all(np.isfinite(Hs)):
+            raise ValueError(f"Hs: finite matrices of shape {(self.K, 3, 3)} are expected, got shape {Hs.shape}")
+        return Hs
+
+    def _active(self, active, nu):
+        if active is None:
+            active = [True] * self.K
+        if len(active) != self.K:
+            raise ValueError(f"active: {self.K} entries are expected, got {len(active)}")
+        active = [bool(a) for a in active]
+        return active, [a and self._launchable(t, nu) for t, a in enumerate(active)]
+
+    def normal_equations(self, frame, Hs, gains=None, biases=None, gain_bias=True, huber_k=None):
+        """One evaluation per target at the states (Hs (K, 3, 3), gains, biases in grey levels; None: 1 and 0) -> K tuples
+        (G, r, cost, n_valid) as PhotoTemplate.normal_equations returns them."""
+        _, gain_bias, huber_k, _, _ = check_options(0, gain_bias, huber_k, 0.5, 0.0)
+        nu = 10 if gain_bias else 8
+        Hs = self._states(Hs)
+        for t in range(self.K):
+            if not self._launchable(t, nu):
+                raise ValueError(f"target {t}: the pixel set holds {self.n_sets[t]} pixels: fewer than the {nu} unknowns")
+        gains = [1.0] * self.K if gains is None else [float(g) for g in gains]
+        biases = [0.0] * self.K if biases is None else [3.0 * float(b) for b in biases]
+        frame = _device_image(frame, "frame")
+        out = torch.empty((self.K, ops.PHOTO_NACC), dtype=torch.float64, device=self.template.device)
+        ops.photo_eval_multi(self.template, self.bits, self.weights, frame, self._call_boxes, self.stride, Hs, gains, biases,
+                             [1] * self.K, gain_bias, huber_k, out)
+        return [unpack_sums(row, nu) for row in out.cpu().numpy()]
+
+    def refine(self, frame, Hs, active=None, iters=10, gain_bias=True, huber_k=None, min_valid=0.5, eps=1e-3):
+        """Refine the K poses Hs (K, 3, 3; template pixels -> frame pixels) against `frame` in ONE woft_photo_refine_multi call and
+        ONE read -> (Hs_out (K, 3, 3) float64, infos): infos[t] is PhotoTemplate.refine's namespace; None and the input back for a
+        target with active[t] false; 'TOO_FEW' with best = -1 and the input back, without taking part in the launch, for a target
+        whose pixel set is empty or smaller than the unknowns.  No launch and no read when no target takes part."""
+        iters, gain_bias, huber_k, min_valid, eps = check_options(iters, gain_bias, huber_k, min_valid, eps)
+        Hs = self._states(Hs)
+        nu = 10 if gain_bias else 8
+        active, takes_part = self._active(active, nu)
+        out = Hs.copy()
+        infos = [None if not a else _info("TOO_FEW", -1, np.zeros((0, ops.PHOTO_REC)), self.n_sets[t], 0.0)
+                 for t, a in enumerate(active)]
+        if not any(takes_part):
+            return out, infos
+        frame = _device_image(frame, "frame")
+        res = self._results.get(iters)
+        if res is None:
+            res = self._results[iters] = _Result(iters, self.template.device, self.K)
+        n_need = [max(nu, int(math.ceil(min_valid * n))) for n in self.n_sets]
+        ops.photo_refine_multi(self.template, self.bits, self.weights, frame, self._call_boxes, self.stride, Hs, n_need,
+                               [int(a) for a in takes_part], iters, gain_bias, huber_k, eps, res.dev)
+        waited = res.read()
+        blocks = res.host.numpy().reshape(self.K, ops.PHOTO_REC * (iters + 2))
+        for t, blk in enumerate(blocks):
+            if not takes_part[t]:
+                continue
+            n_eval = int(blk[2])
+            infos[t] = _info(ops.PHOTO_STATUS[int(blk[0])], int(blk[1]), blk[ops.PHOTO_REC:ops.PHOTO_REC * (1 + n_eval)]
+                             .reshape(n_eval, ops.PHOTO_REC).copy(), self.n_sets[t], waited)
+            if infos[t].best >= 0:
+                out[t] = blk[3:12].reshape(3, 3)
+        return out, infos
 
 
 def unpack_sums(acc, nu):

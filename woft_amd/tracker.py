@@ -203,26 +203,41 @@ class YAOFTrackerSingleControl:
             raise ValueError(f"warm_start_iters {n!r}: not an integer >= 1")
         return on, (None if n is None else int(n))
 
-    def _photo_config(self):
+    def _photo_config(self, ns=""):
         """-> None (off: `photo_refine` absent, None or 0) or the options of the photometric refinement (woft_amd.photo; DESIGN.md
         section 27): dict(iters, gain_bias, huber_k, min_valid, eps, stride, blur_sigma) from the config keys `photo_refine` (the
         iteration count), `photo_gain_bias` (True), `photo_huber_k` (None), `photo_min_valid` (0.5), `photo_eps` (1e-3),
-        `photo_stride` (1), `photo_blur_sigma` (0)."""
+        `photo_stride` (1), `photo_blur_sigma` (0).  ns: a prefix of every key (the chained trackers read `chain_photo_refine`, ...)."""
         C = self.C
-        iters = config_get(C, "photo_refine")
+        iters = config_get(C, f"{ns}photo_refine")
         if iters is None or (not isinstance(iters, bool) and isinstance(iters, (int, np.integer)) and iters == 0):
             return None
         from . import photo
         D = photo.DEFAULTS
         iters, gain_bias, huber_k, min_valid, eps = photo.check_options(
-            iters, config_get(C, "photo_gain_bias", D["gain_bias"]), config_get(C, "photo_huber_k", D["huber_k"]),
-            config_get(C, "photo_min_valid", D["min_valid"]), config_get(C, "photo_eps", D["eps"]), prefix="photo_refine / photo_")
-        stride = config_get(C, "photo_stride", 1)
+            iters, config_get(C, f"{ns}photo_gain_bias", D["gain_bias"]), config_get(C, f"{ns}photo_huber_k", D["huber_k"]),
+            config_get(C, f"{ns}photo_min_valid", D["min_valid"]), config_get(C, f"{ns}photo_eps", D["eps"]),
+            prefix=f"{ns}photo_refine / {ns}photo_")
+        stride = config_get(C, f"{ns}photo_stride", 1)
         if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
-            raise ValueError(f"photo_stride {stride!r}: not an integer >= 1")
-        sigma = _float_key(C, "photo_blur_sigma", 0.0, lambda v: 0.0 <= v < float("inf"), "a finite float >= 0")
+            raise ValueError(f"{ns}photo_stride {stride!r}: not an integer >= 1")
+        sigma = _float_key(C, f"{ns}photo_blur_sigma", 0.0, lambda v: 0.0 <= v < float("inf"), "a finite float >= 0")
         return dict(iters=iters, gain_bias=gain_bias, huber_k=huber_k, min_valid=min_valid, eps=eps, stride=int(stride),
                     blur_sigma=sigma)
+
+    def _photo_options(self):
+        """The keyword arguments of a refine() call."""
+        P = self._photo
+        return dict(iters=P["iters"], gain_bias=P["gain_bias"], huber_k=P["huber_k"], min_valid=P["min_valid"], eps=P["eps"])
+
+    def _photo_decision(self, which):
+        """The refinement's part of `solver_decision`."""
+        P = self._photo
+        return (f"; photometric refinement of {which} frames ({P['iters']} iterations, "
+                + ("gain and bias" if P["gain_bias"] else "no gain / bias")
+                + (f", Huber {P['huber_k']:.9g}" if P["huber_k"] is not None else "")
+                + (f", stride {P['stride']}" if P["stride"] != 1 else "")
+                + (f", blur {P['blur_sigma']:.9g}" if P["blur_sigma"] else "") + ")")
 
     def _photo_image(self, img):
         """The image the photometric stage reads: the uint8 device frame, or with `photo_blur_sigma` its blurred float32 version."""
@@ -236,13 +251,16 @@ class YAOFTrackerSingleControl:
         """Align the fitted pose to the pixels: W0 = inv(H_cur2init) (template -> frame) refined against the template and its mask;
         -> inv(W), normalised as compose_H normalises.  meta.photo says what happened; a refinement without an eligible iterate
         returns the pose it was given."""
-        P = self._photo
         if not np.all(np.isfinite(H_cur2init)):                      # (nothing to start from: the pose stays what the fit gave)
             meta.photo = None
             return H_cur2init
-        W, info = self._photo_template.refine(self._photo_image(frame), np.linalg.inv(H_cur2init), iters=P["iters"],
-                                              gain_bias=P["gain_bias"], huber_k=P["huber_k"], min_valid=P["min_valid"], eps=P["eps"])
+        W, info = self._photo_template.refine(self._photo_image(frame), np.linalg.inv(H_cur2init), **self._photo_options())
         self.host_wait_s += info.host_wait_s
+        return self._photo_result(H_cur2init, W, info, meta)
+
+    @staticmethod
+    def _photo_result(H_cur2init, W, info, meta):
+        """What a refinement returned -> meta.photo and the pose: inv(W), or the given pose when no iterate was eligible."""
         b = info.best
         meta.photo = SimpleNamespace(status=info.status, best=b, iterates=len(info.cost), rms_before=info.rms_before,
                                      rms_after=info.rms_after, n_valid=int(info.n_valid[b]) if b >= 0 else 0,
@@ -314,12 +332,7 @@ class YAOFTrackerSingleControl:
             self.solver_decision += (f"; forward-backward check {self.fb_check} (|f + b|^2 <= {self.fb_alpha:.9g} * (|f|^2 + |b|^2) "
                                      f"+ {self.fb_beta:.9g})")
         if self._photo is not None:
-            P = self._photo
-            self.solver_decision += (f"; photometric refinement of re-detected frames ({P['iters']} iterations, "
-                                     + ("gain and bias" if P["gain_bias"] else "no gain / bias")
-                                     + (f", Huber {P['huber_k']:.9g}" if P["huber_k"] is not None else "")
-                                     + (f", stride {P['stride']}" if P["stride"] != 1 else "")
-                                     + (f", blur {P['blur_sigma']:.9g}" if P["blur_sigma"] else "") + ")")
+            self.solver_decision += self._photo_decision("re-detected")
         return spec
 
     def _fused_specs_plain(self):

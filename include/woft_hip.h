@@ -893,6 +893,31 @@ int woft_photo_refine_multi(const void* tmpl, int32_t tmpl_f32, const uint32_t* 
                             int32_t stride, const double* W0, const int32_t* n_need, const int32_t* active, int32_t iters,
                             int32_t gain_bias, double huber_k, double eps, void* ws, double* result, void* stream);
 
+/* A fold result as the weight map of the photometric refinement, and each target's visible support (csrc/photo_weights.hip;
+ * DESIGN.md section 30, this project's own semantics).  cost, vis: the fp32 planes (rows, cols) woft_flow_chain_fold /
+ * woft_flow_chain_fold_window leave, the rectangle with origin (ry, rx) of a template (h, w) -- (0, 0) and the planes' size for the
+ * full-frame trackers (the planes may be smaller than the template), R0 for the window trackers.  On template pixels (x, y):
+ *   raw(x, y) = 0 outside the rectangle; inside it, with c = cost[p], v = vis[p] at p = (y - ry) * cols + (x - rx): 0 unless c is
+ *     finite and v >= vis_thr (a NaN v fails, v == vis_thr passes); where the gate passes, mode 0 (gate): 1.0f; mode 1 (soft):
+ *     expf(-c) * v in fp32, and a product that is not finite or not > 0 becomes +0.
+ *   map(x, y) = min of raw(x + dx, y + dy) over |dx|, |dy| <= radius (0 .. WOFT_PHOTO_WEIGHTS_MAX_RADIUS): neighbours outside the
+ *     template are ignored, neighbours inside the template but outside the rectangle count as 0.
+ *   support[t] = the number of template pixels with bit t of `bits` set and map > 0, t < n_targets.
+ * bits: the (h, w) uint32 plane of pack_target_bits (device), n_targets 1 .. WOFT_MULTI_MAX_TARGETS; bits and support may be NULL with
+ * n_targets = 0: no support is computed.  map (device, h * w floats): every entry is written.  support (device, n_targets int32).
+ * One launch on 64 x 16 tiles, tile plus halo through LDS, the minimum taken separably (rows, then columns); a workgroup walks
+ * several tiles of a column so that its counts leave in one flush.  Determinism: the map has one writer per pixel; the counts are
+ * INTEGER sums -- one ballot and population count per target and wavefront row, integer LDS atomics per workgroup, one integer
+ * global atomic per target and workgroup after a hipMemsetAsync of `support` on the stream -- so their value does not depend on
+ * the order: two calls give equal bytes.  No workspace.  WOFT_EINVAL before the device is touched on a NULL cost / vis / map, a
+ * side < 1, a template of 2^31 pixels or more, a rectangle that leaves the template, n_targets outside 0 .. WOFT_MULTI_MAX_TARGETS,
+ * a NULL bits or support with n_targets > 0, vis_thr outside [0, 1] or NaN, mode outside {0, 1}, radius outside 0 ..
+ * WOFT_PHOTO_WEIGHTS_MAX_RADIUS, or a map that shares a byte with cost, vis, bits or support. */
+#define WOFT_PHOTO_WEIGHTS_MAX_RADIUS 4
+int woft_photo_weights(const float* cost, const float* vis, int32_t rows, int32_t cols, int32_t ry, int32_t rx, int32_t h, int32_t w,
+                       const uint32_t* bits, int32_t n_targets, float vis_thr, int32_t mode, int32_t radius, float* map,
+                       int32_t* support, void* stream);
+
 /* cv2.resize(img, None, fx, fy) with INTER_LINEAR geometry (tracker/YAOF_tracker_single_control.py:27-30,60-61,
  * `downscale_inputs`): src = (dst + 0.5) * scale - 0.5, edge clamped; scale = 1 / fx. */
 int woft_resize_linear_u8(const uint8_t* img, int32_t h, int32_t w, int32_t c, uint8_t* out, int32_t ho, int32_t wo,

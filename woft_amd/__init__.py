@@ -25,7 +25,7 @@ def __getattr__(name):
                 "augment", "blur_taps", "colour_matrix"):
         from . import hsynth
         return getattr(hsynth, name)
-    if name in ("PhotoTemplate", "PhotoTemplateMulti", "refine_homography"):
+    if name in ("PhotoTemplate", "PhotoTemplateMulti", "refine_homography", "photo_weight_map"):
         from . import photo
         return getattr(photo, name)
     if name == "FrameFeatures":

@@ -147,6 +147,7 @@ _SIGS = {
                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32), i32, C.c_double, vp, vp, vp]),
     "woft_photo_refine_multi": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(C.c_double),
                                       C.POINTER(i32), C.POINTER(i32), i32, i32, C.c_double, C.c_double, vp, vp, vp]),
+    "woft_photo_weights": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, f32, i32, i32, vp, vp, vp]),
     "woft_resize_linear_u8": (i32, [vp, i32, i32, i32, vp, i32, i32, f32, f32, vp]),
     "woft_warp_perspective_window_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_double), i32, i32, i32, i32, vp, vp, i32, vp]),
     "woft_crop_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),

@@ -102,6 +102,17 @@ class WOFTChained(YAOFTrackerSingleControl):
     chain_photo_stride, chain_photo_min_valid, chain_photo_eps, chain_photo_blur_sigma -- the parent's photo_* keys by meaning,
     default and error.
 
+    chain_photo_weights = 'gate' or 'soft' (absent or None: off; it needs chain_photo_refine) weights that refinement by the
+    frame's chain visibility: ONE woft_photo_weights launch per frame, right after the fold, turns the
+    fold's cost and vis into a weight map on the template -- 1 ('gate') or exp(-cost) * vis ('soft') where the chain is valid and
+    vis >= chain_vis_thr, 0 elsewhere, eroded by chain_photo_erode pixels (default 1, an integer 0 .. 4) -- and counts each
+    target's mask pixels with a positive weight; the counts travel to pinned memory behind the launch and are read after the
+    fit.  A target whose count / mask pixels is below chain_photo_min_support (default 0.25, a float in [0, 1]: a configurable
+    default, not a tuned value) is not refined: it keeps the fit's pose and meta.photo.status is 'LOW_SUPPORT' (best -1, no
+    iterates).  The others are refined with the map as the call's weights; meta.photo.support is the fraction and
+    `photo_weight_map` the frame's map, a device tensor valid until the next track().  n_valid still counts in-frame pixels
+    whatever their weight.
+
     A frame is lost when the fit is rejected (its H is still returned, the parent's `no_local_H` behaviour) or when fewer than
     4 correspondences survive or H is not finite (the previous pose is returned).  meta: lost, N_lost, global_H_success,
     H_global_cur2init (None when there was no usable fit), n_kept, chain_hist (int64 numpy, visible mask pixels per delta),
@@ -147,6 +158,17 @@ class WOFTChained(YAOFTrackerSingleControl):
                                  "do_not_mask_TCs_by_prewarped are not used")
         if self._photo is not None:
             self.solver_decision += self._photo_decision("fitted")
+        self._photo_w = self._photo_weights_config()
+        self.photo_weight_map = None              # (the frame's weight map, a device tensor valid until the next track())
+        self.photo_weights_wait_s = 0.0           # (seconds blocked on the support counts, also part of host_wait_s)
+        self._pw = None
+        if self._photo_w is not None:
+            P = self._photo_w
+            raft_type = self.flower.C.raft_type if hasattr(self.flower, "C") else config.flow_config.raft_type
+            self.solver_decision += (f"; refinement weighted by chain visibility ({P['mode']}, vis >= {self.chain_vis_thr:.9g}, eroded by "
+                                     f"{P['erode']}, targets under {P['min_support']:.9g} of their mask left at the fit's pose"
+                                     + ("; raft_type 'orig' provides neither logit: the map only drops invalid chains"
+                                        if raft_type == "orig" else "") + ")")
         if self._fused is not None and not self.chain_weights:
             self._fused = dict(self._fused, weighted=False)
         # the solver's visibility slot carries the chains' 0 / 1 occlusion gate, the way fb_check hands its verdict
@@ -161,6 +183,78 @@ class WOFTChained(YAOFTrackerSingleControl):
     def _device_solver_reads(self, raft_type):
         return True                               # (weights and gate come from chain_tc, whatever the network provides)
 
+    def _photo_weights_config(self):
+        """-> None (off: `chain_photo_weights` absent or None) or dict(mode, erode, min_support) from chain_photo_weights ('gate' /
+        'soft'), chain_photo_erode (1) and chain_photo_min_support (0.25: a configurable default, not a tuned value)."""
+        C = self.C
+        mode = config_get(C, "chain_photo_weights")
+        if mode is None:
+            return None
+        if mode not in ops.PHOTO_WEIGHT_MODES:
+            raise ValueError(f"chain_photo_weights {mode!r}: not None, 'gate' or 'soft'")
+        if self._photo is None:
+            raise ValueError("chain_photo_weights weights the photometric refinement: it needs chain_photo_refine, which is off")
+        erode = config_get(C, "chain_photo_erode", 1)
+        if isinstance(erode, bool) or not isinstance(erode, (int, np.integer)) or not 0 <= erode <= ops.PHOTO_WEIGHTS_MAX_RADIUS:
+            raise ValueError(f"chain_photo_erode {erode!r}: not an integer in 0 .. {ops.PHOTO_WEIGHTS_MAX_RADIUS}")
+        support = config_get(C, "chain_photo_min_support", 0.25)
+        try:
+            support = float(support)
+        except (TypeError, ValueError):
+            raise ValueError(f"chain_photo_min_support {support!r}: not a float in [0, 1]") from None
+        if not (0.0 <= support <= 1.0):
+            raise ValueError(f"chain_photo_min_support {support!r}: not a float in [0, 1]")
+        return dict(mode=mode, erode=int(erode), min_support=support)
+
+    def _init_photo_weights(self, bits, n_mask):
+        """The per-tracker buffers of the weighting: the targets' (H, W) int32 bit plane, their masks' pixel counts, the device and
+        pinned support counts and the event behind their copy."""
+        if self._photo_w is None:
+            return
+        K = len(n_mask)
+        self.photo_weight_map = None
+        self._pw = SimpleNamespace(bits=bits, n_mask=[int(n) for n in n_mask], K=K, frame=None, fractions=None,
+                                   map=torch.empty(tuple(bits.shape), dtype=torch.float32, device=self.device),
+                                   support=torch.zeros(K, dtype=torch.int32, device=self.device),
+                                   host=torch.zeros(K, dtype=torch.int32).pin_memory(), event=torch.cuda.Event())
+
+    def _photo_weights_launch(self, out):
+        """The frame's weight map and support counts from the fold result `out`: one launch, then the counts' asynchronous copy to
+        pinned memory on the same stream -- enqueued before the planar stage, so that its read covers them."""
+        W = self._pw
+        if W is None:
+            return
+        h, w = (int(v) for v in W.bits.shape)
+        rect = tuple(out.rect) if hasattr(out, "rect") else (0, 0, int(out.flow.shape[1]), int(out.flow.shape[2]))
+        P = self._photo_w
+        ops.photo_weights(out.cost, out.vis, rect, (h, w), W.bits, W.K, self.chain_vis_thr, ops.PHOTO_WEIGHT_MODES.index(P["mode"]),
+                          P["erode"], W.map, W.support)
+        W.host.copy_(W.support, non_blocking=True)
+        W.event.record()
+        W.frame, W.fractions, self.photo_weight_map = self._n_tracked, None, W.map
+
+    def _photo_support(self, t):
+        """Target t's support fraction of the frame being tracked (None: chain_photo_weights is off); the first call of a frame
+        waits for the counts' copy -- it was enqueued before the planar stage's own read, so there is normally nothing to wait
+        for -- and the wait is added to host_wait_s."""
+        W = self._pw
+        if W is None:
+            return None
+        if W.fractions is None:
+            import time
+            t0 = time.perf_counter()
+            W.event.synchronize()
+            waited = time.perf_counter() - t0
+            self.host_wait_s += waited
+            self.photo_weights_wait_s += waited
+            counts = W.host.numpy()
+            W.fractions = [float(counts[k]) / n if n else 0.0 for k, n in enumerate(W.n_mask)]
+        return W.fractions[t]
+
+    def _low_support(self, t):
+        f = self._photo_support(t)
+        return f is not None and f < self._photo_w["min_support"]
+
     def _wants_weights(self):
         return self.chain_weights and (self._fused is None or self._fused.get("weighted", True))
 
@@ -169,6 +263,9 @@ class WOFTChained(YAOFTrackerSingleControl):
         self.multi = self._new_multi()
         self._init_multi(img)
         self._photo_frame_of = (None, None)
+        if self._photo_w is not None:
+            inside = self._template_mask_u8 != 0
+            self._init_photo_weights(inside.to(torch.int32).contiguous(), [int(inside.sum())])
         # the chains read every pixel of every flow: no weight region, no flow region, no deferred weights
         if hasattr(self.flower, "pin_weight_region"):
             self.flower.pin_weight_region(None)
@@ -194,6 +291,7 @@ class WOFTChained(YAOFTrackerSingleControl):
     def track(self, input_img, debug=False, img_identifier=None):
         self._n_tracked += 1
         out = self.multi.track(input_img)                            # (uploads the frame: the ring keeps a copy of its own)
+        self._photo_weights_launch(out)
         return self._planar_stage(self, out, input_img, img_identifier)
 
     def _planar_stage(self, state, out, input_img, img_identifier):
@@ -250,15 +348,24 @@ class WOFTChained(YAOFTrackerSingleControl):
         H_cur2init = fit.H if usable else state.prev_H2init
         if self._photo is not None and not state.lost:
             meta.H_flow_cur2init = H_cur2init.copy()                 # (the correspondence fit's pose, un-refined)
+            target = getattr(state, "_target_index", 0)
+            support = self._photo_support(target)                    # (None: chain_photo_weights is off)
+            low = self._low_support(target)
             if photo is None:
                 W0 = self._photo_start(H_cur2init)
                 photo = (None, None)
-                if W0 is not None:
-                    photo = state._photo_template.refine(self._photo_frame(input_img), W0, **self._photo_options())
+                if W0 is not None and not low:
+                    photo = state._photo_template.refine(self._photo_frame(input_img), W0, weights=self.photo_weight_map,
+                                                         **self._photo_options())
                     self.host_wait_s += photo[1].host_wait_s
             meta.photo = None                                        # (no start: the pose stays what the fit gave)
-            if photo[1] is not None:
+            if low and self._photo_start(H_cur2init) is not None:    # (too little of the mask is visible: the fit's pose stays)
+                meta.photo = SimpleNamespace(status="LOW_SUPPORT", best=-1, iterates=0, rms_before=float("nan"),
+                                             rms_after=float("nan"), n_valid=0, gain=1.0, bias=0.0, support=support)
+            elif photo[1] is not None:
                 H_cur2init = self._photo_result(H_cur2init, photo[0], photo[1], meta)
+                if support is not None:
+                    meta.photo.support = support
         self.prev_img, self.prev_img_identifier = input_img, img_identifier
         self._set_pose(H_cur2init.copy(), good=not state.lost, state=state)
         meta.lost, meta.N_lost, meta.global_H_success = state.lost, state.N_lost, success
@@ -358,10 +465,11 @@ class WOFTChainedMulti(WOFTChained):
         super().init(img, masks[0], img_identifier)                  # (template, provider pins, the dense tracker: shared)
         eye = self.prev_H2init
         self._targets = [SimpleNamespace(lost=False, N_lost=0, prev_H2init=eye.copy(), last_good_H2init=eye.copy(),
-                                         _announced=t in self._announced_targets, n_kept=None,
+                                         _announced=t in self._announced_targets, n_kept=None, _target_index=t,
                                          _template_mask_u8=torch.from_numpy((m > 0).astype(np.uint8) * 255).to(self.device))
                          for t, m in enumerate(masks)]
         self._tbits = torch.from_numpy(pack_target_bits(masks).view(np.int32)).to(self.device)
+        self._init_photo_weights(self._tbits, [int(np.count_nonzero(m)) for m in masks])
         if self._photo is not None:
             from .photo import PhotoTemplate, PhotoTemplateMulti
             image, self._photo_template, self._photo_multi = self._photo_image(self.template_img), None, None
@@ -377,12 +485,13 @@ class WOFTChainedMulti(WOFTChained):
         photos = [None] * len(rows)
         if self._photo is not None:
             starts = [self._photo_start(fit.H) if self._verdict(fit, kept)[1] else None for fit, _, kept, _ in rows]
-            active = [W0 is not None for W0 in starts]
+            # (with chain_photo_weights a target with too little visible support is passed as inactive)
+            active = [W0 is not None and not self._low_support(t) for t, W0 in enumerate(starts)]
             photos = [(None, None)] * len(rows)
             if any(active):
                 Ws, infos = self._photo_multi.refine(self._photo_frame(input_img),
                                                      np.stack([W0 if W0 is not None else np.eye(3) for W0 in starts]),
-                                                     active=active, **self._photo_options())
+                                                     active=active, weights=self.photo_weight_map, **self._photo_options())
                 waits = [i.host_wait_s for i in infos if i is not None]
                 self.host_wait_s += max(waits) if waits else 0.0
                 photos = [(W, info) if info is not None else (None, None) for W, info in zip(Ws, infos)]
@@ -397,6 +506,7 @@ class WOFTChainedMulti(WOFTChained):
             raise RuntimeError("WOFTChainedMulti.track() before init()")
         self._n_tracked += 1
         out = self.multi.track(input_img)                            # (the one dense track every target shares)
+        self._photo_weights_launch(out)
         if self._route == "loop":
             res = [self._planar_stage(T, out, input_img, img_identifier) for T in self._targets]
         else:

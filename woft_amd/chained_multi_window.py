@@ -91,6 +91,7 @@ class WOFTChainedMultiWindow(WOFTChainedMulti, WOFTChainedWindow):
             raise RuntimeError("WOFTChainedMultiWindow.track() before init()")
         self._n_tracked += 1
         out = self.multi.track(input_img)                            # (the one dense track on the union window)
+        self._photo_weights_launch(out)                              # (R0's planes placed in the full template frame)
         if self._route == "loop":
             res = [self._planar_stage(T, out, input_img, img_identifier) for T in self._targets]
         else:

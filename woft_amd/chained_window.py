@@ -260,6 +260,7 @@ class WOFTChainedWindow(WOFTChained):
                 self.last_good_H2init = _EYE.copy()
             prewarp_H = self.last_good_H2init
         out = self.multi.track(input_img, prewarp_H=prewarp_H)           # (uploads the frame: the ring keeps crops of its own)
+        self._photo_weights_launch(out)                                  # (R0's planes placed in the full template frame)
         H_cur2init, meta = self._planar_stage(self, out, input_img, img_identifier)
         self._follow()
         meta.chain_window = self.chain_window

@@ -1594,3 +1594,24 @@ def photo_refine_multi(tmpl, bits, weights, frame, boxes, stride, W0, n_need, ac
     check(_lib.load().woft_photo_refine_multi(*head, int(stride), Wc, _i32s(n_need, K), _i32s(active, K), int(iters),
                                               int(bool(gain_bias)), _photo_huber(huber_k), float(eps), ptr(ws), ptr(result),
                                               stream_ptr()), "woft_photo_refine_multi")
+
+
+PHOTO_WEIGHTS_MAX_RADIUS = 4                        # WOFT_PHOTO_WEIGHTS_MAX_RADIUS
+PHOTO_WEIGHT_MODES = ("gate", "soft")               # woft_photo_weights' mode 0 / 1
+
+
+def photo_weights(cost, vis, rect, template_hw, bits, n_targets, vis_thr, mode, radius, out_map, support):
+    """woft_photo_weights: the fold planes cost, vis (fp32 device tensors of rows * cols elements) on rect = (ry, rx, rows, cols) of a
+    template of template_hw = (h, w) -> out_map ((h, w) fp32, every entry written) and support (n_targets int32; None with
+    n_targets = 0, and then bits may be None).  bits: the (h, w) int32 view of the targets' bit plane.  mode: 0 gate, 1 soft."""
+    ry, rx, rows, cols = (int(v) for v in rect)
+    h, w = (int(v) for v in template_hw)
+    assert all(_f32c(t) and t.numel() == rows * cols for t in (cost, vis))
+    assert _f32c(out_map, h, w)
+    n_targets = int(n_targets)
+    if n_targets > 0:
+        assert bits.dtype == torch.int32 and tuple(bits.shape) == (h, w) and bits.is_contiguous() and bits.is_cuda
+        assert support.dtype == torch.int32 and support.numel() >= n_targets and support.is_contiguous() and support.is_cuda
+    check(_lib.load().woft_photo_weights(ptr(cost), ptr(vis), rows, cols, ry, rx, h, w, ptr(bits) if n_targets > 0 else None,
+                                         n_targets, float(vis_thr), int(mode), int(radius), ptr(out_map),
+                                         ptr(support) if n_targets > 0 else None, stream_ptr()), "woft_photo_weights")

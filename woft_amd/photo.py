@@ -12,6 +12,9 @@ host decision inside the loop.
 
     pm = PhotoTemplateMulti(template, [mask_a, mask_b])   # K targets of one template
     Hs, infos = pm.refine(frame, Hs_t2f, active=[True, True])     # one batched call and one read whatever K
+
+    wmap, support = photo_weight_map(cost, vis, (h, w), bits=pm.bits, n_targets=pm.K)   # a fold result as weights (section 30)
+    Hs, infos = pm.refine(frame, Hs_t2f, weights=wmap)                                   # ... of this call alone
 """
 import math
 import time
@@ -86,6 +89,22 @@ def _device_weights(weights, h, w, device):
     return wt.to(device).contiguous()
 
 
+def _call_weights(own, weights, h, w, device):
+    """The weight map of one call: `own` (the constructor's) when `weights` is None, else the per-call (h, w) float32 map.  A numpy
+    map is checked as the constructor checks its own; a device tensor is checked for dtype, shape and device only -- scanning its
+    values would synchronise the stream the map was just produced on (photo_weight_map's output is finite and >= 0 by
+    construction)."""
+    if weights is None:
+        return own
+    if not isinstance(weights, torch.Tensor) or not weights.is_cuda:
+        return _device_weights(weights, h, w, device)
+    if tuple(weights.shape) != (h, w) or weights.dtype != torch.float32:
+        raise ValueError(f"weights: float32 of shape {(h, w)} is expected, got {weights.dtype} {tuple(weights.shape)}")
+    if weights.device != device:
+        raise ValueError(f"weights: a map on {device} is expected, got one on {weights.device}")
+    return weights.contiguous()
+
+
 def _pixel_set(inside, h, w, stride):
     """A boolean mask -> (box (x0, y0, x1, y1) inclusive, n_set, centre, scale) of its pixel set; (None, 0, None, None) when the
     mask is empty."""
@@ -140,21 +159,24 @@ class PhotoTemplate:
     def _launchable(self, nu):
         return self.box is not None and self.n_set >= nu and self.h >= 3 and self.w >= 3
 
-    def normal_equations(self, frame, H_t2f, gain=1.0, bias=0.0, gain_bias=True, huber_k=None):
+    def normal_equations(self, frame, H_t2f, gain=1.0, bias=0.0, gain_bias=True, huber_k=None, weights=None):
         """One evaluation at the state (H_t2f, gain, bias in grey levels) -> (G (nu, nu), r (nu,), cost in grey levels, n_valid),
-        float64 numpy; nu = 10 with gain_bias, else 8."""
+        float64 numpy; nu = 10 with gain_bias, else 8.  weights: as refine's."""
         _, gain_bias, huber_k, _, _ = check_options(0, gain_bias, huber_k, 0.5, 0.0)
         nu = 10 if gain_bias else 8
         if not self._launchable(nu):
             raise ValueError(f"the pixel set holds {self.n_set} pixels: fewer than the {nu} unknowns")
         frame = _device_image(frame, "frame")
         out = torch.empty(ops.PHOTO_NACC, dtype=torch.float64, device=self.template.device)
-        ops.photo_eval(self.template, self.mask, self.weights, frame, self.box, self.stride, _h33(H_t2f, "H_t2f"), float(gain),
+        ops.photo_eval(self.template, self.mask, _call_weights(self.weights, weights, self.h, self.w, self.template.device), frame, self.box, self.stride, _h33(H_t2f, "H_t2f"), float(gain),
                        3.0 * float(bias), gain_bias, huber_k, out)
         return unpack_sums(out.cpu().numpy(), nu)
 
-    def refine(self, frame, H_t2f, iters=10, gain_bias=True, huber_k=None, min_valid=0.5, eps=1e-3):
+    def refine(self, frame, H_t2f, iters=10, gain_bias=True, huber_k=None, min_valid=0.5, eps=1e-3, weights=None):
         """Refine H_t2f (3x3, template pixels -> frame pixels) against `frame` ((hf, wf, 3) uint8 or float32, numpy or device).
+        weights: an (h, w) float32 map >= 0 that replaces the constructor's for this call (None: the constructor's).  A numpy map
+        is checked as the constructor checks its own; a device tensor for dtype, shape and device only: scanning its values would
+        synchronise.
         -> (H, info): H the best iterate's homography (h33 = 1; the input unchanged when no iterate was eligible), info with
         status ('CONVERGED', 'MAX_ITERS', 'TOO_FEW', 'SINGULAR', 'NONFINITE'), best (-1: none), the per-iterate arrays H_iter
         (k, 3, 3), gain, bias, cost (grey levels), n_valid, step (frame pixels; NaN where no step was taken), rms_before,
@@ -162,6 +184,7 @@ class PhotoTemplate:
         iters, gain_bias, huber_k, min_valid, eps = check_options(iters, gain_bias, huber_k, min_valid, eps)
         H0 = _h33(H_t2f, "H_t2f")
         nu = 10 if gain_bias else 8
+        weights = _call_weights(self.weights, weights, self.h, self.w, self.template.device)
         if not self._launchable(nu):                 # (an empty mask, or fewer pixels than unknowns: no launch)
             return H0.copy(), _info("TOO_FEW", -1, np.zeros((0, ops.PHOTO_REC)), self.n_set, 0.0)
         frame = _device_image(frame, "frame")
@@ -169,7 +192,7 @@ class PhotoTemplate:
         if res is None:
             res = self._results[iters] = _Result(iters, self.template.device)
         n_need = max(nu, int(math.ceil(min_valid * self.n_set)))
-        ops.photo_refine(self.template, self.mask, self.weights, frame, self.box, self.stride, H0, iters, gain_bias, huber_k,
+        ops.photo_refine(self.template, self.mask, weights, frame, self.box, self.stride, H0, iters, gain_bias, huber_k,
                          n_need, eps, res.dev)
         waited = res.read()
         blk = res.host.numpy()
@@ -233,9 +256,10 @@ class PhotoTemplateMulti:
         active = [bool(a) for a in active]
         return active, [a and self._launchable(t, nu) for t, a in enumerate(active)]
 
-    def normal_equations(self, frame, Hs, gains=None, biases=None, gain_bias=True, huber_k=None):
+    def normal_equations(self, frame, Hs, gains=None, biases=None, gain_bias=True, huber_k=None, weights=None):
         """One evaluation per target at the states (Hs (K, 3, 3), gains, biases in grey levels; None: 1 and 0) -> K tuples
-        (G, r, cost, n_valid) as PhotoTemplate.normal_equations returns them."""
+        (G, r, cost, n_valid) as PhotoTemplate.normal_equations returns them.  weights: as PhotoTemplate.refine's, shared by the
+        targets."""
         _, gain_bias, huber_k, _, _ = check_options(0, gain_bias, huber_k, 0.5, 0.0)
         nu = 10 if gain_bias else 8
         Hs = self._states(Hs)
@@ -246,18 +270,21 @@ class PhotoTemplateMulti:
         biases = [0.0] * self.K if biases is None else [3.0 * float(b) for b in biases]
         frame = _device_image(frame, "frame")
         out = torch.empty((self.K, ops.PHOTO_NACC), dtype=torch.float64, device=self.template.device)
-        ops.photo_eval_multi(self.template, self.bits, self.weights, frame, self._call_boxes, self.stride, Hs, gains, biases,
+        ops.photo_eval_multi(self.template, self.bits, _call_weights(self.weights, weights, self.h, self.w, self.template.device), frame, self._call_boxes, self.stride, Hs, gains, biases,
                              [1] * self.K, gain_bias, huber_k, out)
         return [unpack_sums(row, nu) for row in out.cpu().numpy()]
 
-    def refine(self, frame, Hs, active=None, iters=10, gain_bias=True, huber_k=None, min_valid=0.5, eps=1e-3):
+    def refine(self, frame, Hs, active=None, iters=10, gain_bias=True, huber_k=None, min_valid=0.5, eps=1e-3, weights=None):
         """Refine the K poses Hs (K, 3, 3; template pixels -> frame pixels) against `frame` in ONE woft_photo_refine_multi call and
         ONE read -> (Hs_out (K, 3, 3) float64, infos): infos[t] is PhotoTemplate.refine's namespace; None and the input back for a
         target with active[t] false; 'TOO_FEW' with best = -1 and the input back, without taking part in the launch, for a target
-        whose pixel set is empty or smaller than the unknowns.  No launch and no read when no target takes part."""
+        whose pixel set is empty or smaller than the unknowns.  No launch and no read when no target takes part.  weights: one
+        (h, w) float32 map for this call, shared by the targets, checked as PhotoTemplate.refine checks its own; target t then gets
+        the bytes of PhotoTemplate.refine(..., weights=weights) on its mask."""
         iters, gain_bias, huber_k, min_valid, eps = check_options(iters, gain_bias, huber_k, min_valid, eps)
         Hs = self._states(Hs)
         nu = 10 if gain_bias else 8
+        weights = _call_weights(self.weights, weights, self.h, self.w, self.template.device)
         active, takes_part = self._active(active, nu)
         out = Hs.copy()
         infos = [None if not a else _info("TOO_FEW", -1, np.zeros((0, ops.PHOTO_REC)), self.n_sets[t], 0.0)
@@ -269,7 +296,7 @@ class PhotoTemplateMulti:
         if res is None:
             res = self._results[iters] = _Result(iters, self.template.device, self.K)
         n_need = [max(nu, int(math.ceil(min_valid * n))) for n in self.n_sets]
-        ops.photo_refine_multi(self.template, self.bits, self.weights, frame, self._call_boxes, self.stride, Hs, n_need,
+        ops.photo_refine_multi(self.template, self.bits, weights, frame, self._call_boxes, self.stride, Hs, n_need,
                                [int(a) for a in takes_part], iters, gain_bias, huber_k, eps, res.dev)
         waited = res.read()
         blocks = res.host.numpy().reshape(self.K, ops.PHOTO_REC * (iters + 2))
@@ -305,5 +332,71 @@ def _info(status, best, rec, n_set, waited):
 
 
 def refine_homography(template, mask, frame, H_t2f, stride=1, weights=None, **kw):
-    """One-shot form: PhotoTemplate(template, mask, stride, weights).refine(frame, H_t2f, **kw)."""
+    """One-shot form: PhotoTemplate(template, mask, stride).refine(frame, H_t2f, weights=weights, **kw) -- a device map is passed
+    through as refine takes it (dtype, shape and device checked, its values not read)."""
+    if isinstance(weights, torch.Tensor) and weights.is_cuda:
+        return PhotoTemplate(template, mask, stride=stride).refine(frame, H_t2f, weights=weights, **kw)
     return PhotoTemplate(template, mask, stride=stride, weights=weights).refine(frame, H_t2f, **kw)
+
+
+def photo_weight_map(cost, vis, template_hw, rect=None, bits=None, n_targets=0, vis_thr=0.5, mode="gate", erode=1, out=None):
+    """A fold result as the refinement's weight map (woft_photo_weights) -> (map (h, w) float32, support
+    (n_targets,) int32 | None), both on the device, nothing read back.
+
+    cost, vis:    the fold's planes (what MultiFlowTracker.track() returns, or chain_fold), fp32 tensors of rows * cols elements.
+    template_hw:  (h, w) of the template the map is laid on.
+    rect:         (ry, rx, rows, cols), where the planes lie in the template; None: origin (0, 0) and the planes' own 2-D size.
+    bits:         the targets' bit plane (pack_target_bits' layout: an (h, w) uint32 numpy array, or its int32 device view) and
+                  n_targets 1 .. 32; n_targets = 0: no support is computed and None is returned for it.
+    vis_thr:      a pixel passes where its cost is finite and its vis >= vis_thr (equality passes, a NaN fails).
+    mode:         'gate' -> 1.0 where the pixel passes; 'soft' -> exp(-cost) * vis in fp32 (0 where that is not finite or not > 0).
+    erode:        the radius 0 .. 4 of the minimum over (2 erode + 1)^2 neighbours; neighbours outside the template are ignored,
+                  neighbours inside the template but outside rect count as 0.
+    out:          (map, support) of an earlier call of the same sizes, reused.
+    support[t] counts the template pixels in target t whose map value is > 0: integer sums, so two calls give equal bytes."""
+    h, w = (int(v) for v in template_hw)
+    if not isinstance(cost, torch.Tensor) or not isinstance(vis, torch.Tensor):
+        raise TypeError("photo_weight_map: cost and vis are tensors")
+    if rect is None:
+        shape = tuple(cost.shape[-2:]) if cost.dim() >= 2 else None
+        if shape is None or cost.numel() != shape[0] * shape[1]:
+            raise ValueError("photo_weight_map: without rect the cost plane must be (rows, cols) or (1, rows, cols)")
+        rect = (0, 0) + shape
+    try:
+        ry, rx, rows, cols = (int(v) for v in rect)
+    except (TypeError, ValueError):
+        raise ValueError(f"photo_weight_map: rect is (ry, rx, rows, cols), got {rect!r}") from None
+    if h < 1 or w < 1 or rows < 1 or cols < 1 or ry < 0 or rx < 0 or ry + rows > h or rx + cols > w:
+        raise ValueError(f"photo_weight_map: rect {(ry, rx, rows, cols)} does not lie inside the template {(h, w)}")
+    if cost.numel() != rows * cols or vis.numel() != rows * cols:
+        raise ValueError(f"photo_weight_map: cost and vis must hold {rows} x {cols} elements")
+    if mode not in ops.PHOTO_WEIGHT_MODES:
+        raise ValueError(f"photo_weight_map: mode {mode!r} is not one of {ops.PHOTO_WEIGHT_MODES}")
+    if isinstance(erode, bool) or not isinstance(erode, (int, np.integer)) or not 0 <= erode <= ops.PHOTO_WEIGHTS_MAX_RADIUS:
+        raise ValueError(f"photo_weight_map: erode {erode!r} is not an integer in 0 .. {ops.PHOTO_WEIGHTS_MAX_RADIUS}")
+    vis_thr = float(vis_thr)
+    if not (0.0 <= vis_thr <= 1.0):
+        raise ValueError(f"photo_weight_map: vis_thr must be in [0, 1], got {vis_thr!r}")
+    if isinstance(n_targets, bool) or not isinstance(n_targets, (int, np.integer)) or not 0 <= n_targets <= ops.MULTI_MAX_TARGETS:
+        raise ValueError(f"photo_weight_map: n_targets {n_targets!r} is not an integer in 0 .. {ops.MULTI_MAX_TARGETS}")
+    n_targets = int(n_targets)
+    if n_targets > 0 and bits is None:
+        raise ValueError("photo_weight_map: n_targets > 0 needs the targets' bit plane")
+    dev32 = lambda t: t.detach().to("cuda", torch.float32).contiguous()
+    cost, vis = dev32(cost), dev32(vis)
+    if n_targets > 0:
+        if isinstance(bits, np.ndarray):
+            if bits.dtype != np.uint32:
+                raise ValueError(f"photo_weight_map: a numpy bit plane is uint32 (pack_target_bits), got {bits.dtype}")
+            bits = torch.from_numpy(np.ascontiguousarray(bits).view(np.int32))
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or tuple(bits.shape) != (h, w):
+            raise ValueError(f"photo_weight_map: bits must be the {(h, w)} bit plane (uint32 numpy or its int32 tensor view)")
+        bits = bits.to(cost.device).contiguous()
+    if out is not None:
+        wmap, support = out
+    else:
+        wmap = torch.empty((h, w), dtype=torch.float32, device=cost.device)
+        support = torch.empty(n_targets, dtype=torch.int32, device=cost.device) if n_targets > 0 else None
+    ops.photo_weights(cost, vis, (ry, rx, rows, cols), (h, w), bits, n_targets, vis_thr, ops.PHOTO_WEIGHT_MODES.index(mode), int(erode),
+                      wmap, support)
+    return wmap, support

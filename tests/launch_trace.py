@@ -347,19 +347,12 @@ def _chained_scenario(multi, **kw):
     def run(patch):
         import chained_multi_util as U
         patch.setenv("WOFT_FUSED", "1")
-        keep = []
-
-        class Keeping(U.AffineProvider):
-            def compute_flow(self, *a, **k):
-                out = super().compute_flow(*a, **k)
-                keep.append(out)
-                return out
         sub = kw.get("subsampler_fn", True)
         conf = U.stub_config(multi, estimator=kw.get("estimator"))
-        conf.flow_config.of_class = lambda fc: Keeping(fc)
         if sub is None:
             conf.subsampler_fn = None
         trk = conf.tracker_class(conf)
+        keep = _keep_flows(trk.flower)
         frame0, frames = U.stub_frames()
         masks = U.stub_masks()
         trk.init(frame0, masks if multi else masks[0])
@@ -374,6 +367,54 @@ def _chained_scenario(multi, **kw):
 def _ransac():
     from woft_amd import presets
     return presets.estimator_ransac(10000, 3.0, 0.995)
+
+
+def _keep_flows(provider):
+    """The stub provider's flows stay alive for the scenario, as the frames do -> the list that holds them."""
+    keep, inner = [], provider.compute_flow
+
+    def compute_flow(*a, **k):
+        out = inner(*a, **k)
+        keep.append(out)
+        return out
+    provider.compute_flow = compute_flow
+    return keep
+
+
+def _windowed(trk, frames):
+    """Three frames of a windowed chained tracker whose R0 is a real window, not the frame."""
+    assert trk.multi.rect0[2:] != tuple(frames[0].shape[:2]) and trk.multi.rect0[:2] != (0, 0), trk.multi.rect0
+    keep = _keep_flows(trk.flower)
+    outs = _tracked(trk, frames[:3])
+    del keep[:]
+    return outs
+
+
+def _chained_window_scenario(patch):
+    """WOFTChainedWindow, chain_prewarp on, on the stub provider, frames and mask of tests/test_chained_window_gpu.py (96 x 128,
+    deltas (None, 1, 2, 4)): every chain unreliable, so the pre-warped direct candidate carries the pose."""
+    import test_chained_window_gpu as W
+    from pytracking.utils.config import load_config
+    patch.setenv("WOFT_FUSED", "1")
+    conf = load_config(ROOT / "pytracking" / "configs" / "WOFT_chained_window.py")
+    conf.flow_config.of_class = lambda fc: W._MotionProvider(fc, "chained")
+    conf.chain_deltas, conf.chain_window_min, conf.chain_window_quantum, conf.chain_prewarp = W.S_DELTAS, 32, 16, True
+    assert conf.search_window_margin
+    trk = conf.tracker_class(conf)
+    trk.flower.tracker = trk
+    trk.init(W._stub_frame(0), W._stub_mask())
+    return _windowed(trk, [W._stub_frame(t) for t in range(1, 4)])
+
+
+def _chained_multi_window_scenario(route, **kw):
+    """WOFTChainedMultiWindow on the two-motion stub provider and the three masks of tests/test_chained_multi_window_gpu.py."""
+    def run(patch):
+        import test_chained_multi_window_gpu as M
+        patch.setenv("WOFT_FUSED", "1")
+        trk = M._two_motion_tracker([M._rect_mask(r) for r in (M.MASK_A, M.MASK_B, M.MASK_C)], **kw)
+        assert trk._route == route and trk._margin, (trk._route, trk._margin)
+        return _windowed(trk, [M.W._stub_frame(t) for t in range(1, 4)])
+    return _private_pool(run)
 
 
 SCENARIOS = {
@@ -403,6 +444,10 @@ SCENARIOS = {
     "chained_multi_batched": _chained_scenario(True, route="batched"),
     "chained_multi_select": lambda patch: _chained_scenario(True, route="select", estimator=_ransac())(patch),
     "chained_multi_loop": _chained_scenario(True, route="loop", subsampler_fn=None),
+    "chained_window": _private_pool(_chained_window_scenario),
+    "chained_multi_window_batched": _chained_multi_window_scenario("batched"),
+    "chained_multi_window_select": lambda patch: _chained_multi_window_scenario("select", estimator=_ransac())(patch),
+    "chained_multi_window_loop": _chained_multi_window_scenario("loop", subsampler_fn=None),
 }
 
 

@@ -19,12 +19,13 @@ K planar targets on one dense track: the fold is shared, 
 (woft_chain_tc_multi, woft_tc_select_multi, woft_hfit_batched, woft_inlier_frac_batched, one read).
 """
 import logging
+import time
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, window
 from .config import config_get, config_set
 from .multiflow import MultiFlowTracker, _check_constants, _dev32
 from .planar import BoundedCache, PlanarBuffers, decode, fit_and_judge
@@ -241,7 +242,6 @@ class WOFTChained(YAOFTrackerSingleControl):
         if W is None:
             return None
         if W.fractions is None:
-            import time
             t0 = time.perf_counter()
             W.event.synchronize()
             waited = time.perf_counter() - t0
@@ -290,25 +290,53 @@ class WOFTChained(YAOFTrackerSingleControl):
 
     def track(self, input_img, debug=False, img_identifier=None):
         self._n_tracked += 1
-        out = self.multi.track(input_img)                            # (uploads the frame: the ring keeps a copy of its own)
+        out = self.multi.track(input_img, **self._begin_frame())      # (uploads the frame: the ring keeps a copy of its own)
         self._photo_weights_launch(out)
-        return self._planar_stage(self, out, input_img, img_identifier)
+        H_cur2init, meta = self._planar_stage(self, out, input_img, img_identifier)
+        self._after_frame([meta])
+        return H_cur2init, meta
+
+    # ---- what a tracker on search windows overrides: three hooks, the stages below are written once --------------------------------
+    def _begin_frame(self):
+        """Whatever the tracker settles before the frame's dense track -> what that track is given beside the frame."""
+        return {}
+
+    def _after_frame(self, metas):
+        """After the frame's planar stage, with the meta of every target."""
+
+    def _planes(self, out, input_img, state=None):
+        """Where the planes of the fold result `out` lie, for the planar stage of `state` (None: of every target at once, on the bit
+        plane) -> SimpleNamespace(
+          origin:   None: whole frames, the stage goes through chain_tc / chain_tc_multi; else (y0, x0) of the planes' rectangle:
+                    chain_tc_window / chain_tc_multi_window, whose gate holds the in-frame rule;
+          frame_hw: the frame's size;  grid: the planes' size;
+          mask, mask_hw: the uint8 mask or the bit plane to read (_frame_mask), laid out on the planes, and its size;
+          bounds:   whether the selection checks the landings against mask_hw itself;
+          crop_box: None, or the box the fit is taken back to frame coordinates from (H_undo_crop))."""
+        hw = (int(input_img.shape[0]), int(input_img.shape[1]))
+        return SimpleNamespace(origin=None, frame_hw=hw, grid=(int(out.flow.shape[1]), int(out.flow.shape[2])),
+                               mask=self._frame_mask(state), mask_hw=hw, bounds=True, crop_box=None)
+
+    def _frame_mask(self, state):
+        return state._template_mask_u8
 
     def _planar_stage(self, state, out, input_img, img_identifier):
         """The fold result of one frame -> (H_cur2init, meta): correspondences, the fit, the update of `state` -- the holder of lost,
-        N_lost, prev_H2init, last_good_H2init, _announced, n_kept, _template_mask_u8: the tracker, or a target of WOFTChainedMulti."""
-        Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
-        gh, gw = int(out.flow.shape[1]), int(out.flow.shape[2])
-        mask = state._template_mask_u8
-        dst, w, ok, hist = self._tc.put((gh, gw), ops.chain_tc(out.flow, out.cost, out.vis, out.sel, mask, self.chain_vis_thr,
-                                                               want_w=self._wants_weights(), mask_hw=(Hh, Ww),
-                                                               out=self._tc.get((gh, gw))))
-        src_xy = None if self._fused is not None else self._source_grid(gh, gw)
+        N_lost, prev_H2init, last_good_H2init, _announced, n_kept and the mask _planes() names: the tracker, or a target of
+        WOFTChainedMulti."""
+        P = self._planes(out, input_img, state)
+        fold = (out.flow, out.cost, out.vis, out.sel, P.mask, self.chain_vis_thr)
+        kw = dict(want_w=self._wants_weights(), mask_hw=P.mask_hw, out=self._tc.get(P.grid))
+        dst, w, ok, hist = self._tc.put(P.grid, ops.chain_tc(*fold, **kw) if P.origin is None
+                                        else ops.chain_tc_window(*fold, P.origin, P.frame_hw, **kw))
+        src_xy = None if self._fused is not None else self._source_grid(*P.grid)
         self.n_kept = None                                           # (the channel by which _solve reports the kept count)
         try:
-            fit = self._solve(src_xy, dst, w, (gh, gw), (Hh, Ww), mask, None, bounds=True, judge=True, vis=ok)
+            fit = self._solve(src_xy, dst, w, P.grid, P.mask_hw, P.mask, None, bounds=P.bounds, judge=True, vis=ok)
         except self._SOLVE_ERRORS:                                   # (too few correspondences for the estimator)
             fit = None
+        if fit is not None and P.crop_box is not None:
+            fit.H = window.H_undo_crop(P.crop_box, fit.H)
         state.n_kept = self.n_kept
         return self._finish(state, fit, hist.cpu().numpy().astype(np.int64), input_img, img_identifier)
 
@@ -479,6 +507,9 @@ class WOFTChainedMulti(WOFTChained):
             else:
                 self._photo_multi = PhotoTemplateMulti(image, [m > 0 for m in masks], stride=self._photo["stride"])
 
+    def _frame_mask(self, state):
+        return self._tbits if state is None else super()._frame_mask(state)     # (None: every target at once, the bit plane)
+
     def _finish_batched(self, rows, input_img, img_identifier):
         """_finish for every target of a batched planar stage's rows; with chain_photo_refine the targets that are not lost go
         through ONE PhotoTemplateMulti.refine call (one launch sequence and one read whatever K) first."""
@@ -503,32 +534,40 @@ class WOFTChainedMulti(WOFTChained):
 
     def track(self, input_img, debug=False, img_identifier=None):
         if not self._targets:
-            raise RuntimeError("WOFTChainedMulti.track() before init()")
+            raise RuntimeError(f"{type(self).__name__}.track() before init()")
         self._n_tracked += 1
-        out = self.multi.track(input_img)                            # (the one dense track every target shares)
+        out = self.multi.track(input_img, **self._begin_frame())      # (the one dense track every target shares)
         self._photo_weights_launch(out)
         if self._route == "loop":
             res = [self._planar_stage(T, out, input_img, img_identifier) for T in self._targets]
         else:
             res = self._finish_batched(self._planar_batched(out, input_img), input_img, img_identifier)
         self._announced_targets.update(t for t, T in enumerate(self._targets) if T._announced)
-        return np.stack([H for H, _ in res]), [meta for _, meta in res]
+        metas = [meta for _, meta in res]
+        self._after_frame(metas)
+        return np.stack([H for H, _ in res]), metas
 
     def _planar_batched(self, out, input_img):
         """The planar stage of every target on one fold result -> [(fit | None, selected, kept, histogram int64 numpy)] per
-        target.  chain_tc_multi's histograms land in the result block: one read."""
+        target, the fits in frame coordinates.  chain_tc_multi's histograms land in the result block: one read."""
         F, K = self._fused, len(self._targets)
-        Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
-        gh, gw = int(out.flow.shape[1]), int(out.flow.shape[2])
-        n_grid, cap, want_w = gh * gw, 1024, self._wants_weights()     # (these routes have a Sobol draw: at most 1024 selected)
+        P = self._planes(out, input_img)
+        n_grid, cap, want_w = P.grid[0] * P.grid[1], 1024, self._wants_weights()     # (these routes have a Sobol draw: at most 1024 selected)
         blk = (b := self._buffers.lookup((K, n_grid, cap), lambda: PlanarBuffers(F, K, n_grid, cap, self.device, True, True))).block
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
         tc = self._tc.lookup((K, n_grid), lambda: (new(2, n_grid), new(1, n_grid) if want_w else None, new(1, n_grid), blk.hist))
-        dst, w, ok, _ = ops.chain_tc_multi(out.flow, out.cost, out.vis, out.sel, self._tbits, K, self.chain_vis_thr, want_w=want_w,
-                                           mask_hw=(Hh, Ww), out=tc)
+        fold = (out.flow, out.cost, out.vis, out.sel, P.mask, K, self.chain_vis_thr)
+        kw = dict(want_w=want_w, mask_hw=P.mask_hw, out=tc)
+        dst, w, ok, _ = (ops.chain_tc_multi(*fold, **kw) if P.origin is None
+                         else ops.chain_tc_multi_window(*fold, P.origin, P.frame_hw, **kw))
         weighted = F.get("weighted", True)
-        ops.tc_select_multi(dst, w if weighted else None, self._tbits, K, Hh, Ww, True, F["sobol_u"], ok, self._vis_mode,
-                            self._vis_thr, b.ws, b.pa, b.pb, b.w, blk.count, grid=(gh, gw))
+        ops.tc_select_multi(dst, w if weighted else None, P.mask, K, *P.mask_hw, P.bounds, F["sobol_u"], ok, self._vis_mode,
+                            self._vis_thr, b.ws, b.pa, b.pb, b.w, blk.count, grid=P.grid)
         fit_and_judge(F, b, weighted)
         self.host_wait_s += blk.read()
-        return decode(blk.host.numpy(), K, F, True)
+        res = decode(blk.host.numpy(), K, F, True)
+        if P.crop_box is not None:
+            for fit, _, _, _ in res:
+                if fit is not None:
+                    fit.H = window.H_undo_crop(P.crop_box, fit.H)
+        return res

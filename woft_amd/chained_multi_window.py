@@ -15,7 +15,6 @@ from . import ops, window
 from .chained import WOFTChainedMulti
 from .chained_window import WOFTChainedWindow
 from .config import config_get
-from .planar import PlanarBuffers, decode, fit_and_judge
 
 _EYE = np.eye(3)
 
@@ -32,12 +31,14 @@ class WOFTChainedMultiWindow(WOFTChainedMulti, WOFTChainedWindow):
     WOFTChainedMulti's; meta.chain_window of every target, and the tracker's chain_window, is the one shared window.  With one mask
     the results are WOFTChainedWindow's (chain_prewarp off) byte for byte; with a falsy margin they are WOFTChainedMulti's.
 
-    The planar stage runs in R0's coordinates, by WOFTChainedMulti's routes:
+    track() and both planar stages are inherited unchanged: WOFTChainedWindow's hooks (_begin_frame, _after_frame, _planes) tell them
+    where the planes lie, and _after_frame calls the _follow below.  The planar stage runs in R0's coordinates, by WOFTChainedMulti's
+    routes:
       batched: chain_tc_multi_window, tc_select_multi without a bounds check on the cropped bit plane (the gate already holds the
           in-frame rule), hfit_batched, inlier_frac_batched, one pinned read of the one result block, H_undo_crop per target on the
           host where R0's origin is not (0, 0).
       select:  the same selection, then the RANSAC or TRS estimator per target.
-      loop:    WOFTChainedWindow's single-target stage per target, on the per-target uint8 mask crops.
+      loop:    the single-target stage per target, on the per-target uint8 mask crops.
     Launches and reads of the batched route do not depend on K: the planar block's read, plus at most one box read.
 
     Config keys: WOFTChainedWindow's (search_window_margin, chain_window_quantum, chain_window_min) and WOFTChainedMulti's.
@@ -85,47 +86,8 @@ class WOFTChainedMultiWindow(WOFTChainedMulti, WOFTChainedWindow):
         self.chain_window = R0
         self._R0_box = window.Box(R0[1], R0[0], R0[3], R0[2])
 
-    # ---- a frame ------------------------------------------------------------------------------------------------------------------
-    def track(self, input_img, debug=False, img_identifier=None):
-        if not self._targets:
-            raise RuntimeError("WOFTChainedMultiWindow.track() before init()")
-        self._n_tracked += 1
-        out = self.multi.track(input_img)                            # (the one dense track on the union window)
-        self._photo_weights_launch(out)                              # (R0's planes placed in the full template frame)
-        if self._route == "loop":
-            res = [self._planar_stage(T, out, input_img, img_identifier) for T in self._targets]
-        else:
-            res = self._finish_batched(self._planar_batched(out, input_img), input_img, img_identifier)
-        self._announced_targets.update(t for t, T in enumerate(self._targets) if T._announced)
-        self._follow()
-        for _, meta in res:
-            meta.chain_window = self.chain_window
-        return np.stack([H for H, _ in res]), [meta for _, meta in res]
-
-    def _planar_batched(self, out, input_img):
-        """WOFTChainedMulti's batched stage in R0's coordinates -> [(fit | None, selected, kept, histogram)] per target, the fits
-        in frame coordinates."""
-        F, K = self._fused, len(self._targets)
-        Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
-        y0, x0, gh, gw = out.rect
-        mh, mw = (int(v) for v in self._tbits_crop.shape)
-        n_grid, cap, want_w = gh * gw, 1024, self._wants_weights()     # (these routes have a Sobol draw: at most 1024 selected)
-        blk = (b := self._buffers.lookup((K, n_grid, cap), lambda: PlanarBuffers(F, K, n_grid, cap, self.device, True, True))).block
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)
-        tc = self._tc.lookup((K, n_grid), lambda: (new(2, n_grid), new(1, n_grid) if want_w else None, new(1, n_grid), blk.hist))
-        dst, w, ok, _ = ops.chain_tc_multi_window(out.flow, out.cost, out.vis, out.sel, self._tbits_crop, K, self.chain_vis_thr,
-                                                  (y0, x0), (Hh, Ww), want_w=want_w, mask_hw=(mh, mw), out=tc)
-        weighted = F.get("weighted", True)
-        ops.tc_select_multi(dst, w if weighted else None, self._tbits_crop, K, mh, mw, False, F["sobol_u"], ok, self._vis_mode,
-                            self._vis_thr, b.ws, b.pa, b.pb, b.w, blk.count, grid=(gh, gw))
-        fit_and_judge(F, b, weighted)
-        self.host_wait_s += blk.read()
-        res = decode(blk.host.numpy(), K, F, True)
-        if (y0, x0) != (0, 0):
-            for fit, _, _, _ in res:
-                if fit is not None:
-                    fit.H = window.H_undo_crop(self._R0_box, fit.H)
-        return res
+    def _window_mask(self, state):
+        return self._tbits_crop if state is None else super()._window_mask(state)     # (None: every target at once)
 
     # ---- the window of the frame just tracked -------------------------------------------------------------------------------------
     def _follow(self):

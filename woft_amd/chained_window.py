@@ -24,19 +24,9 @@ import torch
 from . import ops, window
 from .chained import WOFTChained
 from .config import config_get
-from .multiflow import MAX_DELTA, MultiFlowTracker, _check_constants, _dev32
+from .multiflow import MultiFlowTracker, _chain_fold, _rect
 
 _EYE = np.eye(3)
-
-
-def _rect(rect, what):
-    try:
-        y0, x0, rows, cols = (int(v) for v in rect)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: a rectangle is (y0, x0, rows, cols), got {rect!r}") from None
-    if y0 < 0 or x0 < 0 or rows <= 0 or cols <= 0:
-        raise ValueError(f"{what}: origin >= 0 and sides >= 1 are expected, got {rect!r}")
-    return y0, x0, rows, cols
 
 
 def chain_fold_window(best, prev, step, k, template_rect, step_rect, post_H=None, vis_thr=0.5, unit_cost=1.0):
@@ -49,36 +39,7 @@ def chain_fold_window(best, prev, step, k, template_rect, step_rect, post_H=None
     planes, and a q outside the step rectangle makes the candidate invalid.  post_H (3 x 3, optional): the candidate's landing
     pixel + flow is mapped through it in fp64 before the flow is stored (the inverse of a pre-warp of frame t); a landing with a
     non-positive denominator is invalid.  Everything else -- best, prev, step, k, the key, ties, host tensors -- as chain_fold."""
-    vis_thr, unit_cost = _check_constants(vis_thr, unit_cost)
-    k = int(k)
-    if not 0 <= k <= MAX_DELTA:
-        raise ValueError(f"chain_fold_window: k must be in [0, {MAX_DELTA}], got {k}")
-    ty0, tx0, th, tw = _rect(template_rect, "template_rect")
-    sy0, sx0, sh, sw = _rect(step_rect, "step_rect")
-    step = tuple(step) if isinstance(step, (tuple, list)) else (step,)
-    if not 1 <= len(step) <= 3:
-        raise ValueError("chain_fold_window: step is (flow,), (flow, wlogit) or (flow, wlogit, mlogit)")
-    sflow = step[0]
-    if not isinstance(sflow, torch.Tensor) or tuple(sflow.shape) != (2, sh, sw):
-        raise ValueError(f"chain_fold_window: the step's flow must be a (2, {sh}, {sw}) tensor, the step rectangle's size")
-    n, ns = th * tw, sh * sw
-    f = _dev32(sflow, "step flow")
-    logits = [None if t is None else _dev32(t, "step logit", ns) for t in (step + (None, None))[1:3]]
-    if prev is not None:
-        if len(prev) != 3:
-            raise ValueError("chain_fold_window: prev is None or (flow, cost, vis)")
-        prev = (_dev32(prev[0], "prev flow", 2 * n).reshape(2, th, tw), _dev32(prev[1], "prev cost", n), _dev32(prev[2], "prev vis", n))
-    if best is not None:
-        if len(best) != 4 or best[3].dtype != torch.int32 or best[3].numel() != n:
-            raise ValueError("chain_fold_window: best is None or (flow, cost, vis, sel int32)")
-        # (clones: the fold is in place, the caller's tensors stay as they are)
-        best = (_dev32(best[0], "best flow", 2 * n).reshape(2, th, tw).clone(), _dev32(best[1], "best cost", n).clone(),
-                _dev32(best[2], "best vis", n).clone(), best[3].detach().to("cuda").contiguous().clone())
-    bf, bc, bv, bs = ops.flow_chain_fold_window(best, prev, f, logits[0], logits[1], k=k, template_rect=(ty0, tx0, th, tw),
-                                                step_rect=(sy0, sx0, sh, sw), post_H=post_H, vis_thr=vis_thr, unit_cost=unit_cost,
-                                                first=best is None)
-    dev = sflow.device
-    return bf.to(dev), bc.reshape(1, th, tw).to(dev), bv.reshape(1, th, tw).to(dev), bs.reshape(1, th, tw).to(dev)
+    return _chain_fold("chain_fold_window", best, prev, step, k, vis_thr, unit_cost, rects=(template_rect, step_rect), post_H=post_H)
 
 
 class WindowedMultiFlowTracker(MultiFlowTracker):
@@ -252,40 +213,33 @@ class WOFTChainedWindow(WOFTChained):
         self._R0_box = window.Box(R0[1], R0[0], R0[3], R0[2])
         self._mask_crop = ops.crop_u8(self._template_mask_u8, R0)
 
-    def track(self, input_img, debug=False, img_identifier=None):
-        self._n_tracked += 1
-        prewarp_H = None
-        if self.chain_prewarp:
-            if self.C.no_prewarp_after_N and self.N_lost > self.C.no_prewarp_after_N:
-                self.last_good_H2init = _EYE.copy()
-            prewarp_H = self.last_good_H2init
-        out = self.multi.track(input_img, prewarp_H=prewarp_H)           # (uploads the frame: the ring keeps crops of its own)
-        self._photo_weights_launch(out)                                  # (R0's planes placed in the full template frame)
-        H_cur2init, meta = self._planar_stage(self, out, input_img, img_identifier)
-        self._follow()
-        meta.chain_window = self.chain_window
-        return H_cur2init, meta
+    # ---- WOFTChained's hooks: track() and the planar stages are the whole-frame trackers' ----------------------------------------
+    def _begin_frame(self):
+        """Settles the pre-warp of the direct candidate (None: chain_prewarp is off): last_good_H2init, reset to the identity
+        here once the tracker has been lost for more than no_prewarp_after_N frames."""
+        if not self.chain_prewarp:
+            return dict(prewarp_H=None)
+        if self.C.no_prewarp_after_N and self.N_lost > self.C.no_prewarp_after_N:
+            self.last_good_H2init = _EYE.copy()
+        return dict(prewarp_H=self.last_good_H2init)
 
-    def _planar_stage(self, state, out, input_img, img_identifier):
-        """WOFTChained's stage in R0's coordinates: woft_chain_tc_window's gate holds the in-frame rule, so the selection checks
-        no bounds; the fit is un-cropped where R0 does not start at the frame's origin.  `state` also holds _mask_crop: the
-        tracker, or a target of WOFTChainedMultiWindow."""
-        Hh, Ww = int(input_img.shape[0]), int(input_img.shape[1])
+    def _after_frame(self, metas):
+        self._follow()
+        for meta in metas:
+            meta.chain_window = self.chain_window
+
+    def _planes(self, out, input_img, state=None):
+        """R0's planes: the stage runs in R0's coordinates on the mask cropped to R0 (_window_mask); woft_chain_tc_window's gate
+        holds the in-frame rule, so the selection checks no bounds; the fit is un-cropped where R0 does not start at the frame's
+        origin."""
         y0, x0, gh, gw = out.rect
-        mask, mask_hw = state._mask_crop, tuple(int(v) for v in state._mask_crop.shape)
-        dst, w, ok, hist = self._tc.put((gh, gw), ops.chain_tc_window(out.flow, out.cost, out.vis, out.sel, mask, self.chain_vis_thr,
-                                                                      (y0, x0), (Hh, Ww), want_w=self._wants_weights(),
-                                                                      mask_hw=mask_hw, out=self._tc.get((gh, gw))))
-        src_xy = None if self._fused is not None else self._source_grid(gh, gw)
-        self.n_kept = None                                           # (the channel by which _solve reports the kept count)
-        try:
-            fit = self._solve(src_xy, dst, w, (gh, gw), mask_hw, mask, None, bounds=False, judge=True, vis=ok)
-        except self._SOLVE_ERRORS:                                   # (too few correspondences for the estimator)
-            fit = None
-        if fit is not None and (y0, x0) != (0, 0):
-            fit.H = window.H_undo_crop(self._R0_box, fit.H)
-        state.n_kept = self.n_kept
-        return self._finish(state, fit, hist.cpu().numpy().astype(np.int64), input_img, img_identifier)
+        mask = self._window_mask(state)
+        return SimpleNamespace(origin=(y0, x0), frame_hw=(int(input_img.shape[0]), int(input_img.shape[1])), grid=(gh, gw), mask=mask,
+                               mask_hw=tuple(int(v) for v in mask.shape), bounds=False,
+                               crop_box=self._R0_box if (y0, x0) != (0, 0) else None)
+
+    def _window_mask(self, state):
+        return state._mask_crop                  # (`state` also holds its mask's crop to R0: the tracker, or a target)
 
     def _follow(self):
         """Name the window of the frame just tracked: the template mask carried by inv(prev_H2init), its box, chain_rect."""

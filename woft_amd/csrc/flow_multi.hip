@@ -4,7 +4,9 @@
 // Below it, the step from a fold result to the planar fit's correspondences (woft_chain_tc): streaming, no
 // gather, the 130 integer counters of its histogram in LDS.
 // Both have a form on rectangles (woft_flow_chain_fold_window, woft_chain_tc_window): flows on search windows;
-// so has the multi-target form of the second (woft_chain_tc_multi_window).
+// so has the multi-target form of the second (woft_chain_tc_multi_window).  Each piece of pixel work is
+// written once: flow_chain_fold_kernel<FORM> for the fold's forms, CHAIN_TC_PIXEL for both histogram schemes of the
+// second; fold_launch and outputs_alias hold what the entry points check alike.
 //
 // The sampler, its address rule and the launch geometry are those of flow_chain.hip (flow_sample.h): every tap address derives
 // from a clamped float, so no input, finite or not, addresses outside a plane; the pixel's own planes are read at (x, y) of the
@@ -16,27 +18,50 @@ namespace {
 // softplus(-l) = log(1 + exp(-l)) without overflow: for l < 0 it is -l + log(1 + exp(l))
 __device__ __forceinline__ float softplus_neg(float l) { return l < 0.f ? -l + log1pf(expf(l)) : log1pf(expf(-l)); }
 
-__global__ __launch_bounds__(FC_T) void flow_chain_fold_kernel(const float* __restrict__ prev_flow, const float* __restrict__ prev_cost,
-                                                               const float* __restrict__ prev_vis, const float* __restrict__ step_flow,
-                                                               const float* __restrict__ step_wlogit,
-                                                               const float* __restrict__ step_mlogit, int h, int w, float unit_cost,
-                                                               float vis_thr, int k, int first, float* __restrict__ best_flow,
-                                                               float* __restrict__ best_cost, float* __restrict__ best_vis,
-                                                               int32_t* __restrict__ best_sel) {
-    const int64_t plane = (int64_t)h * w;
+// The closing homography of the fold's POST form: nine host doubles passed by value (no device buffer, no workspace).
+struct PostH {
+    double h[9];
+};
+
+// The forms of the fold kernel.  FRAME (woft_flow_chain_fold): every plane is the [th][tw] frame, a pixel is
+// its own coordinate; the instantiation carries no origin arithmetic and no fp64.  RECT (woft_flow_chain_fold_window, DESIGN.md
+// section 26): the prev / best planes are the [th][tw] rectangle of the template with origin (tx0, ty0), the step planes the
+// [sh][sw] rectangle with origin (sx0, sy0) of frames s and t; flows stay displacements in frame coordinates.  q is formed in frame
+// coordinates, u = q - (step origin) is exact wherever the tap is valid, and the taps are those of u in the step planes: every
+// address still derives from a float clamped into [0, sw-1] x [0, sh-1].  RECT_POST: the candidate's landing also goes through a
+// homography in fp64 (den <= 0 or a non-finite image: invalid), one rounding back to the fp32 flow.
+enum class Fold { FRAME, RECT, RECT_POST };
+
+template <Fold FORM>
+__global__ __launch_bounds__(FC_T) void flow_chain_fold_kernel(
+    const float* __restrict__ prev_flow, const float* __restrict__ prev_cost, const float* __restrict__ prev_vis, int th, int tw, int ty0,
+    int tx0, const float* __restrict__ step_flow, const float* __restrict__ step_wlogit, const float* __restrict__ step_mlogit, int sh,
+    int sw, int sy0, int sx0, PostH H, float unit_cost, float vis_thr, int k, int first, float* __restrict__ best_flow,
+    float* __restrict__ best_cost, float* __restrict__ best_vis, int32_t* __restrict__ best_sel) {
+    constexpr bool RECT = FORM != Fold::FRAME;
+    const int64_t plane = (int64_t)th * tw, splane = RECT ? (int64_t)sh * sw : plane;
     const int x = (int)blockIdx.x * FC_TX + (int)threadIdx.x;
-    if (x >= w) return;
-    for (int y = (int)blockIdx.y * FC_TY + (int)threadIdx.y; y < h; y += (int)gridDim.y * FC_TY) {
-        const int64_t i = (int64_t)y * w + x;
+    if (x >= tw) return;
+    // the pixel in frame coordinates (px, py) and the step planes' origin; FRAME: the pixel's own (x, y), and no origin
+    [[maybe_unused]] float px = (float)x, ox = 0.f, oy = 0.f;
+    if constexpr (RECT) px = (float)(tx0 + x), ox = (float)sx0, oy = (float)sy0;
+    for (int y = (int)blockIdx.y * FC_TY + (int)threadIdx.y; y < th; y += (int)gridDim.y * FC_TY) {
+        const int64_t i = (int64_t)y * tw + x;
         // the stored result template -> s at this pixel (a null prev: s is the template itself)
         float pfx = 0.f, pfy = 0.f, pc = 0.f, pv = 1.f;
         if (prev_flow != nullptr) {
             pfx = prev_flow[i], pfy = prev_flow[plane + i];
             pc = prev_cost[i], pv = prev_vis[i];
         }
-        const float qx = (float)x + pfx, qy = (float)y + pfy;
-        const TapAt t = tap_at(h, w, qx, qy);
-        const float fx = pfx + tap_plane(step_flow, t), fy = pfy + tap_plane(step_flow + plane, t);
+        float py = (float)y;
+        if constexpr (RECT) py = (float)(ty0 + y);
+        const float qx = px + pfx, qy = py + pfy;
+        TapAt t;
+        if constexpr (RECT)
+            t = tap_at(sh, sw, qx - ox, qy - oy);
+        else
+            t = tap_at(th, tw, qx, qy);
+        float fx = pfx + tap_plane(step_flow, t), fy = pfy + tap_plane(step_flow + splane, t);
         // the logits are interpolated, then converted; a non-finite interpolated logit makes the candidate invalid
         bool ok = t.valid;
         float cost = pc + unit_cost, vis = pv;
@@ -50,68 +75,7 @@ __global__ __launch_bounds__(FC_T) void flow_chain_fold_kernel(const float* __re
             ok = ok && isfinite(m);
             vis = pv * sigmoidf_(m);
         }
-        ok = ok && isfinite(fx) && isfinite(fy) && isfinite(cost) && isfinite(vis);
-        // key (occluded, cost), lexicographic; an equal key keeps the earlier fold
-        bool replace = ok;
-        if (ok && !first && best_sel[i] >= 0) {
-            const float bc = best_cost[i];
-            const bool bocc = best_vis[i] < vis_thr, occ = vis < vis_thr;
-            replace = (bocc && !occ) || (bocc == occ && cost < bc);
-        }
-        if (replace) {
-            best_flow[i] = fx, best_flow[plane + i] = fy;
-            best_cost[i] = cost, best_vis[i] = vis, best_sel[i] = k;
-        } else if (first) {
-            best_flow[i] = NAN, best_flow[plane + i] = NAN;
-            best_cost[i] = INFINITY, best_vis[i] = 0.f, best_sel[i] = -1;
-        }
-    }
-}
-
-// The closing homography of flow_chain_fold_window_kernel: nine host doubles passed by value (no device buffer, no workspace).
-struct PostH {
-    double h[9];
-};
-
-// flow_chain_fold_kernel on two rectangles: the prev / best planes are the [th][tw] rectangle of the template
-// with origin (tx0, ty0), the step planes the [sh][sw] rectangle with origin (sx0, sy0) of frames s and t; flows stay displacements
-// in frame coordinates.  q is formed in frame coordinates, u = q - (step origin) is exact wherever the tap is valid, and the taps are
-// those of u in the step planes: every address still derives from a float clamped into [0, sw-1] x [0, sh-1].  POST: the candidate's
-// landing goes through a homography in fp64 (den <= 0 or a non-finite image: invalid), one rounding back to the fp32 flow.
-template <bool POST>
-__global__ __launch_bounds__(FC_T) void flow_chain_fold_window_kernel(
-    const float* __restrict__ prev_flow, const float* __restrict__ prev_cost, const float* __restrict__ prev_vis, int th, int tw, int ty0,
-    int tx0, const float* __restrict__ step_flow, const float* __restrict__ step_wlogit, const float* __restrict__ step_mlogit, int sh,
-    int sw, int sy0, int sx0, PostH H, float unit_cost, float vis_thr, int k, int first, float* __restrict__ best_flow,
-    float* __restrict__ best_cost, float* __restrict__ best_vis, int32_t* __restrict__ best_sel) {
-    const int64_t plane = (int64_t)th * tw, splane = (int64_t)sh * sw;
-    const int x = (int)blockIdx.x * FC_TX + (int)threadIdx.x;
-    if (x >= tw) return;
-    const float px = (float)(tx0 + x), ox = (float)sx0, oy = (float)sy0;
-    for (int y = (int)blockIdx.y * FC_TY + (int)threadIdx.y; y < th; y += (int)gridDim.y * FC_TY) {
-        const int64_t i = (int64_t)y * tw + x;
-        const float py = (float)(ty0 + y);
-        float pfx = 0.f, pfy = 0.f, pc = 0.f, pv = 1.f;
-        if (prev_flow != nullptr) {
-            pfx = prev_flow[i], pfy = prev_flow[plane + i];
-            pc = prev_cost[i], pv = prev_vis[i];
-        }
-        const float qx = px + pfx, qy = py + pfy;
-        const TapAt t = tap_at(sh, sw, qx - ox, qy - oy);
-        float fx = pfx + tap_plane(step_flow, t), fy = pfy + tap_plane(step_flow + splane, t);
-        bool ok = t.valid;
-        float cost = pc + unit_cost, vis = pv;
-        if (step_wlogit != nullptr) {
-            const float l = tap_plane(step_wlogit, t);
-            ok = ok && isfinite(l);
-            cost = pc + softplus_neg(l);
-        }
-        if (step_mlogit != nullptr) {
-            const float m = tap_plane(step_mlogit, t);
-            ok = ok && isfinite(m);
-            vis = pv * sigmoidf_(m);
-        }
-        if constexpr (POST) {
+        if constexpr (FORM == Fold::RECT_POST) {
             const double Px = (double)px, Py = (double)py;
             const double rx = Px + (double)fx, ry = Py + (double)fy;
             const double den = H.h[6] * rx + H.h[7] * ry + H.h[8];
@@ -147,6 +111,31 @@ constexpr unsigned CHAIN_TC_BLOCKS = 2048;        // blocks of a launch with a h
 // WINDOW (woft_chain_tc_window): the planes are the rectangle with origin (tx0, ty0) of a frame_h x frame_w
 // frame and tmask is the cropped mask; dst (window coordinates), w and hist are unchanged, ok is additionally 0 where the landing in
 // FRAME coordinates fails the selection kernels' in-frame rule, so the planar stage needs no bounds check of its own.
+//
+// CHAIN_TC_PIXEL is the pixel work of both kernels below, in their names (flow .. ok, plane, x, y, gw, bin and WINDOW's arguments):
+// pixel (x, y)'s reads, its dst, w and ok stores, and -- where COUNTED, the kernel's own test that a mask holds the pixel -- the
+// counter it adds to, left in `bin`.  The counter is chosen by `seen`, not by the window's gate, so the histograms -- and the
+// ballots and LDS atomics that build them -- see the same lanes and values in both instantiations.  It is text, not a __device__
+// function: through an inlined function (with or without __restrict__, returning the counter, a struct, or taking the test as a
+// callable) this compiler schedules all four kernels differently and spends 2 to 3 more VGPRs on each; as text three of them keep
+// their instruction streams and chain_tc_kernel<true> keeps its instruction count on fewer registers.
+#define CHAIN_TC_PIXEL(COUNTED)                                                                                                    \
+    const int64_t i = (int64_t)y * gw + x;                                                                                         \
+    const float fx = flow[i], fy = flow[plane + i], c = cost[i], v = vis[i];                                                       \
+    const int32_t s = sel[i];                                                                                                      \
+    const bool valid = s >= 0 && s < WOFT_CHAIN_HIST - 2 && isfinite(fx) && isfinite(fy) && isfinite(c) && isfinite(v);            \
+    const bool seen = valid && !(v < vis_thr); /* the fold's occlusion rule */                                                     \
+    dst[i] = valid ? (float)x + fx : NAN;                                                                                          \
+    dst[plane + i] = valid ? (float)y + fy : NAN;                                                                                  \
+    if (w != nullptr) w[i] = valid ? expf(-c) : 0.f;                                                                               \
+    bool gate = seen;                                                                                                              \
+    if constexpr (WINDOW) {                                                                                                        \
+        const float X = (float)(tx0 + x) + fx, Y = (float)(ty0 + y) + fy;                                                          \
+        gate = seen && !(X < 0.f || Y < 0.f || rintf(X) >= frame_w || rintf(Y) >= frame_h);                                        \
+    }                                                                                                                              \
+    ok[i] = gate ? 1.f : 0.f;                                                                                                      \
+    if (COUNTED) bin = !valid ? WOFT_CHAIN_HIST - 2 : (seen ? s : WOFT_CHAIN_HIST - 1)
+
 template <bool WINDOW>
 __global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict__ flow, const float* __restrict__ cost,
                                                         const float* __restrict__ vis, const int32_t* __restrict__ sel,
@@ -165,22 +154,7 @@ __global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict_
     for (int y = (int)blockIdx.y * FC_TY + (int)threadIdx.y; y < gh; y += (int)gridDim.y * FC_TY) {
         int bin = -1;                                 // the counter this lane adds to (-1: none)
         if (in) {
-            const int64_t i = (int64_t)y * gw + x;
-            const float fx = flow[i], fy = flow[plane + i], c = cost[i], v = vis[i];
-            const int32_t s = sel[i];
-            const bool valid = s >= 0 && s < WOFT_CHAIN_HIST - 2 && isfinite(fx) && isfinite(fy) && isfinite(c) && isfinite(v);
-            const bool seen = valid && !(v < vis_thr);                    // the fold's occlusion rule
-            bool gate = seen;
-            if constexpr (WINDOW) {
-                const float X = (float)(tx0 + x) + fx, Y = (float)(ty0 + y) + fy;
-                gate = seen && !(X < 0.f || Y < 0.f || rintf(X) >= frame_w || rintf(Y) >= frame_h);
-            }
-            dst[i] = valid ? (float)x + fx : NAN;
-            dst[plane + i] = valid ? (float)y + fy : NAN;
-            if (w != nullptr) w[i] = valid ? expf(-c) : 0.f;
-            ok[i] = gate ? 1.f : 0.f;
-            if (hist != nullptr && (tmask == nullptr || tmask[(int64_t)y * mw + x] != 0))
-                bin = !valid ? WOFT_CHAIN_HIST - 2 : (seen ? s : WOFT_CHAIN_HIST - 1);
+            CHAIN_TC_PIXEL(hist != nullptr && (tmask == nullptr || tmask[(int64_t)y * mw + x] != 0));
         }
         if (hist != nullptr) {
             // one LDS add per distinct counter of the wave (a frame's pixels mostly agree on it), by the first lane that holds it
@@ -200,13 +174,12 @@ __global__ __launch_bounds__(FC_T) void chain_tc_kernel(const float* __restrict_
     }
 }
 
-// chain_tc_kernel for n_targets masks held as one bit plane: the same pixel work and the same dst, w, ok;
+// chain_tc_kernel for n_targets masks held as one bit plane: CHAIN_TC_PIXEL's work, so the same dst, w, ok;
 // the pixel's counter is the same for every target, its mask bits say which targets count it.  Per distinct counter of the wave,
 // one ballot per target gives that target's number of lanes; lane t keeps target t's, so the wave ends in ONE LDS atomic
 // instruction per distinct counter (lanes 0 .. n_targets-1, one counter each).  LDS: n_targets * 130 counters, 16 640 B at 32.
-// WINDOW (woft_chain_tc_multi_window): chain_tc_kernel<true>'s gate on ok, in its own expression; the planes
-// are the rectangle with origin (tx0, ty0) and tbits is the cropped bit plane.  The counter of a pixel is chosen by `seen`, not by
-// the gate, so the ballots and the LDS atomics below see the same lanes and values in both instantiations.
+// WINDOW (woft_chain_tc_multi_window): the planes are the rectangle with origin (tx0, ty0) and tbits is the
+// cropped bit plane.
 template <bool WINDOW>
 __global__ __launch_bounds__(FC_T) void chain_tc_multi_kernel(const float* __restrict__ flow, const float* __restrict__ cost,
                                                               const float* __restrict__ vis, const int32_t* __restrict__ sel,
@@ -227,22 +200,7 @@ __global__ __launch_bounds__(FC_T) void chain_tc_multi_kernel(const float* __res
         int bin = -1;                                 // the counter this lane adds to (-1: none)
         uint32_t bits = 0;                            // the targets whose mask holds this pixel
         if (in) {
-            const int64_t i = (int64_t)y * gw + x;
-            const float fx = flow[i], fy = flow[plane + i], c = cost[i], v = vis[i];
-            const int32_t s = sel[i];
-            const bool valid = s >= 0 && s < WOFT_CHAIN_HIST - 2 && isfinite(fx) && isfinite(fy) && isfinite(c) && isfinite(v);
-            const bool seen = valid && !(v < vis_thr);                    // the fold's occlusion rule
-            dst[i] = valid ? (float)x + fx : NAN;
-            dst[plane + i] = valid ? (float)y + fy : NAN;
-            if (w != nullptr) w[i] = valid ? expf(-c) : 0.f;
-            bool gate = seen;
-            if constexpr (WINDOW) {
-                const float X = (float)(tx0 + x) + fx, Y = (float)(ty0 + y) + fy;
-                gate = seen && !(X < 0.f || Y < 0.f || rintf(X) >= frame_w || rintf(Y) >= frame_h);
-            }
-            ok[i] = gate ? 1.f : 0.f;
-            bits = tbits[(int64_t)y * mw + x] & live;
-            if (bits != 0) bin = !valid ? WOFT_CHAIN_HIST - 2 : (seen ? s : WOFT_CHAIN_HIST - 1);
+            CHAIN_TC_PIXEL((bits = tbits[(int64_t)y * mw + x] & live) != 0);
         }
         uint64_t todo = __ballot(bin >= 0);
         while (todo != 0) {
@@ -269,37 +227,61 @@ inline bool overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
     return a != nullptr && b != nullptr && pa < pb + nb && pb < pa + na;
 }
 
+// The overlap rule of every entry point below: a pixel's outputs are written while other pixels' inputs are still unread (the fold
+// even gathers them), so no output (outs[a], nout[a] bytes) may share a byte with an input (ins[b], nin[b] bytes) or with another
+// output; a NULL passes.
+template <int N_OUT, int N_IN>
+bool outputs_alias(const void* const (&outs)[N_OUT], const uint64_t (&nout)[N_OUT], const void* const (&ins)[N_IN],
+                   const uint64_t (&nin)[N_IN]) {
+    for (int a = 0; a < N_OUT; ++a) {
+        for (int b = 0; b < N_IN; ++b)
+            if (overlap(outs[a], nout[a], ins[b], nin[b])) return true;
+        for (int b = a + 1; b < N_OUT; ++b)
+            if (overlap(outs[a], nout[a], outs[b], nout[b])) return true;
+    }
+    return false;
+}
+
+// a rectangle's origin and side on one axis: origin >= 0, side >= 1, origin + side <= 2^24 (every coordinate is exact in fp32)
+inline bool bad_span(int32_t origin, int32_t side) { return origin < 0 || side <= 0 || (int64_t)origin + side > FC_MAX_SIDE; }
+
+// What woft_flow_chain_fold and woft_flow_chain_fold_window check alike -- the pointers, the prev triple, the constants, the overlap
+// rule (each plane with its own size) -- and the launch of the form's instantiation; the sides and spans are the caller's.
+int fold_launch(Fold form, const float* prev_flow, const float* prev_cost, const float* prev_vis, int32_t th, int32_t tw, int32_t ty0,
+                int32_t tx0, const float* step_flow, const float* step_wlogit, const float* step_mlogit, int32_t sh, int32_t sw,
+                int32_t sy0, int32_t sx0, const PostH& H, float unit_cost, float vis_thr, int32_t k, int32_t first, float* best_flow,
+                float* best_cost, float* best_vis, int32_t* best_sel, void* stream) {
+    if (!step_flow || !best_flow || !best_cost || !best_vis || !best_sel) return WOFT_EINVAL;
+    const int n_prev = (prev_flow != nullptr) + (prev_cost != nullptr) + (prev_vis != nullptr);
+    if (n_prev != 0 && n_prev != 3) return WOFT_EINVAL;
+    if (!(unit_cost >= 0.f) || !(vis_thr >= 0.f && vis_thr <= 1.f) || k < 0 || k > 127) return WOFT_EINVAL;    // (NaN fails)
+    const uint64_t tb = (uint64_t)th * (uint64_t)tw * 4u, sb = (uint64_t)sh * (uint64_t)sw * 4u;
+    const void* const outs[4] = {best_flow, best_cost, best_vis, best_sel};
+    const uint64_t nout[4] = {2 * tb, tb, tb, tb};
+    const void* const ins[6] = {prev_flow, prev_cost, prev_vis, step_flow, step_wlogit, step_mlogit};
+    const uint64_t nin[6] = {2 * tb, tb, tb, 2 * sb, sb, sb};
+    if (outputs_alias(outs, nout, ins, nin)) return WOFT_EINVAL;
+    // three instantiations: whole frames carry no origin arithmetic, and only a closing homography carries fp64 code
+    auto kernel = form == Fold::FRAME ? flow_chain_fold_kernel<Fold::FRAME>
+                                      : (form == Fold::RECT ? flow_chain_fold_kernel<Fold::RECT> : flow_chain_fold_kernel<Fold::RECT_POST>);
+    hipLaunchKernelGGL(kernel, pixel_grid(th, tw), dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, prev_flow, prev_cost, prev_vis, th, tw,
+                       ty0, tx0, step_flow, step_wlogit, step_mlogit, sh, sw, sy0, sx0, H, unit_cost, vis_thr, k, first != 0, best_flow,
+                       best_cost, best_vis, best_sel);
+    return woft_launch_status();
+}
+
 }  // namespace
 
 extern "C" int woft_flow_chain_fold(const float* prev_flow, const float* prev_cost, const float* prev_vis, const float* step_flow,
                                     const float* step_wlogit, const float* step_mlogit, int32_t h, int32_t w, float unit_cost,
                                     float vis_thr, int32_t k, int32_t first, float* best_flow, float* best_cost, float* best_vis,
                                     int32_t* best_sel, void* stream) {
-    if (!step_flow || !best_flow || !best_cost || !best_vis || !best_sel || bad_side(h, w)) return WOFT_EINVAL;
-    const int n_prev = (prev_flow != nullptr) + (prev_cost != nullptr) + (prev_vis != nullptr);
-    if (n_prev != 0 && n_prev != 3) return WOFT_EINVAL;
-    if (!(unit_cost >= 0.f) || !(vis_thr >= 0.f && vis_thr <= 1.f) || k < 0 || k > 127) return WOFT_EINVAL;    // (NaN fails)
-    // the running best is written while the inputs are still being gathered: it may share no byte with an input or with itself
-    const uint64_t pb = (uint64_t)h * (uint64_t)w * 4u;
-    const void* outs[4] = {best_flow, best_cost, best_vis, best_sel};
-    const void* ins[6] = {prev_flow, prev_cost, prev_vis, step_flow, step_wlogit, step_mlogit};
-    for (int a = 0; a < 4; ++a) {
-        const uint64_t na = a == 0 ? 2 * pb : pb;
-        for (int b = 0; b < 6; ++b)
-            if (overlap(outs[a], na, ins[b], (b == 0 || b == 3) ? 2 * pb : pb)) return WOFT_EINVAL;
-        for (int b = a + 1; b < 4; ++b)
-            if (overlap(outs[a], na, outs[b], pb)) return WOFT_EINVAL;
-    }
-    hipLaunchKernelGGL(flow_chain_fold_kernel, pixel_grid(h, w), dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, prev_flow, prev_cost,
-                       prev_vis, step_flow, step_wlogit, step_mlogit, h, w, unit_cost, vis_thr, k, first != 0, best_flow, best_cost,
-                       best_vis, best_sel);
-    return woft_launch_status();
+    if (bad_side(h, w)) return WOFT_EINVAL;
+    return fold_launch(Fold::FRAME, prev_flow, prev_cost, prev_vis, h, w, 0, 0, step_flow, step_wlogit, step_mlogit, h, w, 0, 0, PostH{},
+                       unit_cost, vis_thr, k, first, best_flow, best_cost, best_vis, best_sel, stream);
 }
 
 namespace {
-
-// a rectangle's origin and side on one axis: origin >= 0, side >= 1, origin + side <= 2^24 (every coordinate is exact in fp32)
-inline bool bad_span(int32_t origin, int32_t side) { return origin < 0 || side <= 0 || (int64_t)origin + side > FC_MAX_SIDE; }
 
 // the checks and the launch of woft_chain_tc and woft_chain_tc_window (WINDOW: the rectangle's origin and the frame's size)
 template <bool WINDOW>
@@ -310,19 +292,12 @@ int chain_tc_launch(const float* flow, const float* cost, const float* vis, cons
     if (WINDOW && (bad_span(ty0, gh) || bad_span(tx0, gw) || bad_side(frame_h, frame_w))) return WOFT_EINVAL;
     if (tmask != nullptr && (mh < gh || mw < gw)) return WOFT_EINVAL;
     if (!(vis_thr >= 0.f && vis_thr <= 1.f)) return WOFT_EINVAL;                                                  // (NaN fails)
-    // every pixel's outputs are written while other pixels' inputs are still unread: an output may share no byte with an input or
-    // with another output (overlap() lets a NULL through)
     const uint64_t pb = (uint64_t)gh * (uint64_t)gw * 4u;
-    const void* outs[4] = {dst, w, ok, hist};
+    const void* const outs[4] = {dst, w, ok, hist};
     const uint64_t nout[4] = {2 * pb, pb, pb, WOFT_CHAIN_HIST * sizeof(int32_t)};
-    const void* ins[5] = {flow, cost, vis, sel, tmask};
+    const void* const ins[5] = {flow, cost, vis, sel, tmask};
     const uint64_t nin[5] = {2 * pb, pb, pb, pb, tmask ? (uint64_t)mh * (uint64_t)mw : 0u};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = 0; b < 5; ++b)
-            if (overlap(outs[a], nout[a], ins[b], nin[b])) return WOFT_EINVAL;
-        for (int b = a + 1; b < 4; ++b)
-            if (overlap(outs[a], nout[a], outs[b], nout[b])) return WOFT_EINVAL;
-    }
+    if (outputs_alias(outs, nout, ins, nin)) return WOFT_EINVAL;
     if (hist != nullptr && hipMemsetAsync(hist, 0, WOFT_CHAIN_HIST * sizeof(int32_t), (hipStream_t)stream) != hipSuccess)
         return WOFT_ELAUNCH;
     // With a histogram every block ends in a few atomics on the same handful of counters, and those serialise: one block per
@@ -364,19 +339,13 @@ int chain_tc_multi_launch(const float* flow, const float* cost, const float* vis
     if (WINDOW && (bad_span(ty0, gh) || bad_span(tx0, gw) || bad_side(frame_h, frame_w))) return WOFT_EINVAL;
     if (mh < gh || mw < gw || n_targets < 1 || n_targets > WOFT_MULTI_MAX_TARGETS) return WOFT_EINVAL;
     if (!(vis_thr >= 0.f && vis_thr <= 1.f)) return WOFT_EINVAL;                                                  // (NaN fails)
-    // as woft_chain_tc: an output may share no byte with an input or with another output (overlap() lets a NULL through)
     const uint64_t pb = (uint64_t)gh * (uint64_t)gw * 4u;
     const uint64_t hist_bytes = (uint64_t)n_targets * WOFT_CHAIN_HIST * sizeof(int32_t);
-    const void* outs[4] = {dst, w, ok, hist};
+    const void* const outs[4] = {dst, w, ok, hist};
     const uint64_t nout[4] = {2 * pb, pb, pb, hist_bytes};
-    const void* ins[5] = {flow, cost, vis, sel, tbits};
+    const void* const ins[5] = {flow, cost, vis, sel, tbits};
     const uint64_t nin[5] = {2 * pb, pb, pb, pb, (uint64_t)mh * (uint64_t)mw * 4u};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = 0; b < 5; ++b)
-            if (overlap(outs[a], nout[a], ins[b], nin[b])) return WOFT_EINVAL;
-        for (int b = a + 1; b < 4; ++b)
-            if (overlap(outs[a], nout[a], outs[b], nout[b])) return WOFT_EINVAL;
-    }
+    if (outputs_alias(outs, nout, ins, nin)) return WOFT_EINVAL;
     if (hipMemsetAsync(hist, 0, hist_bytes, (hipStream_t)stream) != hipSuccess) return WOFT_ELAUNCH;
     // the grid of woft_chain_tc with a histogram: about one resident set of blocks, the row loop does the rest
     dim3 grid = pixel_grid(gh, gw);
@@ -409,11 +378,7 @@ extern "C" int woft_flow_chain_fold_window(const float* prev_flow, const float* 
                                            const float* step_mlogit, int32_t sh, int32_t sw, int32_t sy0, int32_t sx0,
                                            const double* post_H, float unit_cost, float vis_thr, int32_t k, int32_t first,
                                            float* best_flow, float* best_cost, float* best_vis, int32_t* best_sel, void* stream) {
-    if (!step_flow || !best_flow || !best_cost || !best_vis || !best_sel) return WOFT_EINVAL;
     if (bad_span(ty0, th) || bad_span(tx0, tw) || bad_span(sy0, sh) || bad_span(sx0, sw)) return WOFT_EINVAL;
-    const int n_prev = (prev_flow != nullptr) + (prev_cost != nullptr) + (prev_vis != nullptr);
-    if (n_prev != 0 && n_prev != 3) return WOFT_EINVAL;
-    if (!(unit_cost >= 0.f) || !(vis_thr >= 0.f && vis_thr <= 1.f) || k < 0 || k > 127) return WOFT_EINVAL;    // (NaN fails)
     PostH H = {};
     if (post_H != nullptr) {
         for (int j = 0; j < 9; ++j) {
@@ -422,22 +387,8 @@ extern "C" int woft_flow_chain_fold_window(const float* prev_flow, const float* 
         }
         if (post_H[8] != 1.0) return WOFT_EINVAL;
     }
-    // as woft_flow_chain_fold: the running best may share no byte with an input or with itself (each plane with its own size)
-    const uint64_t tb = (uint64_t)th * (uint64_t)tw * 4u, sb = (uint64_t)sh * (uint64_t)sw * 4u;
-    const void* outs[4] = {best_flow, best_cost, best_vis, best_sel};
-    const void* ins[6] = {prev_flow, prev_cost, prev_vis, step_flow, step_wlogit, step_mlogit};
-    const uint64_t nin[6] = {2 * tb, tb, tb, 2 * sb, sb, sb};
-    for (int a = 0; a < 4; ++a) {
-        const uint64_t na = a == 0 ? 2 * tb : tb;
-        for (int b = 0; b < 6; ++b)
-            if (overlap(outs[a], na, ins[b], nin[b])) return WOFT_EINVAL;
-        for (int b = a + 1; b < 4; ++b)
-            if (overlap(outs[a], na, outs[b], tb)) return WOFT_EINVAL;
-    }
-    // two instantiations: the chained candidates (no post_H) carry no fp64 code
-    auto kernel = post_H != nullptr ? flow_chain_fold_window_kernel<true> : flow_chain_fold_window_kernel<false>;
-    hipLaunchKernelGGL(kernel, pixel_grid(th, tw), dim3(FC_TX, FC_TY), 0, (hipStream_t)stream, prev_flow, prev_cost, prev_vis, th, tw,
-                       ty0, tx0, step_flow, step_wlogit, step_mlogit, sh, sw, sy0, sx0, H, unit_cost, vis_thr, k, first != 0, best_flow,
-                       best_cost, best_vis, best_sel);
-    return woft_launch_status();
+    // (the chained candidates, with no post_H, carry no fp64 code)
+    return fold_launch(post_H != nullptr ? Fold::RECT_POST : Fold::RECT, prev_flow, prev_cost, prev_vis, th, tw, ty0, tx0, step_flow,
+                       step_wlogit, step_mlogit, sh, sw, sy0, sx0, H, unit_cost, vis_thr, k, first, best_flow, best_cost, best_vis,
+                       best_sel, stream);
 }

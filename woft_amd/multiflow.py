@@ -43,6 +43,61 @@ def _check_constants(vis_thr, unit_cost):
     return vis_thr, unit_cost
 
 
+def _rect(rect, what):
+    try:
+        y0, x0, rows, cols = (int(v) for v in rect)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: a rectangle is (y0, x0, rows, cols), got {rect!r}") from None
+    if y0 < 0 or x0 < 0 or rows <= 0 or cols <= 0:
+        raise ValueError(f"{what}: origin >= 0 and sides >= 1 are expected, got {rect!r}")
+    return y0, x0, rows, cols
+
+
+def _chain_fold(name, best, prev, step, k, vis_thr, unit_cost, rects=None, post_H=None):
+    """The one body of chain_fold and chain_fold_window (`name`: the caller's, for messages): best / prev / step / k checked and
+    normalised to contiguous fp32 device tensors, the fold, the result on the device of the step's flow.  rects: None (whole
+    frames: every plane has the step flow's size) or (template_rect, step_rect)."""
+    vis_thr, unit_cost = _check_constants(vis_thr, unit_cost)
+    k = int(k)
+    if not 0 <= k <= MAX_DELTA:
+        raise ValueError(f"{name}: k must be in [0, {MAX_DELTA}], got {k}")
+    if rects is not None:
+        trect, srect = _rect(rects[0], "template_rect"), _rect(rects[1], "step_rect")
+    step = tuple(step) if isinstance(step, (tuple, list)) else (step,)
+    if not 1 <= len(step) <= 3:
+        raise ValueError(f"{name}: step is (flow,), (flow, wlogit) or (flow, wlogit, mlogit)")
+    sflow = step[0]
+    if rects is None:
+        if not isinstance(sflow, torch.Tensor) or sflow.dim() != 3 or sflow.shape[0] != 2:
+            raise ValueError(f"{name}: the step's flow must be a (2, H, W) tensor")
+        (h, w), (sh, sw) = sflow.shape[1:], sflow.shape[1:]
+    else:
+        (h, w), (sh, sw) = trect[2:], srect[2:]
+        if not isinstance(sflow, torch.Tensor) or tuple(sflow.shape) != (2, sh, sw):
+            raise ValueError(f"{name}: the step's flow must be a (2, {sh}, {sw}) tensor, the step rectangle's size")
+    n, ns = h * w, sh * sw
+    f = _dev32(sflow, "step flow")
+    logits = [None if t is None else _dev32(t, "step logit", ns) for t in (step + (None, None))[1:3]]
+    if prev is not None:
+        if len(prev) != 3:
+            raise ValueError(f"{name}: prev is None or (flow, cost, vis)")
+        prev = (_dev32(prev[0], "prev flow", 2 * n).reshape(2, h, w), _dev32(prev[1], "prev cost", n), _dev32(prev[2], "prev vis", n))
+    if best is not None:
+        if len(best) != 4 or best[3].dtype != torch.int32 or best[3].numel() != n:
+            raise ValueError(f"{name}: best is None or (flow, cost, vis, sel int32)")
+        # (clones: the fold is in place, the caller's tensors stay as they are)
+        best = (_dev32(best[0], "best flow", 2 * n).reshape(2, h, w).clone(), _dev32(best[1], "best cost", n).clone(),
+                _dev32(best[2], "best vis", n).clone(), best[3].detach().to("cuda").contiguous().clone())
+    common = dict(k=k, vis_thr=vis_thr, unit_cost=unit_cost, first=best is None)
+    if rects is None:
+        bf, bc, bv, bs = ops.flow_chain_fold(best, prev, f, logits[0], logits[1], **common)
+    else:
+        bf, bc, bv, bs = ops.flow_chain_fold_window(best, prev, f, logits[0], logits[1], template_rect=trect, step_rect=srect,
+                                                    post_H=post_H, **common)
+    dev = sflow.device
+    return bf.to(dev), bc.reshape(1, h, w).to(dev), bv.reshape(1, h, w).to(dev), bs.reshape(1, h, w).to(dev)
+
+
 def chain_fold(best, prev, step, k, vis_thr=0.5, unit_cost=1.0):
     """Fold one candidate chain into a running per-pixel best -> (flow (2, H, W), cost (1, H, W), vis (1, H, W),
     sel (1, H, W) int32), new tensors on the device of the step's flow.
@@ -58,34 +113,7 @@ def chain_fold(best, prev, step, k, vis_thr=0.5, unit_cost=1.0):
     the best is empty, or occluded (vis < vis_thr) while the candidate is not, or equally occluded and strictly dearer: ties keep
     the earlier fold.  A pixel without any valid candidate has flow NaN, cost +inf, vis 0, sel -1.
     Host tensors are copied to the device and the result is handed back on their device.  Computed in fp32."""
-    vis_thr, unit_cost = _check_constants(vis_thr, unit_cost)
-    k = int(k)
-    if not 0 <= k <= MAX_DELTA:
-        raise ValueError(f"chain_fold: k must be in [0, {MAX_DELTA}], got {k}")
-    step = tuple(step) if isinstance(step, (tuple, list)) else (step,)
-    if not 1 <= len(step) <= 3:
-        raise ValueError("chain_fold: step is (flow,), (flow, wlogit) or (flow, wlogit, mlogit)")
-    sflow = step[0]
-    if not isinstance(sflow, torch.Tensor) or sflow.dim() != 3 or sflow.shape[0] != 2:
-        raise ValueError("chain_fold: the step's flow must be a (2, H, W) tensor")
-    h, w = sflow.shape[1:]
-    n = h * w
-    f = _dev32(sflow, "step flow")
-    logits = [None if t is None else _dev32(t, "step logit", n) for t in (step + (None, None))[1:3]]
-    if prev is not None:
-        if len(prev) != 3:
-            raise ValueError("chain_fold: prev is None or (flow, cost, vis)")
-        prev = (_dev32(prev[0], "prev flow", 2 * n).reshape(2, h, w), _dev32(prev[1], "prev cost", n), _dev32(prev[2], "prev vis", n))
-    if best is not None:
-        if len(best) != 4 or best[3].dtype != torch.int32 or best[3].numel() != n:
-            raise ValueError("chain_fold: best is None or (flow, cost, vis, sel int32)")
-        # (clones: the fold is in place, the caller's tensors stay as they are)
-        best = (_dev32(best[0], "best flow", 2 * n).reshape(2, h, w).clone(), _dev32(best[1], "best cost", n).clone(),
-                _dev32(best[2], "best vis", n).clone(), best[3].detach().to("cuda").contiguous().clone())
-    bf, bc, bv, bs = ops.flow_chain_fold(best, prev, f, logits[0], logits[1], k=k, vis_thr=vis_thr, unit_cost=unit_cost,
-                                         first=best is None)
-    dev = sflow.device
-    return bf.to(dev), bc.reshape(1, h, w).to(dev), bv.reshape(1, h, w).to(dev), bs.reshape(1, h, w).to(dev)
+    return _chain_fold("chain_fold", best, prev, step, k, vis_thr, unit_cost)
 
 
 class MultiFlowTracker:

@@ -710,74 +710,6 @@ def flow_fb(flow_ab, flow_ba, alpha=0.01, beta=0.5, err=None, ok=None, want_err=
     return err, ok
 
 
-def flow_chain_fold(best, prev, step_flow, step_wlogit=None, step_mlogit=None, k=0, vis_thr=0.5, unit_cost=1.0, first=False):
-    """One candidate chain folded into the running per-pixel best (woft_flow_chain_fold; DESIGN.md section 18).
-    best = (flow (2, H, W), cost, vis (H*W fp32 each), sel (H*W int32)): contiguous device tensors, updated in place and returned;
-    None allocates them (then `first` must be set).  prev = (flow, cost, vis) of the stored result template -> s, or None for
-    the template itself.  step_flow (2, H, W) = the flow s -> t, step_wlogit / step_mlogit (H*W elements each, optional) its
-    reliability and visibility logits.  The candidate's key is (vis < vis_thr, cost); it replaces the best where its key is
-    strictly smaller, sel then holds k.  first: the best is empty and is not read."""
-    assert step_flow.dim() == 3 and step_flow.shape[0] == 2 and _f32c(step_flow)
-    h, w = step_flow.shape[1:]
-    n = h * w
-    plane = lambda t: t is None or (_f32c(t) and t.numel() == n)
-    assert plane(step_wlogit) and plane(step_mlogit)
-    if prev is not None:
-        assert len(prev) == 3 and _f32c(prev[0], 2, h, w) and _f32c(prev[1]) and prev[1].numel() == n and plane(prev[2]) \
-            and prev[2] is not None
-    k, vis_thr, unit_cost = int(k), float(vis_thr), float(unit_cost)
-    if not 0 <= k <= 127:
-        raise ValueError(f"flow_chain_fold: k must be in [0, 127], got {k}")
-    if not (0.0 <= vis_thr <= 1.0) or not (unit_cost >= 0.0):
-        raise ValueError(f"flow_chain_fold: vis_thr must be in [0, 1] and unit_cost >= 0, got {vis_thr!r}, {unit_cost!r}")
-    if best is None:
-        assert first, "flow_chain_fold: without a running best the fold must be the first"
-        new = lambda dtype: torch.empty((h, w), dtype=dtype, device=step_flow.device)
-        best = (torch.empty_like(step_flow), new(torch.float32), new(torch.float32), new(torch.int32))
-    bf, bc, bv, bs = best
-    assert _f32c(bf, 2, h, w) and plane(bc) and plane(bv) and bc is not None and bv is not None
-    assert bs.dtype == torch.int32 and bs.is_contiguous() and bs.is_cuda and bs.numel() == n
-    pf, pc, pv = prev if prev is not None else (None, None, None)
-    check(_lib.load().woft_flow_chain_fold(ptr(pf), ptr(pc), ptr(pv), ptr(step_flow), ptr(step_wlogit), ptr(step_mlogit), h, w,
-                                           unit_cost, vis_thr, k, int(bool(first)), ptr(bf), ptr(bc), ptr(bv), ptr(bs),
-                                           stream_ptr()), "woft_flow_chain_fold")
-    return best
-
-
-CHAIN_HIST = 130        # WOFT_CHAIN_HIST: one counter per candidate index 0..127, [128] invalid, [129] valid but occluded
-
-
-def chain_tc(flow, cost, vis, sel, tmask_u8, vis_thr, want_w=True, mask_hw=None, out=None):
-    """A fold result as correspondences for the planar fit (woft_chain_tc; DESIGN.md section 19) -> (dst (2, n), w (1, n) | None,
-    ok (1, n), hist (130,) int32), n = H * W.  flow (2, H, W), cost, vis (n fp32 each), sel (n int32): contiguous device tensors,
-    what flow_chain_fold leaves.  tmask_u8: the template mask (uint8, mask_hw = (mh, mw) >= (H, W), default the grid's size), or
-    None: every pixel counts in hist.  dst = pixel + flow (NaN where the pixel has no valid chain), w = exp(-cost) (0 there;
-    want_w=False: not computed), ok = 1 where valid and not (vis < vis_thr), hist[s] = masked pixels with ok = 1 and sel = s,
-    hist[128] = masked invalid pixels, hist[129] = masked occluded ones.  out: the tuple of an earlier call at this size, reused."""
-    assert flow.dim() == 3 and flow.shape[0] == 2 and _f32c(flow)
-    h, w = flow.shape[1:]
-    n = h * w
-    assert all(_f32c(t) and t.numel() == n for t in (cost, vis))
-    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.is_cuda and sel.numel() == n
-    vis_thr = float(vis_thr)
-    if not (0.0 <= vis_thr <= 1.0):
-        raise ValueError(f"chain_tc: vis_thr must be in [0, 1], got {vis_thr!r}")
-    mh, mw = mask_hw or (h, w)
-    if tmask_u8 is not None:
-        assert tmask_u8.dtype == torch.uint8 and tmask_u8.is_contiguous() and tmask_u8.is_cuda and tmask_u8.numel() == mh * mw
-    if out is None:
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=flow.device)
-        out = (new(2, n), new(1, n) if want_w else None, new(1, n), torch.empty(CHAIN_HIST, dtype=torch.int32, device=flow.device))
-    dst, wout, ok, hist = out
-    if not want_w:
-        wout = None
-    assert _f32c(dst, 2, n) and _f32c(ok, 1, n) and (wout is None or _f32c(wout, 1, n))
-    assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda and hist.numel() == CHAIN_HIST)
-    check(_lib.load().woft_chain_tc(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tmask_u8), h, w, mh, mw, vis_thr, ptr(dst),
-                                    ptr(wout), ptr(ok), ptr(hist), stream_ptr()), "woft_chain_tc")
-    return dst, wout, ok, hist
-
-
 def _post_h9(post_H):
     """A closing homography -> the 9 doubles woft_flow_chain_fold_window takes (h8 = 1: normalised here); None -> NULL."""
     if post_H is None:
@@ -792,6 +724,56 @@ def _post_h9(post_H):
     return (C.c_double * 9)(*Hm.ravel().tolist())
 
 
+def _flow_chain_fold(name, best, prev, step_flow, step_wlogit, step_mlogit, k, rects, post_H, vis_thr, unit_cost, first):
+    """The one body of flow_chain_fold and flow_chain_fold_window (`name`: the caller's, for messages).  rects: (template_rect,
+    step_rect), or None: whole frames -- every plane has the step flow's size, and the entry point is woft_flow_chain_fold."""
+    assert step_flow.dim() == 3 and step_flow.shape[0] == 2 and _f32c(step_flow)
+    if rects is None:
+        th, tw = sh, sw = step_flow.shape[1:]
+    else:
+        (ty0, tx0, th, tw), (sy0, sx0, sh, sw) = ([int(v) for v in r] for r in rects)
+        assert tuple(step_flow.shape[1:]) == (sh, sw), f"step flow {tuple(step_flow.shape)} is not on the step rect {(sh, sw)}"
+    n, ns = th * tw, sh * sw
+    plane = lambda t, m: t is not None and _f32c(t) and t.numel() == m
+    assert (step_wlogit is None or plane(step_wlogit, ns)) and (step_mlogit is None or plane(step_mlogit, ns))
+    if prev is not None:
+        assert len(prev) == 3 and _f32c(prev[0], 2, th, tw) and plane(prev[1], n) and plane(prev[2], n)
+    k, vis_thr, unit_cost = int(k), float(vis_thr), float(unit_cost)
+    if not 0 <= k <= 127:
+        raise ValueError(f"{name}: k must be in [0, 127], got {k}")
+    if not (0.0 <= vis_thr <= 1.0) or not (unit_cost >= 0.0):
+        raise ValueError(f"{name}: vis_thr must be in [0, 1] and unit_cost >= 0, got {vis_thr!r}, {unit_cost!r}")
+    h9 = None if rects is None else _post_h9(post_H)
+    if best is None:
+        assert first, f"{name}: without a running best the fold must be the first"
+        new = lambda dtype, *s: torch.empty(s, dtype=dtype, device=step_flow.device)
+        best = (new(torch.float32, 2, th, tw), new(torch.float32, th, tw), new(torch.float32, th, tw), new(torch.int32, th, tw))
+    bf, bc, bv, bs = best
+    assert _f32c(bf, 2, th, tw) and plane(bc, n) and plane(bv, n)
+    assert bs.dtype == torch.int32 and bs.is_contiguous() and bs.is_cuda and bs.numel() == n
+    pf, pc, pv = prev if prev is not None else (None, None, None)
+    if rects is None:
+        rc = _lib.load().woft_flow_chain_fold(ptr(pf), ptr(pc), ptr(pv), ptr(step_flow), ptr(step_wlogit), ptr(step_mlogit), th, tw,
+                                              unit_cost, vis_thr, k, int(bool(first)), ptr(bf), ptr(bc), ptr(bv), ptr(bs), stream_ptr())
+    else:
+        rc = _lib.load().woft_flow_chain_fold_window(ptr(pf), ptr(pc), ptr(pv), th, tw, ty0, tx0, ptr(step_flow), ptr(step_wlogit),
+                                                     ptr(step_mlogit), sh, sw, sy0, sx0, h9, unit_cost, vis_thr, k, int(bool(first)),
+                                                     ptr(bf), ptr(bc), ptr(bv), ptr(bs), stream_ptr())
+    check(rc, "woft_" + name)
+    return best
+
+
+def flow_chain_fold(best, prev, step_flow, step_wlogit=None, step_mlogit=None, k=0, vis_thr=0.5, unit_cost=1.0, first=False):
+    """One candidate chain folded into the running per-pixel best (woft_flow_chain_fold; DESIGN.md section 18).
+    best = (flow (2, H, W), cost, vis (H*W fp32 each), sel (H*W int32)): contiguous device tensors, updated in place and returned;
+    None allocates them (then `first` must be set).  prev = (flow, cost, vis) of the stored result template -> s, or None for
+    the template itself.  step_flow (2, H, W) = the flow s -> t, step_wlogit / step_mlogit (H*W elements each, optional) its
+    reliability and visibility logits.  The candidate's key is (vis < vis_thr, cost); it replaces the best where its key is
+    strictly smaller, sel then holds k.  first: the best is empty and is not read."""
+    return _flow_chain_fold("flow_chain_fold", best, prev, step_flow, step_wlogit, step_mlogit, k, None, None, vis_thr, unit_cost,
+                            first)
+
+
 def flow_chain_fold_window(best, prev, step_flow, step_wlogit=None, step_mlogit=None, k=0, template_rect=None, step_rect=None,
                            post_H=None, vis_thr=0.5, unit_cost=1.0, first=False):
     """flow_chain_fold on two rectangles (woft_flow_chain_fold_window).  template_rect = (y0, x0, rows, cols):
@@ -799,64 +781,11 @@ def flow_chain_fold_window(best, prev, step_flow, step_wlogit=None, step_mlogit=
     for step_flow (2, rows, cols) and the step's logits, the same rectangle of frames s and t.  Flows are displacements in frame
     coordinates.  post_H (3 x 3, optional): the candidate's landing is mapped through it in fp64 (normalised to h8 = 1 here).
     best = None allocates the running best (then `first` must be set); it is updated in place and returned."""
-    assert step_flow.dim() == 3 and step_flow.shape[0] == 2 and _f32c(step_flow)
-    sy0, sx0, sh, sw = (int(v) for v in step_rect)
-    ty0, tx0, th, tw = (int(v) for v in template_rect)
-    assert tuple(step_flow.shape[1:]) == (sh, sw), f"step flow {tuple(step_flow.shape)} is not on the step rect {(sh, sw)}"
-    n, ns = th * tw, sh * sw
-    plane = lambda t, m: t is None or (_f32c(t) and t.numel() == m)
-    assert plane(step_wlogit, ns) and plane(step_mlogit, ns)
-    if prev is not None:
-        assert len(prev) == 3 and _f32c(prev[0], 2, th, tw) and prev[1] is not None and prev[2] is not None \
-            and plane(prev[1], n) and plane(prev[2], n)
-    k, vis_thr, unit_cost = int(k), float(vis_thr), float(unit_cost)
-    if not 0 <= k <= 127:
-        raise ValueError(f"flow_chain_fold_window: k must be in [0, 127], got {k}")
-    if not (0.0 <= vis_thr <= 1.0) or not (unit_cost >= 0.0):
-        raise ValueError(f"flow_chain_fold_window: vis_thr must be in [0, 1] and unit_cost >= 0, got {vis_thr!r}, {unit_cost!r}")
-    h9 = _post_h9(post_H)
-    if best is None:
-        assert first, "flow_chain_fold_window: without a running best the fold must be the first"
-        new = lambda dtype, *s: torch.empty(s, dtype=dtype, device=step_flow.device)
-        best = (new(torch.float32, 2, th, tw), new(torch.float32, th, tw), new(torch.float32, th, tw), new(torch.int32, th, tw))
-    bf, bc, bv, bs = best
-    assert _f32c(bf, 2, th, tw) and bc is not None and bv is not None and plane(bc, n) and plane(bv, n)
-    assert bs.dtype == torch.int32 and bs.is_contiguous() and bs.is_cuda and bs.numel() == n
-    pf, pc, pv = prev if prev is not None else (None, None, None)
-    check(_lib.load().woft_flow_chain_fold_window(ptr(pf), ptr(pc), ptr(pv), th, tw, ty0, tx0, ptr(step_flow), ptr(step_wlogit),
-                                                  ptr(step_mlogit), sh, sw, sy0, sx0, h9, unit_cost, vis_thr, k, int(bool(first)),
-                                                  ptr(bf), ptr(bc), ptr(bv), ptr(bs), stream_ptr()), "woft_flow_chain_fold_window")
-    return best
+    return _flow_chain_fold("flow_chain_fold_window", best, prev, step_flow, step_wlogit, step_mlogit, k, (template_rect, step_rect),
+                            post_H, vis_thr, unit_cost, first)
 
 
-def chain_tc_window(flow, cost, vis, sel, tmask_u8, vis_thr, origin, frame_hw, want_w=True, mask_hw=None, out=None):
-    """chain_tc on a template rectangle (woft_chain_tc_window; DESIGN.md section 26): flow (2, H, W) etc. are the planes of the
-    rectangle with origin = (y0, x0) in a frame of frame_hw = (frame_h, frame_w); tmask_u8 is the CROPPED mask (mask_hw >= (H, W),
-    default the grid's size).  dst (window coordinates), w and hist are chain_tc's bytes; ok is additionally 0 where the landing
-    leaves the frame (the selection kernels' rule in frame coordinates)."""
-    assert flow.dim() == 3 and flow.shape[0] == 2 and _f32c(flow)
-    h, w = flow.shape[1:]
-    n = h * w
-    assert all(_f32c(t) and t.numel() == n for t in (cost, vis))
-    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.is_cuda and sel.numel() == n
-    vis_thr = float(vis_thr)
-    if not (0.0 <= vis_thr <= 1.0):
-        raise ValueError(f"chain_tc_window: vis_thr must be in [0, 1], got {vis_thr!r}")
-    mh, mw = mask_hw or (h, w)
-    if tmask_u8 is not None:
-        assert tmask_u8.dtype == torch.uint8 and tmask_u8.is_contiguous() and tmask_u8.is_cuda and tmask_u8.numel() == mh * mw
-    if out is None:
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=flow.device)
-        out = (new(2, n), new(1, n) if want_w else None, new(1, n), torch.empty(CHAIN_HIST, dtype=torch.int32, device=flow.device))
-    dst, wout, ok, hist = out
-    if not want_w:
-        wout = None
-    assert _f32c(dst, 2, n) and _f32c(ok, 1, n) and (wout is None or _f32c(wout, 1, n))
-    assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda and hist.numel() == CHAIN_HIST)
-    check(_lib.load().woft_chain_tc_window(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tmask_u8), h, w, mh, mw, int(origin[0]),
-                                           int(origin[1]), int(frame_hw[0]), int(frame_hw[1]), vis_thr, ptr(dst), ptr(wout),
-                                           ptr(ok), ptr(hist), stream_ptr()), "woft_chain_tc_window")
-    return dst, wout, ok, hist
+CHAIN_HIST = 130        # WOFT_CHAIN_HIST: one counter per candidate index 0..127, [128] invalid, [129] valid but occluded
 
 
 MULTI_MAX_TARGETS = 32  # WOFT_MULTI_MAX_TARGETS: the targets of one bit plane (uint32 per pixel)
@@ -869,12 +798,10 @@ def _check_tbits(tbits, mh, mw, n_targets):
     assert tbits.dtype == torch.int32 and tbits.is_contiguous() and tbits.is_cuda and tbits.numel() == mh * mw
 
 
-def chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=True, mask_hw=None, out=None, _window=None):
-    """chain_tc for n_targets template masks at once (woft_chain_tc_multi; DESIGN.md section 25) -> (dst (2, n), w (1, n) | None,
-    ok (1, n), hist (n_targets, 130) int32).  tbits: the masks as one bit plane, an int32 device tensor of mask_hw = (mh, mw) >=
-    (H, W) elements (default the grid's size), bit t set where the pixel lies in target t's mask.  dst, w, ok: chain_tc's bytes;
-    hist[t]: chain_tc's for a uint8 mask equal to bit t.  out: the tuple of an earlier call at this size, reused (its hist may
-    be a view into a larger result block).  (_window: chain_tc_multi_window's (y0, x0, frame_h, frame_w), below.)"""
+def _chain_tc(name, flow, cost, vis, sel, mask, n_targets, vis_thr, window, want_w, mask_hw, out):
+    """The one body of chain_tc, chain_tc_window, chain_tc_multi and chain_tc_multi_window (`name`: the caller's, for messages
+    and for its entry point woft_<name>).  mask: with n_targets None the uint8 template mask or None, else the int32 bit plane of
+    n_targets masks.  window: None, or the rectangle forms' (origin, frame_hw)."""
     assert flow.dim() == 3 and flow.shape[0] == 2 and _f32c(flow)
     h, w = flow.shape[1:]
     n = h * w
@@ -882,26 +809,66 @@ def chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=True,
     assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.is_cuda and sel.numel() == n
     vis_thr = float(vis_thr)
     if not (0.0 <= vis_thr <= 1.0):
-        raise ValueError(f"chain_tc_multi: vis_thr must be in [0, 1], got {vis_thr!r}")
+        raise ValueError(f"{name}: vis_thr must be in [0, 1], got {vis_thr!r}")
     mh, mw = mask_hw or (h, w)
-    _check_tbits(tbits, mh, mw, n_targets)
+    multi = n_targets is not None
+    if multi:
+        _check_tbits(mask, mh, mw, n_targets)
+    elif mask is not None:
+        assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.is_cuda and mask.numel() == mh * mw
+    hist_shape = (n_targets, CHAIN_HIST) if multi else (CHAIN_HIST,)
     if out is None:
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=flow.device)
-        out = (new(2, n), new(1, n) if want_w else None, new(1, n),
-               torch.empty(n_targets, CHAIN_HIST, dtype=torch.int32, device=flow.device))
+        out = (new(2, n), new(1, n) if want_w else None, new(1, n), torch.empty(hist_shape, dtype=torch.int32, device=flow.device))
     dst, wout, ok, hist = out
     if not want_w:
         wout = None
     assert _f32c(dst, 2, n) and _f32c(ok, 1, n) and (wout is None or _f32c(wout, 1, n))
-    assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda and hist.numel() == n_targets * CHAIN_HIST
-    if _window is not None:
-        check(_lib.load().woft_chain_tc_multi_window(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tbits), h, w, mh, mw, int(n_targets),
-                                                     *_window, vis_thr, ptr(dst), ptr(wout), ptr(ok), ptr(hist), stream_ptr()),
-              "woft_chain_tc_multi_window")
-        return dst, wout, ok, hist
-    check(_lib.load().woft_chain_tc_multi(ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(tbits), h, w, mh, mw, int(n_targets), vis_thr,
-                                          ptr(dst), ptr(wout), ptr(ok), ptr(hist), stream_ptr()), "woft_chain_tc_multi")
+    # (a single mask may go without a histogram; a multi-target one may be a view into a larger result block)
+    assert hist is not None or not multi, f"{name}: a histogram is required"
+    assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.is_cuda
+                            and hist.numel() == (n_targets if multi else 1) * CHAIN_HIST)
+    lib, planes = _lib.load(), (ptr(flow), ptr(cost), ptr(vis), ptr(sel), ptr(mask), h, w, mh, mw)
+    outs = (vis_thr, ptr(dst), ptr(wout), ptr(ok), ptr(hist), stream_ptr())
+    if window is not None:
+        rect = (int(window[0][0]), int(window[0][1]), int(window[1][0]), int(window[1][1]))
+    if multi and window is not None:
+        rc = lib.woft_chain_tc_multi_window(*planes, int(n_targets), *rect, *outs)
+    elif multi:
+        rc = lib.woft_chain_tc_multi(*planes, int(n_targets), *outs)
+    elif window is not None:
+        rc = lib.woft_chain_tc_window(*planes, *rect, *outs)
+    else:
+        rc = lib.woft_chain_tc(*planes, *outs)
+    check(rc, "woft_" + name)
     return dst, wout, ok, hist
+
+
+def chain_tc(flow, cost, vis, sel, tmask_u8, vis_thr, want_w=True, mask_hw=None, out=None):
+    """A fold result as correspondences for the planar fit (woft_chain_tc; DESIGN.md section 19) -> (dst (2, n), w (1, n) | None,
+    ok (1, n), hist (130,) int32), n = H * W.  flow (2, H, W), cost, vis (n fp32 each), sel (n int32): contiguous device tensors,
+    what flow_chain_fold leaves.  tmask_u8: the template mask (uint8, mask_hw = (mh, mw) >= (H, W), default the grid's size), or
+    None: every pixel counts in hist.  dst = pixel + flow (NaN where the pixel has no valid chain), w = exp(-cost) (0 there;
+    want_w=False: not computed), ok = 1 where valid and not (vis < vis_thr), hist[s] = masked pixels with ok = 1 and sel = s,
+    hist[128] = masked invalid pixels, hist[129] = masked occluded ones.  out: the tuple of an earlier call at this size, reused."""
+    return _chain_tc("chain_tc", flow, cost, vis, sel, tmask_u8, None, vis_thr, None, want_w, mask_hw, out)
+
+
+def chain_tc_window(flow, cost, vis, sel, tmask_u8, vis_thr, origin, frame_hw, want_w=True, mask_hw=None, out=None):
+    """chain_tc on a template rectangle (woft_chain_tc_window; DESIGN.md section 26): flow (2, H, W) etc. are the planes of the
+    rectangle with origin = (y0, x0) in a frame of frame_hw = (frame_h, frame_w); tmask_u8 is the CROPPED mask (mask_hw >= (H, W),
+    default the grid's size).  dst (window coordinates), w and hist are chain_tc's bytes; ok is additionally 0 where the landing
+    leaves the frame (the selection kernels' rule in frame coordinates)."""
+    return _chain_tc("chain_tc_window", flow, cost, vis, sel, tmask_u8, None, vis_thr, (origin, frame_hw), want_w, mask_hw, out)
+
+
+def chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=True, mask_hw=None, out=None):
+    """chain_tc for n_targets template masks at once (woft_chain_tc_multi; DESIGN.md section 25) -> (dst (2, n), w (1, n) | None,
+    ok (1, n), hist (n_targets, 130) int32).  tbits: the masks as one bit plane, an int32 device tensor of mask_hw = (mh, mw) >=
+    (H, W) elements (default the grid's size), bit t set where the pixel lies in target t's mask.  dst, w, ok: chain_tc's bytes;
+    hist[t]: chain_tc's for a uint8 mask equal to bit t.  out: the tuple of an earlier call at this size, reused (its hist may
+    be a view into a larger result block)."""
+    return _chain_tc("chain_tc_multi", flow, cost, vis, sel, tbits, n_targets, vis_thr, None, want_w, mask_hw, out)
 
 
 def chain_tc_multi_window(flow, cost, vis, sel, tbits, n_targets, vis_thr, origin, frame_hw, want_w=True, mask_hw=None, out=None):
@@ -909,8 +876,8 @@ def chain_tc_multi_window(flow, cost, vis, sel, tbits, n_targets, vis_thr, origi
     rectangle with origin = (y0, x0) in a frame of frame_hw = (frame_h, frame_w); tbits is the bit plane CROPPED to the rectangle
     (mask_hw >= (H, W), default the grid's size).  dst (window coordinates), w and hist are chain_tc_multi's bytes; ok is
     additionally 0 where the landing leaves the frame: dst, w, ok are chain_tc_window's bytes, hist[t] its histogram for bit t."""
-    return chain_tc_multi(flow, cost, vis, sel, tbits, n_targets, vis_thr, want_w=want_w, mask_hw=mask_hw, out=out,
-                          _window=(int(origin[0]), int(origin[1]), int(frame_hw[0]), int(frame_hw[1])))
+    return _chain_tc("chain_tc_multi_window", flow, cost, vis, sel, tbits, n_targets, vis_thr, (origin, frame_hw), want_w, mask_hw,
+                     out)
 
 
 def coords_update(coords, delta, ld_delta, wf, flow4=None, flow_cat=None, ld_cat=0):
